@@ -14,8 +14,11 @@ N > 1 (launched by torch.distributed.run, one rank per GPU):
                                chromosomes -> ONE RCCL all-gather of the segment boundaries -> global segment ids.  "scaling": "strong".
     --multi cohort             one sample per rank, no data-path collective.  "scaling": "weak".
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (dominant HBM kernel, hipEvent-timed inside the library on its own stream), "cpu_baseline" (the CPU
-oracle on this box's host cores, whole genome, no extrapolation; rank 0, N = 1 only), "h2d", "packed_path", "cbs_path", "wavelets_path", "somatic_flow" (BASELINE configs[4]), "pedigree_flow" (BASELINE configs[3]).
+Prints ONE JSON line (rank 0).  A plain run (N = 1 or --multi cohort) sets up, warms up, times --steps passes and prints the headline figure (value, ms_per_step,
+config); everything else it can measure or check runs only with --full.  Extra objects of --full: "roofline" (dominant HBM kernel, hipEvent-timed inside the library
+on its own stream), "cpu_baseline" (the CPU oracle on this box's host cores, whole genome, no extrapolation; rank 0, N = 1 only), "h2d", "packed_path", "cbs_path",
+"wavelets_path", "somatic_flow" (BASELINE configs[4]), "pedigree_flow" (BASELINE configs[3]); the --no-* options leave single legs out of it.
+--dump-outputs DIR writes what the last timed pass returned (see dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -30,6 +33,7 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # read by the HIP runtime at its first call: CBS keeps more than 4 kernels in flight.  8, not 16 (round 6): every hardware queue the
                                                     # runtime creates costs ~5 ms at the first streams and again at exit — 16: first CBS call 0.27-0.32 s, 8: 0.17-0.21, 4: 0.12; the warm tumour / normal CBS 0.39-0.40 / 0.40-0.41 / 0.41 s
 
+DUMP_BINS, DUMP_SEED = 1_000_000, 20260927   # --dump-outputs: per-bin columns at most at this many bins (~56 MB in all), sampled with this seed
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured float4 copy)
 
 
@@ -52,7 +56,15 @@ def main():
     ap.add_argument("--no-cbs", action="store_true", help="skip the (untimed) CBS run on the cleaned coverage that is reported as cbs_path")
     ap.add_argument("--no-pedigree", action="store_true", help="skip the trio flow of BASELINE configs[3] that is reported as pedigree_flow")
     ap.add_argument("--no-somatic", action="store_true", help="skip the tumour / normal flow of BASELINE configs[4] that is reported as somatic_flow")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: roofline and per-stage device times, the cohort Clean and every leg the --no-* options "
+                                                         "name (off: set up, warm up, time --steps passes, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed passes, write what the last one returned as DIR/<name>.npy (float32 / float64, a fixed sample of "
+                                                          "the per-bin columns when the genome has more than %d bins)" % DUMP_BINS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 and args.multi == "sharded" or os.environ.get("CANVAS_BENCH_FORCE_SHARDED")):
+        ap.error("--dump-outputs writes the results of the single-sample path (--gpus 1 or --multi cohort), not those of the sharded one")
     launch_ranks_if_asked(args)
 
     import torch
@@ -84,7 +96,7 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
     cv = Canvas(local_rank)
     cv.profile_enable(True)
-    if world == 1 and not (args.no_cbs and args.no_somatic):
+    if world == 1 and args.full and not (args.no_cbs and args.no_somatic):
         # what INTEGRATION.md tells a host to do right behind canvas_create (and CanvasPartition -m CBS does during its file read): the draw streams of CBS are constants of
         # the method — the library starts generating them, and creates its launchers' streams, on a thread of its own while the host is busy with something else
         cv.cbs_prefetch(len(synth.GRCH38), 16 << 20)
@@ -134,6 +146,7 @@ def main():
             r = cv.sample_pipeline(bases, masks, hits, lens, is_auto, out, cov_buf, state_buf, seg_buf, counts_per_bin=100, bin_size=-1, mode=3, flags=flags,
                                    prepared=keep.get("prepared"))
             keep["prepared"] = r["prepared"]          # the marshalled pointer tables of the (unchanged) input arrays
+            keep["last"] = r                          # what the call returned besides the arrays it filled (bin size, counts, offsets)
             cv.synchronize()
             return r["total"]
         tp = time.perf_counter()
@@ -152,6 +165,7 @@ def main():
         seg, nseg = cv.segment_ids(off_h, state, out["start"], out["stop"], out=seg_buf)
         tp = tick("segment_ids", tp)
         cv.synchronize()
+        keep["last"] = dict(bin_size=bs, total=total, n_out=n_out, lsd=lsd, off=off_h, nseg=nseg)
         if record:
             keep.update(bin_size=bs, total=total, n_out=n_out, lsd=lsd, info=info, cov=cov.clone(), off=off_h, state=state.clone(), seg=seg.clone(), nseg=nseg,
                         cleaned={k: v[:n_out].clone() for k, v in out.items()})
@@ -178,6 +192,21 @@ def main():
         bins_step = step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, keep["last"], out, cov_buf, state_buf, seg_buf)
+    if not args.full:
+        from canvas_amd import parallel
+        dt, total_bins_all, _ = parallel.aggregate_throughput(dt, float(bins_step), device=device)   # MAX over ranks, SUM of bins
+        result = headline(args, world, total_bins_all / (dt / args.steps), dt / args.steps * 1e3, total_bases, keep["last"])
+        if rank == 0:
+            if args.stage_times:
+                print("stage times (ms, host wall incl. sync): " + json.dumps(stage), file=sys.stderr)
+            result["summary"] = {"ms_per_step": result["ms_per_step"], "value": result["value"]}
+            print(json.dumps(result), flush=True)
+        cv.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     ms_bin, k_bin = cv.profile_get("bin_pass")
     ms_stats, k_stats = cv.profile_get("bin_tile_stats")
     ms_sum, k_sum = cv.profile_get("bin_summary")
@@ -266,14 +295,8 @@ def main():
         if abs(tj.get("scale", -1) - args.scale) < 1e-9 and abs(tj.get("rate", -1) - args.rate) < 1e-9:
             roofline["idle_us_per_pass"] = tj["idle_us"]; roofline["idle_source"] = "profiles/pass_timeline.json (rocprofv3 --kernel-trace of this command, git head %s: span %.0f us, busy %.0f us; the run's own figure is hand_over_us_per_pass)" % (tj.get("git_head", "?"), tj["span_us"], tj["busy_us"])
 
-    result = {"metric": "genome-bins/sec (bin+clean+partition)", "value": round(value, 1), "unit": "bins/s", "n_gpus": world, "steps": args.steps,
-              "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-              "dtype": "u8/int32 (bin), f32/f64 (clean, viterbi)", "data": "synthetic",
-              "config": {"workload": "BASELINE configs[2]: whole-genome GRCh38 60x single sample, full bin+clean+partition HIP path on 1 MI355X per sample",
-                         "bases_per_sample": total_bases, "bins_per_sample": int(keep["total"]), "bins_after_clean": int(keep["n_out"]), "bin_size": int(keep["bin_size"]),
-                         "partition": "PerSampleHMM", "clean_flags": "-g -s -r --local-sd-metric-file", "segments": int(keep["nseg"]),
-                         "samples": world, "scale": args.scale, "rate": args.rate, "multi": "cohort" if world > 1 else None},
-              "roofline": roofline}
+    result = headline(args, world, value, ms_per_step, total_bases, keep)
+    result["roofline"] = roofline
 
     if rank == 0 and world == 1:
         # CanvasClean on a cohort (canvas_clean_batch): B copies of this sample's bins, every copy on its own stream.  The single-sample stage is a chain of ~60
@@ -428,6 +451,37 @@ def main():
     cv.close()              # streams, engines and workspaces go while the runtime is still up (not from __del__ at interpreter shutdown)
     if world > 1:
         dist.destroy_process_group()
+
+
+def headline(args, world, value, ms_per_step, total_bases, r):
+    """the fields every line carries; r: what canvas_sample_pipeline returned for a pass (bin_size, total, n_out, nseg)"""
+    return {"metric": "genome-bins/sec (bin+clean+partition)", "value": round(value, 1), "unit": "bins/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u8/int32 (bin), f32/f64 (clean, viterbi)", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[2]: whole-genome GRCh38 60x single sample, full bin+clean+partition HIP path on 1 MI355X per sample",
+                       "bases_per_sample": total_bases, "bins_per_sample": int(r["total"]), "bins_after_clean": int(r["n_out"]), "bin_size": int(r["bin_size"]),
+                       "partition": "PerSampleHMM", "clean_flags": "-g -s -r --local-sd-metric-file", "segments": int(r["nseg"]),
+                       "samples": world, "scale": args.scale, "rate": args.rate, "multi": "cohort" if world > 1 else None}}
+
+
+def dump_outputs(d, torch, r, out, cov, state, seg):
+    """--dump-outputs DIR: what the last timed pass handed its caller, as DIR/<name>.npy.  The per-bin results of the cleaned bins (bins_chr, bins_start, bins_stop,
+    bins_gc, bins_count, coverage (F2 hand-off), state (PerSampleHMM), segment_id) are taken at the same bins: all of them up to DUMP_BINS, beyond that a fixed seeded
+    sample (bin_index says which, ascending).  bin_size, bins_total, bins_after_clean, local_sd, segments and chr_offset are written whole.  Integer results are stored
+    exactly: as float32 below 2^24, as float64 otherwise."""
+    os.makedirs(d, exist_ok=True)
+    n = int(r["n_out"])
+    idx = np.arange(n) if n <= DUMP_BINS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_BINS, replace=False))
+    di = torch.from_numpy(idx).to(cov.device)
+    cols = {"bins_chr": (out["chr"], np.float32), "bins_start": (out["start"], np.float64), "bins_stop": (out["stop"], np.float64), "bins_gc": (out["gc"], np.float32),
+            "bins_count": (out["count"], np.float32), "coverage": (cov, np.float64), "state": (state, np.float32), "segment_id": (seg, np.float64)}
+    arrays = {name: t[di].cpu().numpy().astype(dt) for name, (t, dt) in cols.items()}
+    arrays["bin_index"] = idx.astype(np.float64)
+    for name, key in (("bin_size", "bin_size"), ("bins_total", "total"), ("bins_after_clean", "n_out"), ("local_sd", "lsd"), ("segments", "nseg")):
+        arrays[name] = np.array([r[key]], np.float64)
+    arrays["chr_offset"] = np.asarray(r["off"], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def ONE_GPU_HOOK():

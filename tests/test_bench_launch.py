@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +25,31 @@ def test_gpus_n_refuses_when_the_box_has_fewer_devices():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "64", "--steps", "1", "--warmup", "0"], env=_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 2, (p.returncode, p.stderr[-2000:])
     assert "needs 64 visible GPUs" in p.stderr and "{" not in p.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_pass(tmp_path):
+    """a plain run times --steps passes and prints the headline only (the other legs belong to --full); --dump-outputs writes what the last timed pass returned,
+    the same files for the same arguments"""
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / ("d%d" % i)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "0.02", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                           env=_env(), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
+        lines.append(json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1]))
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    j = lines[0]
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and j["higher_is_better"] is True
+    assert not any(k in j for k in ("roofline", "cbs_path", "wavelets_path", "cpu_baseline", "h2d", "packed_path", "somatic_flow", "pedigree_flow"))
+    a, b = dumps
+    assert sorted(a) == sorted(b) and all(a[f].dtype in (np.float32, np.float64) and a[f].tobytes() == b[f].tobytes() for f in a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    n = int(a["bins_after_clean.npy"][0])
+    assert n == j["config"]["bins_after_clean"] and int(a["segments.npy"][0]) == j["config"]["segments"] and int(a["bin_size.npy"][0]) == j["config"]["bin_size"]
+    assert len(a["coverage.npy"]) == min(n, 1_000_000) and a["chr_offset.npy"][-1] == n
+    assert (np.diff(a["bin_index.npy"]) > 0).all() and (np.diff(a["bins_chr.npy"]) >= 0).all() and (a["bins_stop.npy"] > a["bins_start.npy"]).all()
+    assert all((a[f] == np.round(a[f])).all() for f in ("state.npy", "segment_id.npy", "bins_gc.npy"))
 
 
 @pytest.mark.gpu

@@ -3,7 +3,7 @@
 # wall time by the caller's clock against the tool's own total.  usage: tools/cbs_exit_probe.sh
 export CANVAS_TEST_HOOKS=1
 export CANVAS_EXE_KEEP=/tmp/exe_root.txt
-python bench.py --no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-gc-only --no-pedigree --steps 2 --warmup 1 > gpurun_out/exe.log 2>&1
+python bench.py --full --no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-gc-only --no-pedigree --steps 2 --warmup 1 > /tmp/exe.log 2>&1
 root=$(cat /tmp/exe_root.txt); mkdir -p $root/WholeGenomeFasta
 run() {
   for i in 1 2 3; do

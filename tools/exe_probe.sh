@@ -2,10 +2,10 @@
 # experiments on the one-shot executables: bench.py's executables leg with the sample's files kept, then CanvasBin timed under a few environment settings
 export CANVAS_TEST_HOOKS=1      # (the library reads its CANVAS_* switches only with this set)
 export CANVAS_EXE_KEEP=/tmp/exe_root.txt
-python bench.py --no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-gc-only --no-pedigree --steps 2 --warmup 1 > gpurun_out/exe.log 2>&1
+python bench.py --full --no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-gc-only --no-pedigree --steps 2 --warmup 1 > /tmp/exe.log 2>&1
 python - <<PY
 import json
-for l in open("gpurun_out/exe.log"):
+for l in open("/tmp/exe.log"):
     if l.startswith("{"):
         d=json.loads(l)["executables"]
         for k,v in d.items():

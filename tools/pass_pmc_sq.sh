@@ -2,7 +2,7 @@
 # SQ counters of the kernels of one bench pass (two rocprofv3 --pmc runs, counters only): gpurun_out/<tag>/pmc_sq_pass.txt, pmc_lds_pass.txt.  usage: tools/pass_pmc_sq.sh <tag>
 tag=${1:-sq}; R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$tag; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-OFF="--no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree --steps 3 --warmup 1"
+OFF="--full --no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree --steps 3 --warmup 1"
 rm -rf /tmp/pq1 /tmp/pq2
 timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAVES --output-format csv -d /tmp/pq1 -o g -- python $R/bench.py $OFF > /tmp/pq1.log 2>&1; echo "sq rc $?"
 python $R/tools/pmc_sq_summary.py $(find /tmp/pq1 -name "*counter_collection.csv" | head -n 1) > $O/pmc_sq_pass.txt 2>&1

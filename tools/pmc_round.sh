@@ -6,7 +6,7 @@
 export CANVAS_TEST_HOOKS=1
 tag=${1:-pmc}; head=${2:-unknown}; R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$tag; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-OFF="--no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-executables --no-gc-only --no-pedigree"
+OFF="--full --no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-executables --no-gc-only --no-pedigree"
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$c; timeout 400 rocprofv3 --pmc $c --output-format csv -d /tmp/pmc_$c -o p -- python $R/bench.py $OFF --steps 1 --warmup 0 > /tmp/pmc_$c.log 2>&1; echo "pass $c rc $?"
 done

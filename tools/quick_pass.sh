@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$tag; mkdir -p $O
 cd $R
 if [ -n "$sel" ]; then timeout 900 python -m pytest tests -m gpu -x -q -k "$sel" 2>&1 | tail -15 > $O/tests.txt; cat $O/tests.txt; fi
 cd /tmp; export TMPDIR=/tmp
-FLAGS="--no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree"
+FLAGS="--full --no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree"
 timeout 300 python $R/bench.py $FLAGS --steps 20 --warmup 5 "$@" > $O/bench_plain.log 2>&1; echo "bench rc $?"; tail -c 1500 $O/bench_plain.log | python -c "
 import sys,json
 for l in sys.stdin.read().splitlines()[::-1]:

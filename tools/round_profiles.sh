@@ -6,9 +6,9 @@ export CANVAS_TEST_HOOKS=1      # (the library reads its CANVAS_* switches only 
 tag=${1:-rXX}; mins=${2:-6}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$tag; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof1 -o pass -- python $R/bench.py --no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree --steps 5 --warmup 2 > /tmp/bench_prof.log 2>&1; echo "pass profile rc $?"
+timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof1 -o pass -- python $R/bench.py --full --no-cpu-baseline --no-cbs --no-wavelets --no-somatic --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree --steps 5 --warmup 2 > /tmp/bench_prof.log 2>&1; echo "pass profile rc $?"
 db=$(find /tmp/prof1 -name "*.db" | head -1); (cd $R; python tools/rocprof_summary.py $db $O/kernel_stats.txt /tmp/bench_prof.log > /dev/null; python tools/timeline.py $db > $O/pass_timeline.txt 2>&1)
-timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof2 -o som -- python $R/bench.py --no-cpu-baseline --no-cbs --no-wavelets --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree --steps 1 --warmup 0 > /tmp/som.log 2>&1; echo "somatic profile rc $?"
+timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof2 -o som -- python $R/bench.py --full --no-cpu-baseline --no-cbs --no-wavelets --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree --steps 1 --warmup 0 > /tmp/som.log 2>&1; echo "somatic profile rc $?"
 db=$(find /tmp/prof2 -name "*.db" | head -1); (cd $R; python tools/rocprof_summary.py $db $O/somatic_kernel_stats.txt /tmp/som.log > /dev/null)
 timeout 200 rocprofv3 --kernel-trace --stats -d /tmp/prof3 -o cbs -- python $R/tools/cbs_time.py 4700000 2 > /tmp/cbs.log 2>&1; echo "cbs profile rc $?"
 db=$(find /tmp/prof3 -name "*.db" | head -1); (cd $R; python tools/rocprof_summary.py $db $O/cbs_kernel_stats.txt > /dev/null; echo "# $(tail -1 /tmp/cbs.log)" >> $O/cbs_kernel_stats.txt)

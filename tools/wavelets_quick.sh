@@ -3,7 +3,7 @@
 export CANVAS_TEST_HOOKS=1      # (the library reads its CANVAS_* switches only with this set)
 tag=${1:-wv}; shift; R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$tag; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-FLAGS="--no-cpu-baseline --no-cbs --no-somatic --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree --steps 1 --warmup 0"
+FLAGS="--full --no-cpu-baseline --no-cbs --no-somatic --no-h2d --no-packed --no-executables --no-gc-only --no-pedigree --steps 1 --warmup 0"
 env "$@" CANVAS_WV_TIMING=1 python $R/bench.py $FLAGS > /tmp/wv0.log 2>&1; echo "plain rc $?"
 grep "canvas_wavelets" /tmp/wv0.log | tail -6 > $O/wavelets_phases.txt; cat $O/wavelets_phases.txt
 rm -rf /tmp/prof3; env "$@" timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof3 -o wv -- python $R/bench.py $FLAGS > /tmp/wv.log 2>&1; echo "profile rc $?"
