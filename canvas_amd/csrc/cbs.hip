@@ -2191,12 +2191,13 @@ struct MtStreamCache {
         if (it != streams.end()) return it->second.get();
         std::unique_ptr<MtStream> S(new MtStream()); S->seed = seed;
         if (hipSetDevice(ctx->device) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        if (useVmm) {
+        bool vmm = useVmm;
+        if (vmm) {      // (a failed reservation — address space runs out with thousands of streams — gives THIS stream a fixed allotment; later ones try again)
             void* base = nullptr;
-            if (hipMemAddressReserve(&base, MTS_VA_BYTES, 0, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); useVmm = false; }
+            if (hipMemAddressReserve(&base, MTS_VA_BYTES, 0, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); vmm = false; }
             else S->va = (char*)base;
         }
-        if (!useVmm) {          // no virtual memory management: one fixed allotment per stream (1 / 32 of the bound), served until it is full
+        if (!vmm) {          // no virtual memory management: one fixed allotment per stream (1 / 32 of the bound), served until it is full
             S->plain = true; S->plainBytes = std::max<size_t>(MTS_GRANULE, std::min<size_t>(size_t(512) << 20, capBytes / 32) & ~(MTS_GRANULE - 1));      // (at most 512 MB each: allocating 25 x 2.9 GB took 2 s)
             if (usedBytes + S->plainBytes > capBytes || hipMalloc((void**)&S->va, S->plainBytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
             S->mappedBytes = S->plainBytes; usedBytes += S->plainBytes;
@@ -2355,6 +2356,12 @@ struct MtStreamCache {
 
 // ---- device permutation engine, one instance per chromosome thread (own stream and buffers)
 #define PERM_GPU_MIN_N 201           // every hybrid segment (> 200 bins) takes the device engine (round 2 kept those below 1024 bins on the host: 12 % slower on the device then; with this round's kernels 0.19 vs 0.23 s on the 4.7 M-bin probe); CANVAS_CBS_PERM_GPU_MIN_N overrides
+static int perm_gpu_min_n() { static const int v = cvx_hook("CANVAS_CBS_PERM_GPU_MIN_N") ? atoi(cvx_hook("CANVAS_CBS_PERM_GPU_MIN_N")) : PERM_GPU_MIN_N; return v; }
+// Which chromosomes get a draw stream in the cache: those long enough for the device engine's permutation loops (perm_loop_gpu), which read tens of millions of draws.
+// A shorter chromosome reads at most a few million (nPerm x n per loop, n <= 200) that its loops draw on the host as before the cache existed (perm_loop_small_gpu's
+// pinned batches), instead of holding a 64 MB piece of the bound each: with a reference's thousands of small contigs those pieces filled the bound in seed order and
+// left the long chromosomes' loops to generate their own draws in the middle of a call.
+static bool wants_stream(long long n) { return n >= perm_gpu_min_n(); }
 #define PERM_TARGET_ELEMS (64 << 20) // permuted elements per batch (44 B of workspace each)
 #define PERM_FY_MIN_N 16384          // segments from this length on take k_perm_fy (block-wise simulation of the swaps); shorter ones k_perm_stat (CANVAS_CBS_FY_MIN_N overrides: test hook)
 // (batches of up to 2048 permutations for loops that run long were tried: k_perm_stat then takes 26 ms instead of 3.5 ms for 256 — the same rate per permutation — so
@@ -3052,7 +3059,7 @@ static int32_t phase2_run(PermGpu& PG, Phase1& P, uint32_t nPerm, double cutoff,
         int k = nrejc * (nrejc + 1) / 2 + 1;
         auto t0 = std::chrono::steady_clock::now();
         struct Acc { std::atomic<long long>& a; std::chrono::steady_clock::time_point t; ~Acc() { a += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t).count(); } };
-        static const int permGpuMinN = cvx_hook("CANVAS_CBS_PERM_GPU_MIN_N") ? atoi(cvx_hook("CANVAS_CBS_PERM_GPU_MIN_N")) : PERM_GPU_MIN_N;
+        const int permGpuMinN = perm_gpu_min_n();
         if (hybrid && n >= permGpuMinN && hk <= PG_MAXK && cvx_hook("CANVAS_CBS_HOST_PERMUTATIONS") == nullptr) {
             Acc acc{st.ns_dev, t0};
             struct L { std::chrono::steady_clock::time_point t; ~L() { tlClock.dev += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); tlClock.devLoops++; } } lc{t0};
@@ -3625,7 +3632,7 @@ int32_t cvx_cbs_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const
     long long mtsBefore[4] = {0, 0, 0, 0};
     if (mts) {
         mtsBefore[0] = mts->servedWords; mtsBefore[1] = mts->fallbackWords; mtsBefore[2] = mts->generatedWords; mtsBefore[3] = mts->fetches;
-        for (int c = 0; c < nchr; c++) { const long long n = h_chr_offset[c + 1] - h_chr_offset[c]; if (n >= 4 && (!h_mask || h_mask[c])) mts->prefetch(mts->get((uint32_t)seeds[c]), std::max<long long>(MTS_FIRST_WORDS, 32 * n)); }
+        for (int c = 0; c < nchr; c++) { const long long n = h_chr_offset[c + 1] - h_chr_offset[c]; if (cbs::wants_stream(n) && (!h_mask || h_mask[c])) mts->prefetch(mts->get((uint32_t)seeds[c]), std::max<long long>(MTS_FIRST_WORDS, 32 * n)); }
     }
     auto work = [&]() {
         cbs::EngineCache& cache = cbs::EngineCache::of(ctx);                             // per thread: own buffers, borrowed from the context's cache (created on first use)
@@ -3642,7 +3649,7 @@ int32_t cvx_cbs_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const
             int c = next++; if (c >= nchr) break;
             int n = (int)(h_chr_offset[c + 1] - h_chr_offset[c]);
             if (n <= 0 || (h_mask && !h_mask[c])) continue;
-            cbs::Rng rnd; rnd.init((uint32_t)seeds[c], mts);
+            cbs::Rng rnd; rnd.init((uint32_t)seeds[c], cbs::wants_stream(n) ? mts : nullptr);
             auto tC = std::chrono::steady_clock::now();
             struct CAcc { std::mutex& m; double& mx; double& sm; std::chrono::steady_clock::time_point t; ~CAcc() { double d = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); std::lock_guard<std::mutex> lk(m); mx = std::max(mx, d); sm += d; } } cAcc{chromMu, maxChromSec, sumChromSec, tC};
             cbs::tlClock = cbs::ChromClock();

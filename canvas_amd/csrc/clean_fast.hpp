@@ -1670,7 +1670,7 @@ static int32_t clean_batch_finish(canvas_ctx* ctx, double* h_local_sd_out, int64
         if (h_local_sd_out) h_local_sd_out[s] = H.haveLocalSd ? H.localSd : -1.0;
         if (h_info) {
             int32_t info[8] = {0};
-            info[0] = (int32_t)H.nA; info[1] = (int32_t)H.nAB; info[2] = (int32_t)(H.gcActive ? H.kept : (long long)H.nAB); info[3] = (int32_t)H.nFinal; info[4] = H.changed; info[5] = q.useCq ? 1 : 0;
+            info[0] = (int32_t)H.nA; info[1] = (int32_t)H.nAB; info[2] = (int32_t)(H.gcActive ? H.kept : (long long)H.nAB); info[3] = (int32_t)H.nFinal; info[4] = H.changed; info[5] = q.useCq ? 1 : 0; info[7] = 1;
             memcpy(h_info + 8 * s, info, sizeof info);
         }
     }

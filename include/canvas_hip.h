@@ -185,7 +185,8 @@ int32_t canvas_bin_predefined_gcweighted(canvas_ctx* ctx, int32_t nchr, const ui
  * [0] after size filter, [1] after outlier filter, [2] after GC strip, [3] after local-SD filter, [4] variance-normalised,
  * [5] 1 = the medians / quartiles were read off exact per-value counters (counts that are two-decimal values, as the F2 text
  * of a .binned file always is), 0 = radix selects (any other input; same results), [6] 1 = flags were -g alone (CANVAS_CLEAN_GCNORM) on whole-number counts and
- * the stage ran as RemoveBinsWithExtremeGC + NormalizeByGC (CanvasClean.cs:163-237,497-505) in three launches, in place (same results as the general chain). */
+ * the stage ran as RemoveBinsWithExtremeGC + NormalizeByGC (CanvasClean.cs:163-237,497-505) in three launches, in place (same results as the general chain), [7] with [6] = 1: chunks
+ * k_cg_fixup moved; with [6] = 0: 1 = the device-driven chain (clean_fast.hpp) produced the result, 0 = the host-driven path did (LOESS, -w < 100, more than 1024 chromosome runs). */
 int32_t canvas_clean(canvas_ctx* ctx, int64_t n, int32_t* d_chr, int32_t* d_start, int32_t* d_stop, float* d_count,
                      int32_t* d_gc, int32_t nchr, const uint8_t* h_chr_is_autosome, uint32_t flags, int32_t min_bins_per_gc,
                      double* h_local_sd_out, int64_t* h_n_out, int32_t* h_info);
@@ -305,7 +306,7 @@ int64_t canvas_cbs_boundary(uint32_t nperm, double alpha, uint32_t* h_out, int64
  * library keeps them per context in device memory (generated once, extended on demand, bounded by CANVAS_CBS_CACHE_GB — default 30 % of the device's memory, 0 = off) and
  * canvas_cbs reads its permutations' draws out of them.  canvas_cbs_prefetch starts the generator for the first `words_per_chromosome` draws of the first nchr streams on a
  * thread and stream of its own — and creates, on another, the streams and request tables of canvas_cbs's launchers (a stream costs ~5 ms on this runtime: 60 ms of a first
- * call) — and returns at once: a host calls it while it is still reading its input (CanvasPartition does).  Optional — canvas_cbs asks for what it needs itself.  canvas_cbs_cache_stats: h_out6 = {draws the last canvas_cbs call read out of the cache, draws it generated inside its batches (cache off / bound reached),
+ * call) — and returns at once: a host calls it while it is still reading its input (CanvasPartition does).  Optional — canvas_cbs asks for what it needs itself.  canvas_cbs_cache_stats: h_out6 = {draws the last canvas_cbs call read out of the cache, draws it generated inside its batches (cache off / bound reached; chromosomes shorter than the device engine's 201 bins have no stream and draw on the host, uncounted),
  * draws the cache's generator produced during the call, generator states fetched for host code, bytes of device memory the cache holds, draws it holds}. */
 int32_t canvas_cbs_prefetch(canvas_ctx* ctx, int32_t nchr, int64_t words_per_chromosome);
 /* Diagnostic / test entry: nwords tempered outputs of the chromosome-th generator (0-based, file order) from output number `position` on, read out of the context's cache

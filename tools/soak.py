@@ -15,10 +15,12 @@ budget = float(sys.argv[1]) * 60 if len(sys.argv) > 1 else 120
 t0 = time.time(); it = 0; fallbacks = 0; retries = 0; fb = {}; nbatch = 0; ncount = 0; ngconly = 0; by_noise = {}; by_disp = {}
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 while time.time() - t0 < budget:
-    seed = int(rng.randint(1, 2**31 - 1)); n = int(rng.choice([3_000, 30_000, 120_000, 600_000])); nchr = int(rng.choice([1, 3, 24]))
+    seed = int(rng.randint(1, 2**31 - 1)); n = int(rng.choice([3_000, 30_000, 120_000, 600_000])); nchr = int(rng.choice([1, 3, 24, 65, 257, 1025]))
     if os.environ.get("SOAK_N"): n = int(rng.choice([int(v) for v in os.environ["SOAK_N"].split(",")]))          # (hooks for hunting a rare case: fixed sizes / noise level)
     if os.environ.get("SOAK_NCHR"): nchr = int(os.environ["SOAK_NCHR"])
-    bins = synth.generate_bins(seed, n, nchr=nchr)
+    # past 24: GRCh38's chromosomes followed by contigs (tables uploaded past 64, autosome flags past index 255 read from memory, > 1 024 runs handed back to the host)
+    lens = None if nchr <= 24 else synth.GRCH38 + [int(v) for v in rng.randint(20_000, 2_000_000, nchr - 24)]
+    bins = synth.generate_bins(seed, n, nchr=nchr, lengths=lens)
     noise = rng.choice([0.0, 10.0, 40.0])
     if os.environ.get("SOAK_NOISE"): noise = float(os.environ["SOAK_NOISE"])
     if noise: bins["count"] = (bins["count"] + rng.normal(0, noise, len(bins["count"]))).clip(0).astype(np.float32)
@@ -31,14 +33,14 @@ while time.time() - t0 < budget:
         scale = 1.0 if shape == "f2" else float(rng.choice([0.05, 0.4, 1.7, 4.0]))
         bins["count"] = (np.round(bins["count"].astype(np.float64) * scale * 100.0) / 100.0).astype(np.float32)
     flags = int(rng.choice([CLEAN_GCNORM | CLEAN_FILTSIZE | CLEAN_OUTLIERS | CLEAN_LOCALSD, CLEAN_GCNORM, CLEAN_FILTSIZE | CLEAN_OUTLIERS, CLEAN_GCNORM | CLEAN_LOCALSD | CLEAN_FILTSIZE]))
-    is_auto = synth.IS_AUTOSOME[:nchr]; is_y = np.zeros(nchr, np.uint8)
+    is_auto = synth.IS_AUTOSOME[:nchr] if nchr <= 24 else np.concatenate([synth.IS_AUTOSOME, rng.rand(nchr - 24) < 0.6]).astype(np.uint8); is_y = np.zeros(nchr, np.uint8)
     ex = O.clean(bins["chr"], bins["start"], bins["stop"], bins["count"], bins["gc"], is_auto, is_y, flags)
     dev = {k: torch.from_numpy(np.ascontiguousarray(v)).to(cv.device) for k, v in bins.items()}
     if rng.rand() < 0.3:
         # the sample as one of a cohort of 2-4 different samples through canvas_clean_batch (one launch chain for all of them); the others are checked too
         others = []
         for _ in range(int(rng.randint(1, 4))):
-            b2 = synth.generate_bins(int(rng.randint(1, 2**31 - 1)), int(rng.choice([3_000, 30_000, 120_000, 600_000])), nchr=nchr)
+            b2 = synth.generate_bins(int(rng.randint(1, 2**31 - 1)), int(rng.choice([3_000, 30_000, 120_000, 600_000])), nchr=nchr, lengths=lens)
             others.append((b2, O.clean(b2["chr"], b2["start"], b2["stop"], b2["count"], b2["gc"], is_auto, is_y, flags)))
         devs = [dev] + [{k: torch.from_numpy(np.ascontiguousarray(v)).to(cv.device) for k, v in b2.items()} for b2, _ in others]
         pos = int(rng.randint(0, len(devs))); devs[0], devs[pos] = devs[pos], devs[0]

@@ -18,6 +18,10 @@ t0 = time.time(); it = 0; npath = {}
 while time.time() - t0 < budget:
     nchr = int(rng.choice([1, 2, 5]))
     lengths = [int(rng.choice([4096, 4097, 65_537, 300_000, 1_000_003, 2_500_000])) + int(rng.randint(0, 5000)) for _ in range(nchr)]
+    if rng.rand() < 0.3:                  # dozens of tiny contigs behind the chromosomes (a reference with its unplaced / alt contigs): chains of one- and few-tile chromosomes
+        tiny = int(rng.randint(20, 80))
+        lengths += [int(rng.choice([1, 63, 64, 65, 4095, 4096, 4097])) if rng.rand() < 0.3 else int(rng.randint(2_000, 50_000)) for _ in range(tiny)]
+        nchr += tiny
     rate = float(rng.choice([0.02, 0.105, 0.21, 0.9]))
     seed = int(rng.randint(1, 2**31 - 1))
     thr = synth.poisson_thresholds(rate)
