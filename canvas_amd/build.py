@@ -203,13 +203,14 @@ def _tool_hash(srcs):
 
 
 def build_tools(force=False, verbose=False):
-    """drop-in tool drivers (plain C++ over the C ABI + zlib): canvas_amd/bin/CanvasBin, CanvasClean, CanvasPartition"""
+    """drop-in tool drivers (plain C++ over the C ABI + zlib): canvas_amd/bin/CanvasBin, CanvasClean, CanvasPartition, CanvasNormalize"""
     tdir = os.path.join(HERE, "tools")
     bdir = os.path.join(HERE, "bin")
     os.makedirs(bdir, exist_ok=True)
     tl = _torch_lib_dir()
     outs = []
-    for name, src in (("CanvasBin", "canvas_bin_main.cpp"), ("CanvasClean", "canvas_clean_main.cpp"), ("CanvasPartition", "canvas_partition_main.cpp")):
+    for name, src in (("CanvasBin", "canvas_bin_main.cpp"), ("CanvasClean", "canvas_clean_main.cpp"), ("CanvasPartition", "canvas_partition_main.cpp"),
+                      ("CanvasNormalize", "canvas_normalize_main.cpp")):
         out = os.path.join(bdir, name)
         srcs = [os.path.join(tdir, src), os.path.join(tdir, "tool_common.hpp"), os.path.join(tdir, "protobuf_dat.hpp"), os.path.join(tdir, "fast_io.hpp")]
         th = _tool_hash(srcs)

@@ -19,7 +19,7 @@ ABI_SYMBOLS = [
     "canvas_packed_plane_bytes", "canvas_pack_reference_host", "canvas_pack_hits_host", "canvas_pack_genome_device", "canvas_upload_packed_begin", "canvas_bin_sample_packed", "canvas_sample_pipeline_packed", "canvas_pack_hits2_host", "canvas_upload_packed2_begin",
     "canvas_mask_from_fasta", "canvas_mask_exclude_intervals", "canvas_screen_hits",
     "canvas_bin_rates", "canvas_bin_size_from_rates", "canvas_bin_count_upper_bound", "canvas_bin_genome", "canvas_bin_sample", "canvas_bin_sample_gcweighted", "canvas_bin_predefined", "canvas_bin_predefined_gcweighted",
-    "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_sample_pipeline",
+    "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_normalize_best_normal", "canvas_normalize_pca_reference", "canvas_sample_pipeline",
     "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads",
 ]
 
@@ -709,6 +709,33 @@ class Canvas:
                                                     C.c_void_p(keep.data_ptr()), C.c_void_p(ratio.data_ptr()), C.c_void_p(count.data_ptr()), C.byref(n_out), C.byref(lsf)))
         k = n_out.value
         return keep[:k], ratio[:k], count[:k], lsf.value
+
+    def normalize_best_normal(self, tumor, normals, on_target_idx=None):
+        """BestLR2ReferenceGenerator.Run for more than one normal (f64 tensors): (index of the chosen normal, mean squared log ratio per normal,
+        ignored bins per normal, how many normals were replayed exactly on the host)"""
+        n = int(tumor.numel())
+        ptrs = (C.c_void_p * len(normals))(*[C.c_void_p(c.data_ptr()) for c in normals])
+        best = C.c_int32(-1); replayed = C.c_int32(0)
+        msl = np.zeros(len(normals), np.float64); ign = np.zeros(len(normals), np.int64)
+        self._check(self.lib.canvas_normalize_best_normal(self.ctx, C.c_void_p(tumor.data_ptr()), len(normals), ptrs, C.c_int64(n),
+                                                          C.c_void_p(on_target_idx.data_ptr()) if on_target_idx is not None else None,
+                                                          C.c_int64(int(on_target_idx.numel()) if on_target_idx is not None else 0),
+                                                          C.byref(best), _np_ptr(msl), _np_ptr(ign), C.byref(replayed)))
+        return best.value, msl, ign, replayed.value
+
+    def normalize_pca_reference(self, sample, mu, axes, min_ref=1.0, max_ref=float("inf")):
+        """PCAReferenceGenerator.Run: sample / mu f32 tensors of the model's length, axes = list of f64 tensors (raw, not normalised).
+        Returns (reference counts f32 tensor, median ratio, projection sizes) or None when the axes are not orthogonal (the reference throws)."""
+        torch = self.torch
+        n = int(mu.numel())
+        ptrs = (C.c_void_p * len(axes))(*[C.c_void_p(a.data_ptr()) for a in axes])
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        med = C.c_double(0); sizes = np.zeros(len(axes), np.float64); orth = C.c_int32(0)
+        self._check(self.lib.canvas_normalize_pca_reference(self.ctx, C.c_int64(n), C.c_void_p(sample.data_ptr()), C.c_void_p(mu.data_ptr()), len(axes), ptrs,
+                                                            C.c_double(min_ref), C.c_double(max_ref), C.c_void_p(out.data_ptr()), C.byref(med), _np_ptr(sizes), C.byref(orth)))
+        if not orth.value:
+            return None
+        return out, med.value, sizes
 
     def wavelets_decisions(self):
         """[long nodes decided from the closed form, undecided -> exact chain, chained for their coefficient, closed form in use] of the last wavelets() call"""

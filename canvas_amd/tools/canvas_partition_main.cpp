@@ -34,38 +34,6 @@ struct BinFilter {
     }
 };
 
-// PloidyInterval (PloidyInfo.cs:182-198): one-based Start = POS, End = INFO/END, Ploidy = the sample's CN field ("." = 2)
-struct PloidyIv { int start, end, ploidy; };
-// the single-sample ploidy VCF as Isas' VcfReader exposes it to PloidyInfo.LoadPloidyFromVcfFile (PloidyInfo.cs:112-165); plain or gzip text
-static bool load_ploidy_vcf(const std::string& path, std::map<std::string, std::vector<PloidyIv>>& out, std::string& err) {
-    GzReader rd(path); if (!rd.ok()) { err = "cannot open ploidy VCF '" + path + "'"; return false; }
-    std::string row; int samples = -1;
-    while (rd.line(row)) {
-        if (row.empty()) continue;
-        if (row[0] == '#') { if (row.rfind("#CHROM", 0) == 0) { auto h = split_tab(row); samples = (int)h.size() > 9 ? (int)h.size() - 9 : 0; } continue; }
-        if (samples < 0) { err = "File '" + path + "' has no #CHROM header line"; return false; }
-        if (samples == 0) { err = "File '" + path + "' does not contain any genotype column"; return false; }
-        if (samples > 1) { err = "File '" + path + "' cannot have more than one genotype columns when no sample ID provided"; return false; }
-        auto f = split_tab(row);
-        if (f.size() < 10) { err = "malformed ploidy VCF record: " + row; return false; }
-        PloidyIv iv; iv.start = atoi(f[1].c_str()); iv.end = -1; iv.ploidy = 2;
-        bool haveEnd = false;
-        for (size_t a0 = 0; a0 <= f[7].size();) { size_t b = f[7].find(';', a0); std::string kv = f[7].substr(a0, b == std::string::npos ? b : b - a0);
-            if (kv.rfind("END=", 0) == 0) { iv.end = atoi(kv.c_str() + 4); haveEnd = true; } if (b == std::string::npos) break; a0 = b + 1; }
-        if (!haveEnd) { err = "ploidy VCF record without INFO/END: " + row; return false; }            // InfoFields["END"] throws KeyNotFoundException
-        std::vector<std::string> keys, vals;
-        for (int which = 0; which < 2; which++) { const std::string& src = f[which == 0 ? 8 : 9]; auto& dst = which == 0 ? keys : vals;
-            for (size_t a0 = 0;;) { size_t b = src.find(':', a0); dst.push_back(src.substr(a0, b == std::string::npos ? b : b - a0)); if (b == std::string::npos) break; a0 = b + 1; } }
-        bool haveCn = false;
-        for (size_t k = 0; k < keys.size() && k < vals.size(); k++) if (keys[k] == "CN") { haveCn = true; iv.ploidy = vals[k] == "." ? 2 : atoi(vals[k].c_str()); }
-        if (!haveCn) { err = "File '" + path + "' must contain one genotype CN column!"; return false; }
-        out[f[0]].push_back(iv);
-    }
-    if (samples < 0) { err = "File '" + path + "' has no #CHROM header line"; return false; }
-    if (samples == 0) { err = "File '" + path + "' does not contain any genotype column"; return false; }
-    if (samples > 1) { err = "File '" + path + "' cannot have more than one genotype columns when no sample ID provided"; return false; }
-    return true;
-}
 // PloidyInfo.IsUniformReferencePloidy over the one-based interval [qs, qe] (PloidyInfo.cs:78-110); -1: a ploidy outside 0..4 indexes past baseCounts (the reference throws)
 static int is_uniform_reference_ploidy(const std::vector<PloidyIv>& ivs, int qs, int qe) {
     int baseCounts[5] = {0, 0, qe - qs + 1, 0, 0};

@@ -1,4 +1,4 @@
-// Shared host code of the drop-in tool drivers (CanvasClean / CanvasPartition): option parsing in the reference's NDesk OptionSet
+// Shared host code of the drop-in tool drivers (CanvasClean / CanvasPartition / CanvasNormalize): option parsing in the reference's NDesk OptionSet
 // style, gzip text I/O of the intermediate files (CanvasCommon/IO.cs), .NET Core 2.x number formatting, and the
 // IsAutosome assumption (Isas.SequencingFiles is not in /root/reference: "optional chr prefix + integer").
 // The drivers use ONLY the C ABI of include/canvas_hip.h (what the C# hosts would P/Invoke).
@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <atomic>
@@ -150,6 +151,58 @@ static bool load_bed(const std::string& path, std::map<std::string, std::vector<
     char buf[1 << 14];
     while (fgets(buf, sizeof buf, f)) { std::string s(buf); while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back(); auto t = split_tab(s); if (t.size() < 3) continue; out[t[0]].push_back({atoi(t[1].c_str()), atoi(t[2].c_str())}); }
     fclose(f); return true;
+}
+
+// PloidyInterval (PloidyInfo.cs:182-198): one-based Start = POS, End = INFO/END, Ploidy = the sample's CN field ("." = 2)
+struct PloidyIv { int start, end, ploidy; };
+// the single-sample ploidy VCF as Isas' VcfReader exposes it to PloidyInfo.LoadPloidyFromVcfFileNoSampleId (PloidyInfo.cs:112-165; no genotype column or more
+// than one is refused); plain or gzip text.  CanvasPartition -p and CanvasNormalize -p
+static bool load_ploidy_vcf(const std::string& path, std::map<std::string, std::vector<PloidyIv>>& out, std::string& err) {
+    GzReader rd(path); if (!rd.ok()) { err = "cannot open ploidy VCF '" + path + "'"; return false; }
+    std::string row; int samples = -1;
+    while (rd.line(row)) {
+        if (row.empty()) continue;
+        if (row[0] == '#') { if (row.rfind("#CHROM", 0) == 0) { auto h = split_tab(row); samples = (int)h.size() > 9 ? (int)h.size() - 9 : 0; } continue; }
+        if (samples < 0) { err = "File '" + path + "' has no #CHROM header line"; return false; }
+        if (samples == 0) { err = "File '" + path + "' does not contain any genotype column"; return false; }
+        if (samples > 1) { err = "File '" + path + "' cannot have more than one genotype columns when no sample ID provided"; return false; }
+        auto f = split_tab(row);
+        if (f.size() < 10) { err = "malformed ploidy VCF record: " + row; return false; }
+        PloidyIv iv; iv.start = atoi(f[1].c_str()); iv.end = -1; iv.ploidy = 2;
+        bool haveEnd = false;
+        for (size_t a0 = 0; a0 <= f[7].size();) { size_t b = f[7].find(';', a0); std::string kv = f[7].substr(a0, b == std::string::npos ? b : b - a0);
+            if (kv.rfind("END=", 0) == 0) { iv.end = atoi(kv.c_str() + 4); haveEnd = true; } if (b == std::string::npos) break; a0 = b + 1; }
+        if (!haveEnd) { err = "ploidy VCF record without INFO/END: " + row; return false; }            // InfoFields["END"] throws KeyNotFoundException
+        std::vector<std::string> keys, vals;
+        for (int which = 0; which < 2; which++) { const std::string& src = f[which == 0 ? 8 : 9]; auto& dst = which == 0 ? keys : vals;
+            for (size_t a0 = 0;;) { size_t b = src.find(':', a0); dst.push_back(src.substr(a0, b == std::string::npos ? b : b - a0)); if (b == std::string::npos) break; a0 = b + 1; } }
+        bool haveCn = false;
+        for (size_t k = 0; k < keys.size() && k < vals.size(); k++) if (keys[k] == "CN") { haveCn = true; iv.ploidy = vals[k] == "." ? 2 : atoi(vals[k].c_str()); }
+        if (!haveCn) { err = "File '" + path + "' must contain one genotype CN column!"; return false; }
+        out[f[0]].push_back(iv);
+    }
+    if (samples < 0) { err = "File '" + path + "' has no #CHROM header line"; return false; }
+    if (samples == 0) { err = "File '" + path + "' does not contain any genotype column"; return false; }
+    if (samples > 1) { err = "File '" + path + "' cannot have more than one genotype columns when no sample ID provided"; return false; }
+    return true;
+}
+// PloidyInfo.GetReferenceCopyNumber of the bin [start, stop) (PloidyInfo.cs:56-75, through CanvasNormalizeUtilities.GetPloidy, :13-20): the copy number that
+// covers most bases, 2 on a chromosome the VCF does not list; -1: a ploidy outside 0..4 indexes past baseCounts (the reference throws)
+static int reference_copy_number(const std::vector<PloidyIv>* ivs, int start, int stop) {
+    if (!ivs) return 2;
+    int baseCounts[5] = {0, 0, stop - start, 0, 0};
+    for (auto& iv : *ivs) {
+        if (iv.ploidy == 2) continue;
+        const int overlapStart = std::max(start, iv.start - 1);
+        if (overlapStart > iv.end) continue;
+        const int overlapBases = std::min(stop, iv.end) - overlapStart;
+        if (overlapBases <= 0) continue;
+        if (iv.ploidy < 0 || iv.ploidy > 4) return -1;
+        baseCounts[2] -= overlapBases; baseCounts[iv.ploidy] += overlapBases;
+    }
+    int best = 0, cn = 2;
+    for (int c = 0; c < 5; c++) if (baseCounts[c] > best) { best = baseCounts[c]; cn = c; }
+    return cn;
 }
 
 struct Dev {      // tiny RAII around the ABI's device memory

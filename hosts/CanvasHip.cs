@@ -113,6 +113,15 @@ namespace CanvasHipInterop
         [DllImport(Lib)] public static extern int canvas_allgather_host(IntPtr ctx, double[] send, long bytesPerRank, double[] recv);
         [DllImport(Lib)] public static extern int canvas_merge_cleaned_sharded(IntPtr ctx, long nMine, IntPtr dChr, IntPtr dStart, IntPtr dStop, IntPtr dCount,
             IntPtr dOutChr, IntPtr dOutStart, IntPtr dOutStop, IntPtr dOutCount, long cap, out long nOut);
+        // CanvasNormalize: the three reference generators (WeightedAverage, BestLR2, PCA) and the LSNorm (mode 0) / Raw (mode 1) ratio + RatiosToCounts
+        [DllImport(Lib)] public static extern int canvas_normalize_reference(IntPtr ctx, int nsamples, IntPtr[] dCountsPerSample, long n, IntPtr dOnTargetIdx, long nOnTarget,
+            IntPtr dWeighted, double[] weights);
+        [DllImport(Lib)] public static extern int canvas_normalize_best_normal(IntPtr ctx, IntPtr dTumor, int nnormals, IntPtr[] dNormals, long n, IntPtr dOnTargetIdx, long nOnTarget,
+            out int best, double[] meanSquaredLogRatios, long[] ignoredBins, out int replayed);
+        [DllImport(Lib)] public static extern int canvas_normalize_pca_reference(IntPtr ctx, long n, IntPtr dSample, IntPtr dMu, int naxes, IntPtr[] dAxes, double minRef, double maxRef,
+            IntPtr dReference, out double medianRatio, double[] sizes, out int orthogonal);
+        [DllImport(Lib)] public static extern int canvas_normalize_ratio(IntPtr ctx, long n, IntPtr dSample, IntPtr dReference, IntPtr dOnTargetIdx, long nOnTarget, int mode,
+            double minRef, double maxRef, IntPtr dPloidy, IntPtr dKeepIdx, IntPtr dRatio, IntPtr dCount, out long nOut, out double librarySizeFactor);
 
         /// <summary>Turns a non-zero status into the module's own failure convention (message on stderr, exit code 1).</summary>
         public static void Check(IntPtr ctx, int status, string what)

@@ -372,6 +372,26 @@ int32_t canvas_normalize_reference(canvas_ctx* ctx, int32_t nsamples, const doub
 int32_t canvas_normalize_ratio(canvas_ctx* ctx, int64_t n, const float* d_sample, const float* d_reference, const int32_t* d_on_target_idx, int64_t n_on_target,
                                int32_t mode, double min_ref, double max_ref, const int32_t* d_ploidy, int32_t* d_keep_idx, float* d_ratio, float* d_count,
                                int64_t* h_n_out, double* h_library_size_factor);
+/* BestLR2ReferenceGenerator.Run for more than one control sample (BestLR2ReferenceGenerator.cs:31-80): weight = 1 / OnTargetMedianBinCount (0 if the
+ * median is not positive) for the tumour and every normal, over the bins of d_on_target_idx (NULL: all bins); per normal the mean of
+ * log(t*wt / (n*wn))^2 over the bins where n*wn > 0 and the term is finite (GetMeanSquaredLogRatios, :83-124; nBins > 0 ? sum / nBins : sum); the
+ * smallest mean wins, the first normal a tie.  d_tumor / h_d_normals: device doubles (double.Parse of the 4th column, BinCounts.cs:51-52).  The sums
+ * are taken in parallel with an error bound that covers the summation order and the device's log; the normals the bounds cannot separate from the
+ * best one are replayed on the host in the reference's order with libm log, so *h_best is the reference's choice.  Outputs: *h_best, per normal
+ * the mean (exact for the replayed ones) and the ignored-bin count (both optional), *h_replayed = how many normals were replayed (optional).
+ * With one control sample the reference copies the file and never gets here. */
+int32_t canvas_normalize_best_normal(canvas_ctx* ctx, const double* d_tumor, int32_t nnormals, const double* const* h_d_normals, int64_t n, const int32_t* d_on_target_idx,
+                                     int64_t n_on_target, int32_t* h_best, double* h_mean_sq_log_ratio, int64_t* h_ignored, int32_t* h_replayed);
+/* PCAReferenceGenerator.Run (PCAReferenceGenerator.cs:32-69) with the model of PCAModel.LoadModel (:92-127): d_sample = the sample's float counts
+ * (float.Parse), d_mu = the model's float means, h_d_axes = naxes (1..64) device pointers to the raw axes (double.Parse), n = bins of the model.
+ * The axes are normalised by their 2-norm (Utilities.NormalizeBy2Norm, an all-zero axis stays as it is); *h_orthogonal = 0 when a pair's
+ * |DotProduct| exceeds 1e-4 (AreOrthogonal, :129-140: the reference throws) and nothing else is computed.  Otherwise: centred sample
+ * max(1f, count) - mu, projection sizes DotProduct(x, unit axis) (h_sizes, optional), ref = max(1, mu + sum_k size_k * unit_k), its
+ * "{F2}" text read back, RawRatioCalculator of the UNCLAMPED sample against it over [min_ref, max_ref] (RawRatioCalculator.cs:21-46),
+ * *h_median_ratio = median of those ratios, d_reference[i] = (float)(ref[i] * medianRatio).  The 2-norms and the projection sizes are
+ * sequential FP64 sums in the reference's order; the result is bit-identical to the reference's. */
+int32_t canvas_normalize_pca_reference(canvas_ctx* ctx, int64_t n, const float* d_sample, const float* d_mu, int32_t naxes, const double* const* h_d_axes,
+                                       double min_ref, double max_ref, float* d_reference, double* h_median_ratio, double* h_sizes, int32_t* h_orthogonal);
 
 /* ---- multi-GPU (one process per GPU; chromosomes sharded across ranks) ------------------------------------------ */
 int32_t canvas_comm_unique_id(void* h_id128);  /* ncclGetUniqueId, 128 bytes, rank 0 */
