@@ -281,15 +281,20 @@ void orc_xperm(const double* x, double* px, int n, uint32_t seed, int skip_perms
     }
 }
 // ChangePoints for one chromosome. stats: 7 int64 (CbsStats). Returns number of segments.
-int orc_cbs_chromosome(const double* x, int n, int32_t seed, const uint32_t* sbdry, int nsbdry, double alpha, uint32_t nPerm, int undo,
-                       double trimmedSD, int32_t* lengthSeg, int cap, int64_t* stats) {
+// undoSD: the reference fixes it at 3 (CBSRunner.cs); the product's C ABI takes it, so the checker does too.
+int orc_cbs_chromosome_sd(const double* x, int n, int32_t seed, const uint32_t* sbdry, int nsbdry, double alpha, uint32_t nPerm, int undo,
+                          double trimmedSD, double undoSD, int32_t* lengthSeg, int cap, int64_t* stats) {
     std::vector<uint32_t> sb(sbdry, sbdry + nsbdry);
     MT19937 rnd((uint32_t)seed);
     CbsStats st;
-    auto ls = ChangePoints(x, n, sb, rnd, alpha, nPerm, 2, 25, 200, undo, trimmedSD, 0.05, 3, &st);
+    auto ls = ChangePoints(x, n, sb, rnd, alpha, nPerm, 2, 25, 200, undo, trimmedSD, 0.05, undoSD, &st);
     for (size_t i = 0; i < ls.size() && (int)i < cap; i++) lengthSeg[i] = ls[i];
     if (stats) { stats[0] = st.tmaxo_calls; stats[1] = st.tmaxo_elems; stats[2] = st.perms; stats[3] = st.perm_elems; stats[4] = st.tpermp_draws; stats[5] = st.tailp_exits; stats[6] = st.big_t_splits; }
     return (int)ls.size();
+}
+int orc_cbs_chromosome(const double* x, int n, int32_t seed, const uint32_t* sbdry, int nsbdry, double alpha, uint32_t nPerm, int undo,
+                       double trimmedSD, int32_t* lengthSeg, int cap, int64_t* stats) {
+    return orc_cbs_chromosome_sd(x, n, seed, sbdry, nsbdry, alpha, nPerm, undo, trimmedSD, 3.0, lengthSeg, cap, stats);
 }
 // whole genome CBS (finite data assumed), one std::thread per chromosome (CBSRunner.cs:115-147)
 void orc_cbs_genome_undo(int nchr, const double* const* x, const int64_t* n, const uint32_t* sbdry, int nsbdry, double alpha, uint32_t nPerm,
@@ -298,8 +303,14 @@ void orc_cbs_genome(int nchr, const double* const* x, const int64_t* n, const ui
                     int32_t* const* lengthSeg, const int* cap, int32_t* nseg, int64_t* stats7, int threads) {
     orc_cbs_genome_undo(nchr, x, n, sbdry, nsbdry, alpha, nPerm, 0, lengthSeg, cap, nseg, stats7, threads);
 }
+void orc_cbs_genome_undo_sd(int nchr, const double* const* x, const int64_t* n, const uint32_t* sbdry, int nsbdry, double alpha, uint32_t nPerm,
+                            int undo, double undoSD, int32_t* const* lengthSeg, const int* cap, int32_t* nseg, int64_t* stats7, int threads);
 void orc_cbs_genome_undo(int nchr, const double* const* x, const int64_t* n, const uint32_t* sbdry, int nsbdry, double alpha, uint32_t nPerm,
                          int undo, int32_t* const* lengthSeg, const int* cap, int32_t* nseg, int64_t* stats7, int threads) {
+    orc_cbs_genome_undo_sd(nchr, x, n, sbdry, nsbdry, alpha, nPerm, undo, 3.0, lengthSeg, cap, nseg, stats7, threads);
+}
+void orc_cbs_genome_undo_sd(int nchr, const double* const* x, const int64_t* n, const uint32_t* sbdry, int nsbdry, double alpha, uint32_t nPerm,
+                            int undo, double undoSD, int32_t* const* lengthSeg, const int* cap, int32_t* nseg, int64_t* stats7, int threads) {
     double trimmedSD = 1.0;
     if (undo == 2) {   // CBSRunner.cs:102
         std::vector<const double*> sc(x, x + nchr); std::vector<int> ln(nchr); for (int c = 0; c < nchr; c++) ln[c] = (int)n[c];
@@ -311,7 +322,7 @@ void orc_cbs_genome_undo(int nchr, const double* const* x, const int64_t* n, con
     std::vector<std::thread> th;
     std::atomic_int next{0};
     auto work = [&]() { for (;;) { int c = next++; if (c >= nchr) break;
-        nseg[c] = n[c] > 0 ? orc_cbs_chromosome(x[c], (int)n[c], seeds[c], sbdry, nsbdry, alpha, nPerm, undo, trimmedSD, lengthSeg[c], cap[c], &st[(size_t)c * 7]) : 0; } };
+        nseg[c] = n[c] > 0 ? orc_cbs_chromosome_sd(x[c], (int)n[c], seeds[c], sbdry, nsbdry, alpha, nPerm, undo, trimmedSD, undoSD, lengthSeg[c], cap[c], &st[(size_t)c * 7]) : 0; } };
     for (int t = 0; t < std::max(1, threads); t++) th.emplace_back(work);
     for (auto& t : th) t.join();
     if (stats7) { for (int k = 0; k < 7; k++) { stats7[k] = 0; for (int c = 0; c < nchr; c++) stats7[k] += st[(size_t)c * 7 + k]; } }

@@ -318,9 +318,11 @@ _SBDRY = {}
 def cbs_boundary(n_perm=10000, alpha=0.01, eta=0.05):
     key = (n_perm, alpha, eta)
     if key not in _SBDRY:
-        cap = 8192 * 8
+        k = int(n_perm * alpha) + 2                       # (k + 1)(k + 2) / 2 entries for k = floor(nperm alpha); two spare rows
+        cap = max(8192 * 8, (k + 1) * (k + 2) // 2)
         out = np.zeros(cap, np.uint32)
         n = lib.orc_cbs_boundary(C.c_uint32(n_perm), C.c_double(alpha), C.c_double(eta), _p(out), cap)
+        assert n <= cap, (n_perm, alpha, n, cap)
         _SBDRY[key] = out[:n].copy()
     return _SBDRY[key]
 
@@ -379,13 +381,14 @@ def changepoints_prune(x, length_seg, cutoff=0.05):
     return out[:k].copy()
 
 
-def cbs_genome(xs, alpha=0.01, n_perm=10000, threads=1, undo=0):
+def cbs_genome(xs, alpha=0.01, n_perm=10000, threads=1, undo=0, undo_sd=3.0):
+    """undo_sd: the reference fixes it at 3 (CBSRunner.cs); the product's C ABI takes it, so the checker does too"""
     sb = cbs_boundary(n_perm, alpha)
     n = np.array([len(x) for x in xs], np.int64)
     caps = np.array([len(x) + 1 for x in xs], np.int32)
     ls = [np.zeros(int(c), np.int32) for c in caps]
     nseg = np.zeros(len(xs), np.int32); stats = np.zeros(7, np.int64)
-    lib.orc_cbs_genome_undo(len(xs), _pp(xs), _p(n), _p(sb), len(sb), C.c_double(alpha), C.c_uint32(n_perm), undo, _pp(ls), _p(caps), _p(nseg), _p(stats), threads)
+    lib.orc_cbs_genome_undo_sd(len(xs), _pp(xs), _p(n), _p(sb), len(sb), C.c_double(alpha), C.c_uint32(n_perm), undo, C.c_double(undo_sd), _pp(ls), _p(caps), _p(nseg), _p(stats), threads)
     return [l[:k].copy() for l, k in zip(ls, nseg)], stats
 
 

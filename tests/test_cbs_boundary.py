@@ -9,12 +9,14 @@ import oracle_lib as O
 from canvas_amd.lib import load_library
 
 
-# (the oracle wrapper holds 65 536 entries: floor(nperm alpha) <= 360)
-@pytest.mark.parametrize("nperm,alpha", [(10000, 0.01), (10000, 0.02), (5000, 0.01), (2500, 0.02), (1000, 0.01), (500, 0.05), (200, 0.01)])
+# (the oracle wrapper sizes its buffer from floor(nperm alpha); the last six pairs are those of tests/parameter_cases.py: 125 751 and 2 003 001 entries, and tables of 66, 3 and 1)
+@pytest.mark.parametrize("nperm,alpha", [(10000, 0.01), (10000, 0.02), (5000, 0.01), (2500, 0.02), (1000, 0.01), (500, 0.05), (200, 0.01),
+                                         (10000, 0.05), (10000, 0.2), (2000, 0.1), (10000, 0.001), (500, 0.002), (1000, 0.0005)])
 def test_boundary_table_equals_the_oracles(nperm, alpha):
     lib = load_library()
     lib.canvas_cbs_boundary.restype = C.c_int64
-    out = np.zeros(1 << 17, np.uint32)
+    k = int(np.floor(nperm * alpha))
+    out = np.zeros(max(1 << 17, (k + 3) * (k + 4) // 2), np.uint32)
     n = lib.canvas_cbs_boundary(C.c_uint32(nperm), C.c_double(alpha), out.ctypes.data_as(C.c_void_p), C.c_int64(len(out)))
     exp = O.cbs_boundary(nperm, alpha)
     assert n == len(exp) and n == (int(np.floor(nperm * alpha)) + 1) * (int(np.floor(nperm * alpha)) + 2) // 2

@@ -32,8 +32,9 @@ while time.time() - t0 < budget:
     off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
     nperm = int(rng.choice([500, 2000, 10000]))
     undo = int(rng.choice([0, 0, 1, 2]))
-    exp, est = O.cbs_genome(parts, 0.01, nperm, threads=8, undo=undo)
-    seg_len, nseg, stats = cv.cbs(torch.from_numpy(cov).to(cv.device), off, 0.01, nperm, undo=undo)
+    alpha = float(rng.choice([0.001, 0.01, 0.05]))        # CBSalpha of CanvasPartitionParameters.json: the boundary table, the TailP cutoff and the first batch's size follow it
+    exp, est = O.cbs_genome(parts, alpha, nperm, threads=8, undo=undo)
+    seg_len, nseg, stats = cv.cbs(torch.from_numpy(cov).to(cv.device), off, alpha, nperm, undo=undo)
     got = seg_len.cpu().numpy()
     for c in range(nchr):
         g = got[off[c]:off[c] + nseg[c]]

@@ -29,7 +29,7 @@ while time.time() - t0 < budget:
         per.append(np.round(x * 100) / 100)
     germ = bool(rng.rand() < 0.5)
     window = int(rng.choice([11, 100, 1000, 20000, 100000]))
-    kw = dict(is_germline=germ, window=window, mad_factor=float(rng.choice([2.0, 5.0])), thr_lower=float(rng.choice([0.05, 5.0])), min_size=int(rng.choice([10, 10, 4])))
+    kw = dict(is_germline=germ, window=window, mad_factor=float(rng.choice([0.5, 2.0, 5.0])), thr_lower=float(rng.choice([0.05, 5.0])), min_size=int(rng.choice([10, 10, 4])))
     exp = O.wavelets_genome(per, **kw)
     cov = np.ascontiguousarray(np.concatenate(per)); off = np.concatenate([[0], np.cumsum([len(a) for a in per])]).astype(np.int64)
     kg = dict(kw); kg['threshold_lower'] = kg.pop('thr_lower')
