@@ -116,6 +116,12 @@ int32_t canvas_memcpy_h2d(canvas_ctx* ctx, void* d_dst, const void* h_src, int64
     CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CANVAS_OK;
 }
+// queued on the context's stream and not waited for: h_src must stay untouched until the stream has been synchronised (asynchronous only from pinned / registered memory)
+int32_t canvas_memcpy_h2d_async(canvas_ctx* ctx, void* d_dst, const void* h_src, int64_t bytes) {
+    if (!ctx || bytes < 0) return CANVAS_ERR_INVALID;
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(d_dst, h_src, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
+    return CANVAS_OK;
+}
 int32_t canvas_memcpy_d2h(canvas_ctx* ctx, void* h_dst, const void* d_src, int64_t bytes) {
     if (!ctx || bytes < 0) return CANVAS_ERR_INVALID;
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(h_dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "canvas_bin_rates", "canvas_bin_size_from_rates", "canvas_bin_count_upper_bound", "canvas_bin_genome", "canvas_bin_sample", "canvas_bin_sample_gcweighted", "canvas_bin_predefined", "canvas_bin_predefined_gcweighted",
     "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_normalize_best_normal", "canvas_normalize_pca_reference", "canvas_sample_pipeline",
     "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads",
+    "canvas_memcpy_h2d_async", "canvas_snv_count",
 ]
 
 
@@ -127,6 +128,11 @@ def pack_hits2_host(hits, length, lo=None, hdr=None, extras=None, threads=0):
         if rc:
             raise CanvasError(f"canvas_pack_hits2_host: error {rc} (extras needed: {nx.value})")
         return lo, hdr, extras, nx.value, sat.value
+
+
+def snv_allele_codes(alleles):
+    """the site codes canvas_snv_count compares a read's 4-bit base code with: index of the allele's character in "=ACMGRSVTWYHKDBN", 255 for anything else"""
+    return np.array([("=ACMGRSVTWYHKDBN".find(a) if len(a) == 1 else -1) & 0xFF for a in alleles], np.uint8)
 
 
 class Canvas:
@@ -479,6 +485,30 @@ class Canvas:
         score = C.c_double(0); valid = C.c_int32(0)
         self._check(self.lib.canvas_evenness_score(self.ctx, len(off) - 1, C.c_void_p(cov.data_ptr()), _np_ptr(off), int(window), C.byref(score), C.byref(valid)))
         return score.value if valid.value else None
+
+    def snv_count(self, records, offsets, ref_id, site_pos, site_ref, site_alt, ref_counts=None, alt_counts=None, min_mapq=0, min_base_q=20, nbytes=None, want_info=True):
+        """SNVReviewer.ProcessBamFile + ProcessReadBases (SNVReviewer.cs:172-271) over one chunk of raw BAM records.  records: uint8 tensor (record bytes, each with
+        its block_size word), offsets: int64 tensor (byte offset of every record); site_pos int32 (one-based, sorted), site_ref / site_alt uint8 codes (snv_allele_codes);
+        ref_counts / alt_counts int32 are added to (created as zeros when None).  Returns (ref_counts, alt_counts, info[5] or None: seen, passed, walked, stopped at an
+        unsupported CIGAR operation, malformed).  want_info=False only queues the work."""
+        torch = self.torch
+        ns = int(site_pos.numel())
+        if ref_counts is None:
+            ref_counts = torch.zeros(max(ns, 1), dtype=torch.int32, device=self.device)
+        if alt_counts is None:
+            alt_counts = torch.zeros(max(ns, 1), dtype=torch.int32, device=self.device)
+        assert records.dtype == torch.uint8 and offsets.dtype == torch.int64 and site_pos.dtype == torch.int32 and site_ref.dtype == torch.uint8 and site_alt.dtype == torch.uint8
+        assert ref_counts.dtype == torch.int32 and alt_counts.dtype == torch.int32 and ref_counts.numel() >= ns and alt_counts.numel() >= ns
+        for t in (records, offsets, site_pos, site_ref, site_alt, ref_counts, alt_counts):      # the kernel reads dense arrays on this context's device
+            assert t.is_contiguous() and t.dim() == 1 and (t.numel() == 0 or t.device == self.device), "snv_count: tensors must be dense, one-dimensional and on the context's device"
+        nb = int(records.numel()) if nbytes is None else int(nbytes)
+        assert 0 <= nb <= records.numel()
+        info = np.zeros(5, np.int64) if want_info else None
+        self._check(self.lib.canvas_snv_count(self.ctx, C.c_void_p(records.data_ptr()), C.c_uint64(nb), C.c_void_p(offsets.data_ptr()), C.c_int64(int(offsets.numel())),
+                                              int(ref_id), int(min_mapq), int(min_base_q), C.c_void_p(site_pos.data_ptr()), C.c_void_p(site_ref.data_ptr()),
+                                              C.c_void_p(site_alt.data_ptr()), ns, C.c_void_p(ref_counts.data_ptr()), C.c_void_p(alt_counts.data_ptr()),
+                                              _np_ptr(info) if want_info else None))
+        return ref_counts, alt_counts, info
 
     def segment_ids(self, chr_offset, state, start, stop, max_inter_bin_dist=1000000, excluded=None, out=None, ploidy=None):
         """DeriveSegments + PostProcessSegments; excluded = per-chromosome list of (starts, stops) of the -b BED file; ploidy = per-chromosome list

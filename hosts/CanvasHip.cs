@@ -24,6 +24,7 @@ namespace CanvasHipInterop
         [DllImport(Lib)] public static extern int canvas_device_free(IntPtr ctx, IntPtr dptr);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d(IntPtr ctx, IntPtr dDst, byte[] hSrc, long bytes);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d(IntPtr ctx, IntPtr dDst, short[] hSrc, long bytes);
+        [DllImport(Lib)] public static extern int canvas_memcpy_h2d(IntPtr ctx, IntPtr dDst, ulong[] hSrc, long bytes);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d(IntPtr ctx, IntPtr dDst, int[] hSrc, long bytes);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d(IntPtr ctx, IntPtr dDst, float[] hSrc, long bytes);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d(IntPtr ctx, IntPtr dDst, double[] hSrc, long bytes);
@@ -122,6 +123,10 @@ namespace CanvasHipInterop
             IntPtr dReference, out double medianRatio, double[] sizes, out int orthogonal);
         [DllImport(Lib)] public static extern int canvas_normalize_ratio(IntPtr ctx, long n, IntPtr dSample, IntPtr dReference, IntPtr dOnTargetIdx, long nOnTarget, int mode,
             double minRef, double maxRef, IntPtr dPloidy, IntPtr dKeepIdx, IntPtr dRatio, IntPtr dCount, out long nOut, out double librarySizeFactor);
+        // CanvasSNV: allele counts at the variant sites from chunks of raw BAM record bytes (SNVReviewer.ProcessBamFile + ProcessReadBases); info = long[5] or null (queue only)
+        [DllImport(Lib)] public static extern int canvas_snv_count(IntPtr ctx, IntPtr dRecords, ulong nbytes, IntPtr dRecordOffsets, long nrecords, int refId, int minMapQ, int minBaseQ,
+            IntPtr dSitePos, IntPtr dSiteRef, IntPtr dSiteAlt, int nsites, IntPtr dRefCounts, IntPtr dAltCounts, long[] info);
+        [DllImport(Lib)] public static extern int canvas_memcpy_h2d_async(IntPtr ctx, IntPtr dDst, IntPtr hSrc, long bytes);
 
         /// <summary>Turns a non-zero status into the module's own failure convention (message on stderr, exit code 1).</summary>
         public static void Check(IntPtr ctx, int status, string what)

@@ -59,6 +59,9 @@ void* canvas_device_malloc(canvas_ctx* ctx, int64_t bytes);
 int32_t canvas_device_free(canvas_ctx* ctx, void* d_ptr);
 int32_t canvas_memcpy_h2d(canvas_ctx* ctx, void* d_dst, const void* h_src, int64_t bytes);
 int32_t canvas_memcpy_d2h(canvas_ctx* ctx, void* h_dst, const void* d_src, int64_t bytes);
+/* canvas_memcpy_h2d without the wait: queued on the context's stream; h_src (pinned or registered with canvas_host_register) must not change before the next
+ * canvas_synchronize.  What CanvasSNV's chunk loop uses to upload chunk k while it inflates chunk k + 1. */
+int32_t canvas_memcpy_h2d_async(canvas_ctx* ctx, void* d_dst, const void* h_src, int64_t bytes);
 
 /* Pins a host array (hipHostRegister) so that uploads from it run at the full PCIe rate and asynchronously: what a C# host does once with the arrays
  * LoadIntermediateData left in memory (GCHandle.Alloc(..., Pinned) + this call). */
@@ -474,6 +477,24 @@ int32_t canvas_wavelets_sharded(canvas_ctx* ctx, int32_t nchr, const int32_t* h_
 int32_t canvas_allgather_host(canvas_ctx* ctx, const void* h_send, int64_t bytes_per_rank, void* h_recv);
 int32_t canvas_merge_cleaned_sharded(canvas_ctx* ctx, int64_t n_mine, const int32_t* d_chr, const int32_t* d_start, const int32_t* d_stop, const float* d_count,
                                      int32_t* d_out_chr, int32_t* d_out_start, int32_t* d_out_stop, float* d_out_count, int64_t cap, int64_t* h_n_out);
+
+/* ---- CanvasSNV: allele counts at the sites of a VCF (SNVReviewer.ProcessBamFile + ProcessReadBases, CanvasSNV/SNVReviewer.cs:172-271) ---------------- */
+/* One chunk of one chromosome's alignments as RAW BAM record bytes (SAM specification 4.2, each record with its block_size word, exactly as BGZF inflation
+ * leaves them) plus the byte offset of every record in the chunk; no field is decoded on the host.  Records and sites must be sorted by position (the
+ * caller's to check: any indexed BAM and sorted VCF are); then the result equals the reference's sequential scan.
+ *   sites       d_site_pos: one-based positions, non-decreasing, duplicates allowed (each is a site of its own); d_site_ref / d_site_alt: the BAM 4-bit code of
+ *               the allele's character ("=ACMGRSVTWYHKDBN" -> 0..15), 0xFF for any other character (lower case included: the reference compares chars)
+ *   filters     flag & 0x100 / 0x4 / 0x400 and mapq <= min_mapq are skipped; records of another refID or without a position as well
+ *   counters    d_ref_counts / d_alt_counts (int32 per site) are ADDED to, never cleared: a chromosome is any number of chunks
+ *   h_info      NULL: the call only queues work on the context's stream (counters complete after canvas_synchronize).  Otherwise int64[5], valid on return
+ *               (the call waits): records seen, passed the filters, walked (a site within reach: SNVReviewer.cs:206-213), whose walk ended at a CIGAR operation
+ *               other than M/I/D/S (:266-268), rejected as malformed (an offset, block_size, name / CIGAR / sequence length that does not fit the record or the
+ *               chunk, or a CIGAR that consumes more bases than l_seq: such a record is skipped whole and never read past its bounds).  The CIGAR
+ *               is only read for records that are walked, so a record whose CIGAR outruns l_seq but has no site within reach counts as passed, not as malformed:
+ *               that one figure depends on the site list; the counters do not (such a record touches no site either way). */
+int32_t canvas_snv_count(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nbytes, const uint64_t* d_record_offsets, int64_t nrecords, int32_t ref_id,
+                         int32_t min_mapq, int32_t min_base_q, const int32_t* d_site_pos, const uint8_t* d_site_ref, const uint8_t* d_site_alt, int32_t nsites,
+                         int32_t* d_ref_counts, int32_t* d_alt_counts, int64_t* h_info);
 
 /* ---- profiling hooks (hipEvent pairs recorded on the context's stream around the named kernels) --------------------- */
 /* on: 0 off; 1 every named scope; 2 only the scopes around the dominant (HBM-bound) kernel of CanvasBin — "bin_summary", "bin_summary_packed", "bin_pass",
