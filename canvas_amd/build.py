@@ -10,7 +10,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-result"]
-PRODUCT_SRC = ["ctx.hip", "prep.hip", "bin.hip", "clean.hip", "hmm.hip", "cbs.hip", "wavelets.hip", "evenness.hip", "normalize.hip", "pipeline.hip", "sharded.hip", "comm.hip", "snv.hip"]
+PRODUCT_SRC = ["ctx.hip", "prep.hip", "bin.hip", "clean.hip", "hmm.hip", "cbs.hip", "wavelets.hip", "evenness.hip", "normalize.hip", "pipeline.hip", "sharded.hip", "comm.hip", "snv.hip", "kmer.hip"]
 
 
 def _hipcc():
@@ -203,14 +203,14 @@ def _tool_hash(srcs):
 
 
 def build_tools(force=False, verbose=False):
-    """drop-in tool drivers (plain C++ over the C ABI + zlib): canvas_amd/bin/CanvasBin, CanvasClean, CanvasPartition, CanvasNormalize, CanvasSNV"""
+    """drop-in tool drivers (plain C++ over the C ABI + zlib): canvas_amd/bin/CanvasBin, CanvasClean, CanvasPartition, CanvasNormalize, CanvasSNV, FlagUniqueKmers"""
     tdir = os.path.join(HERE, "tools")
     bdir = os.path.join(HERE, "bin")
     os.makedirs(bdir, exist_ok=True)
     tl = _torch_lib_dir()
     outs = []
     for name, src in (("CanvasBin", "canvas_bin_main.cpp"), ("CanvasClean", "canvas_clean_main.cpp"), ("CanvasPartition", "canvas_partition_main.cpp"),
-                      ("CanvasNormalize", "canvas_normalize_main.cpp"), ("CanvasSNV", "canvas_snv_main.cpp")):
+                      ("CanvasNormalize", "canvas_normalize_main.cpp"), ("CanvasSNV", "canvas_snv_main.cpp"), ("FlagUniqueKmers", "flag_unique_kmers_main.cpp")):
         out = os.path.join(bdir, name)
         srcs = [os.path.join(tdir, src), os.path.join(tdir, "tool_common.hpp"), os.path.join(tdir, "protobuf_dat.hpp"), os.path.join(tdir, "fast_io.hpp"), os.path.join(tdir, "bam_io.hpp")]
         th = _tool_hash(srcs)

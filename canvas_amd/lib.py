@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "canvas_bin_rates", "canvas_bin_size_from_rates", "canvas_bin_count_upper_bound", "canvas_bin_genome", "canvas_bin_sample", "canvas_bin_sample_gcweighted", "canvas_bin_predefined", "canvas_bin_predefined_gcweighted",
     "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_normalize_best_normal", "canvas_normalize_pca_reference", "canvas_sample_pipeline",
     "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads",
-    "canvas_memcpy_h2d_async", "canvas_snv_count",
+    "canvas_memcpy_h2d_async", "canvas_snv_count", "canvas_flag_unique_kmers", "canvas_fasta_case_from_mask",
 ]
 
 
@@ -509,6 +509,35 @@ class Canvas:
                                               C.c_void_p(site_alt.data_ptr()), ns, C.c_void_p(ref_counts.data_ptr()), C.c_void_p(alt_counts.data_ptr()),
                                               _np_ptr(info) if want_info else None))
         return ref_counts, alt_counts, info
+
+    # ---- reference preparation (Tools/FlagUniqueKmers)
+    def flag_unique_kmers(self, bases, lens, masks=None, max_table_bytes=0):
+        """KmerChecker (Tools/FlagUniqueKmers/KmerChecker.cs): bases = one uint8 device tensor per contig (ASCII, any case, not modified), lens = their lengths.
+        Returns (masks, stats): masks = one int64 tensor of ceil(len / 64) words per contig (BitArray layout; created unless given), bit p set iff position p starts a
+        35-mer that occurs once in the whole input, both strands counted; stats = dict(positions, keyed, unique, passes, table_slots, longest_probe, table_bytes).
+        max_table_bytes bounds the working table (0: chosen from free device memory); the masks do not depend on it."""
+        torch = self.torch
+        n = len(bases)
+        hl = np.ascontiguousarray(lens, np.int64)
+        assert len(hl) == n
+        if masks is None:
+            masks = [torch.empty((int(L) + 63) // 64, dtype=torch.int64, device=self.device) for L in hl]
+        for t, m, L in zip(bases, masks, hl):
+            assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() >= L and (L == 0 or t.device == self.device), "flag_unique_kmers: bases must be dense uint8 tensors on the context's device"
+            assert m.dtype == torch.int64 and m.is_contiguous() and m.numel() >= (int(L) + 63) // 64 and (L == 0 or m.device == self.device), "flag_unique_kmers: masks must be dense int64 tensors on the context's device"
+        st = np.zeros(8, np.int64)
+        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        self._check(self.lib.canvas_flag_unique_kmers(self.ctx, n, _ptr_table(bases), _np_ptr(hl), _ptr_table(masks), C.c_int64(int(max_table_bytes)), _np_ptr(st)))
+        return masks, dict(positions=int(st[0]), keyed=int(st[1]), unique=int(st[2]), passes=int(st[3]), table_slots=int(st[4]), longest_probe=int(st[5]), table_bytes=int(st[6]))
+
+    def fasta_case_from_mask(self, bases, length, mask):
+        """inverse of mask_from_fasta, in place: ASCII letters of bases[:length] become upper case where the mask bit is 1 and lower case where it is 0"""
+        torch = self.torch
+        assert bases.dtype == torch.uint8 and bases.is_contiguous() and bases.numel() >= length and mask.dtype == torch.int64 and mask.numel() >= (int(length) + 63) // 64
+        torch.cuda.synchronize(self.device)
+        self._check(self.lib.canvas_fasta_case_from_mask(self.ctx, C.c_void_p(bases.data_ptr()), C.c_int64(int(length)), C.c_void_p(mask.data_ptr())))
+        self.synchronize()
+        return bases
 
     def segment_ids(self, chr_offset, state, start, stop, max_inter_bin_dist=1000000, excluded=None, out=None, ploidy=None):
         """DeriveSegments + PostProcessSegments; excluded = per-chromosome list of (starts, stops) of the -b BED file; ploidy = per-chromosome list

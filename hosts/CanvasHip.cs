@@ -127,6 +127,9 @@ namespace CanvasHipInterop
         [DllImport(Lib)] public static extern int canvas_snv_count(IntPtr ctx, IntPtr dRecords, ulong nbytes, IntPtr dRecordOffsets, long nrecords, int refId, int minMapQ, int minBaseQ,
             IntPtr dSitePos, IntPtr dSiteRef, IntPtr dSiteAlt, int nsites, IntPtr dRefCounts, IntPtr dAltCounts, long[] info);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d_async(IntPtr ctx, IntPtr dDst, IntPtr hSrc, long bytes);
+        // Tools/FlagUniqueKmers (KmerChecker): unique-35-mer masks of all contigs at once (stats = long[8] or null), and the letter case of kmer.fa from a mask
+        [DllImport(Lib)] public static extern int canvas_flag_unique_kmers(IntPtr ctx, int nchr, IntPtr[] dBases, long[] len, IntPtr[] dMask, long maxTableBytes, long[] stats);
+        [DllImport(Lib)] public static extern int canvas_fasta_case_from_mask(IntPtr ctx, IntPtr dBases, long len, IntPtr dMask);
 
         /// <summary>Turns a non-zero status into the module's own failure convention (message on stderr, exit code 1).</summary>
         public static void Check(IntPtr ctx, int status, string what)

@@ -496,6 +496,20 @@ int32_t canvas_snv_count(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nby
                          int32_t min_mapq, int32_t min_base_q, const int32_t* d_site_pos, const uint8_t* d_site_ref, const uint8_t* d_site_alt, int32_t nsites,
                          int32_t* d_ref_counts, int32_t* d_alt_counts, int64_t* h_info);
 
+/* ---- reference preparation: Tools/FlagUniqueKmers ---------------------------------------------------------------------- */
+/* Tools/FlagUniqueKmers (KmerChecker.cs): d_mask[c] (ceil(len/64) words, BitArray layout, bits >= len written 0) gets bit p = 1 iff position p of
+ * chromosome c starts a 35-mer whose canonical key occurs once in the whole input.  d_bases: ASCII, any case, not modified.
+ * max_table_bytes: bound of the working table (0 = chosen from free device memory); any value that holds one key class must give the same mask.
+ * h_stats[8]: positions, keyed positions, unique positions, passes, table slots, longest probe, table bytes, reserved.
+ * Rules (KmerChecker.cs:124,136,147-154 and GetKeyForKmer, :30-105): bases are upper-cased first; position p of a contig of length L is keyed when p + 35 < L and
+ * its 35 bases are all of A C G T; a keyed position is flagged when no other keyed position of any contig carries the same 35-mer or its reverse complement.
+ * A contig of length 0 has no words (its pointers are not looked at); a single contig is shorter than 2^31.  A budget that does not hold the largest of the 1 024
+ * key classes returns CANVAS_ERR_CAPACITY (the message names the bytes needed) and writes no mask.  The call waits for its result. */
+int32_t canvas_flag_unique_kmers(canvas_ctx* ctx, int32_t nchr, const uint8_t* const* d_bases, const int64_t* h_len,
+                                 uint64_t* const* d_mask, int64_t max_table_bytes, int64_t* h_stats);
+/* inverse of canvas_mask_from_fasta: ASCII letters of d_bases become upper case where the mask bit is 1 and lower case where it is 0, in place */
+int32_t canvas_fasta_case_from_mask(canvas_ctx* ctx, uint8_t* d_bases, int64_t len, const uint64_t* d_mask);
+
 /* ---- profiling hooks (hipEvent pairs recorded on the context's stream around the named kernels) --------------------- */
 /* on: 0 off; 1 every named scope; 2 only the scopes around the dominant (HBM-bound) kernel of CanvasBin — "bin_summary", "bin_summary_packed", "bin_pass",
    "bin_tile_stats" — so that a timed pass carries two event records instead of a dozen (each scope costs two barrier packets on the stream) */
