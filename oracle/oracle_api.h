@@ -27,4 +27,5 @@ int64_t clean(int64_t n, int32_t* chr, int32_t* start, int32_t* stop, float* cou
 void Quartiles(const std::vector<float>& x, float& q1, float& q2, float& q3);
 void loess_fit(const double* x, const double* y, int n, double bandwidth, int robIters, double xStep, double* fittedOrig, double* predicted);
 double golden_section_square(double a, double b);
+int64_t last_loess_double(double* out, int64_t cap);   // Math.Exp(smoothed) of the last LOESS normalisation, before the cast to float
 }  // namespace oracle

@@ -703,6 +703,15 @@ static double loess_objective(double bandwidth, const std::vector<double>& gcs, 
     return StandardDeviationAll(fitted);
 }
 
+// the doubles that the last NormalizeByGC_Loess call rounded to float (Math.Exp(smoothed) before invCountTransformer's cast): read by the tests that bound the
+// oracle's own arithmetic error against an extended-precision restatement (tests/loess_ref.py)
+static std::vector<double> g_lastLoessDouble;
+int64_t last_loess_double(double* out, int64_t cap) {
+    int64_t n = (int64_t)g_lastLoessDouble.size();
+    if (out) std::copy(g_lastLoessDouble.begin(), g_lastLoessDouble.begin() + std::min(n, cap), out);
+    return n;
+}
+
 // LoessGCNormalizer.initialize/Normalize (LoessGCNormalizer.cs:36-90) with CanvasClean's log/exp transformers (CanvasClean.cs:147-151)
 static void NormalizeByGC_Loess(Bins& bins, const uint8_t* isChrY) {
     std::vector<double> gcs, counts;
@@ -726,10 +735,12 @@ static void NormalizeByGC_Loess(Bins& bins, const uint8_t* isChrY) {
     int maxGC = (int)*std::max_element(gcs.begin(), gcs.end());
     LoessModel model = LoessTrain(gcs, counts, best, 0, 1, false);
     auto fittedByGC = LoessPredictMany(model, gc_range(minGC, maxGC));
+    g_lastLoessDouble.assign(bins.size(), 0.0);
     for (size_t b = 0; b < bins.size(); b++) {
         int k = std::min((int)fittedByGC.size() - 1, std::max(0, bins.gc[b] - minGC));
         double smoothed = std::log((double)bins.count[b]) - fittedByGC[k] + medianY;
-        bins.count[b] = (float)std::exp(smoothed);
+        g_lastLoessDouble[b] = std::exp(smoothed);
+        bins.count[b] = (float)g_lastLoessDouble[b];
     }
 }
 

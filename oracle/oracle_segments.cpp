@@ -106,6 +106,7 @@ float orc_median_f32(const float* x, int n) { std::vector<float> v(x, x + n); re
 void orc_loess_fit(const double* x, const double* y, int n, double bw, int rob, double xStep, double* fitted, double* predicted) {
     loess_fit(x, y, n, bw, rob, xStep, fitted, predicted);
 }
+int64_t orc_last_loess_double(double* out, int64_t cap) { return last_loess_double(out, cap); }
 double orc_golden_section_square(double a, double b) { return golden_section_square(a, b); }
 
 void orc_negbin(double mean, double variance, int maxValue, double* out) {

@@ -152,6 +152,15 @@ def clean(chr_id, start, stop, count, gc, is_auto, is_y, flags, min_bins_weighte
     return dict(chr=chr_id[:n], start=start[:n], stop=stop[:n], count=count[:n], gc=gc[:n], local_sd=local_sd.value, stages=stages)
 
 
+def last_loess_double():
+    """Math.Exp(smoothed) of every bin in the last LOESS normalisation that clean() ran, before the cast to float (LoessGCNormalizer.cs:79-80)"""
+    lib.orc_last_loess_double.restype = C.c_int64
+    n = lib.orc_last_loess_double(None, C.c_int64(0))
+    out = np.zeros(n, np.float64)
+    lib.orc_last_loess_double(_p(out), C.c_int64(n))
+    return out
+
+
 def merge_cleaned(samples):
     """Utilities.MergeMultiSampleCleanedBedFile (Utilities.cs:834-920); samples = list of dicts with chr/start/stop/count arrays"""
     S = len(samples)
