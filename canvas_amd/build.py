@@ -212,7 +212,7 @@ def build_tools(force=False, verbose=False):
     for name, src in (("CanvasBin", "canvas_bin_main.cpp"), ("CanvasClean", "canvas_clean_main.cpp"), ("CanvasPartition", "canvas_partition_main.cpp"),
                       ("CanvasNormalize", "canvas_normalize_main.cpp"), ("CanvasSNV", "canvas_snv_main.cpp"), ("FlagUniqueKmers", "flag_unique_kmers_main.cpp")):
         out = os.path.join(bdir, name)
-        srcs = [os.path.join(tdir, src), os.path.join(tdir, "tool_common.hpp"), os.path.join(tdir, "protobuf_dat.hpp"), os.path.join(tdir, "fast_io.hpp"), os.path.join(tdir, "bam_io.hpp")]
+        srcs = [os.path.join(tdir, src)] + sorted(glob.glob(os.path.join(tdir, "*.hpp")))      # every header: a tool is stale when any of them changes
         th = _tool_hash(srcs)
         if force or embedded_hash(out) != th:
             tmp_out = "%s.%d.tmp" % (out, os.getpid())

@@ -16,7 +16,6 @@
 // reference: the json file must exist and is never read, nothing is binned or written (CanvasBin.cs:936-944), exit code 0; with -i it is the reference's ArgumentException.
 #include "tool_common.hpp"
 #include "protobuf_dat.hpp"
-#include "bam_io.hpp"
 #include <algorithm>
 #include <memory>
 #include <set>
@@ -25,96 +24,59 @@ using namespace tool;
 // ---------------------------------------------------------------- FASTA (kmer.fa: upper case = start of a unique k-mer)
 // An entry whose sequence is ONE line (FastaWriter-style kmer.fa files and the samples of bench.py) is a VIEW into the mapped file: nothing is copied and the process holds no
 // anonymous copy of the reference (3.1 GB of a human genome: 0.1 s to copy on the host threads and another 0.11 s for the kernel to take back when the process leaves).  An entry
-// folded into lines is copied with its line ends dropped, as before.
-struct FastaEntry {
+// folded into lines is copied with its line ends dropped.  (the scan itself: fast_io.hpp)
+struct FastaSeq {
     std::string name, owned; const char* view = nullptr; size_t viewLen = 0; std::shared_ptr<MappedFile> keep;
     const char* data() const { return view ? view : owned.data(); }
     size_t size() const { return view ? viewLen : owned.size(); }
 };
-// the file is mapped, the entry headers are located in one scan and the entries are copied (line ends dropped) on several threads
-static bool read_fasta(const std::string& path, const std::string* only, std::vector<FastaEntry>& out) {
-    std::shared_ptr<MappedFile> mfp = std::make_shared<MappedFile>(); MappedFile& mf = *mfp; if (!mf.open(path)) return false;
-    const char* p = mf.p; const size_t n = mf.n;
-    struct Ent { size_t hdr, seq, end; std::string name; };
-    std::vector<Ent> ents;
-    {   // '>' at the start of a line (scanned in slices on several threads, then put in order)
-        const int nt = io_threads();
-        std::vector<std::vector<size_t>> found((size_t)nt);
-        parallel_for(nt, [&](int64_t t) {
-            size_t a = n / (size_t)nt * (size_t)t, b = t == nt - 1 ? n : n / (size_t)nt * (size_t)(t + 1);
-            for (const char* q = p + a; q < p + b;) { q = (const char*)memchr(q, '>', (size_t)(p + b - q)); if (!q) break; if (q == p || q[-1] == '\n') found[(size_t)t].push_back((size_t)(q - p)); q++; }
-        });
-        for (auto& v : found) for (size_t h : v) { Ent e; e.hdr = h; e.seq = e.end = n; ents.push_back(e); }
-    }
-    for (size_t i = 0; i < ents.size(); i++) {
-        const char* le = (const char*)memchr(p + ents[i].hdr, '\n', n - ents[i].hdr);
-        const size_t lineEnd = le ? (size_t)(le - p) : n;
-        std::string name(p + ents[i].hdr + 1, lineEnd - ents[i].hdr - 1);
-        while (!name.empty() && (name.back() == '\r')) name.pop_back();
-        const size_t sp = name.find_first_of(" \t"); if (sp != std::string::npos) name = name.substr(0, sp);
-        ents[i].name = name; ents[i].seq = std::min(n, lineEnd + 1); ents[i].end = i + 1 < ents.size() ? ents[i + 1].hdr : n;
-    }
-    std::vector<size_t> keep;
-    for (size_t i = 0; i < ents.size(); i++) if (!only || ents[i].name == *only) keep.push_back(i);
-    const size_t base = out.size();
-    out.resize(base + keep.size());
-    parallel_for((int64_t)keep.size(), [&](int64_t k) {
-        const Ent& e = ents[keep[(size_t)k]]; FastaEntry& fe = out[base + (size_t)k];
-        fe.name = e.name; fe.owned.clear(); fe.view = nullptr; fe.viewLen = 0;
-        {   // one line?  (nothing but line ends behind the first line end)
-            const char* le = (const char*)memchr(p + e.seq, '\n', e.end - e.seq); const char* stop = le ? le : p + e.end;
-            bool single = true; for (const char* q = stop; q < p + e.end; q++) if (*q != '\n' && *q != '\r') { single = false; break; }
-            if (single && !getenv("CANVAS_TOOL_COPY_FASTA")) {
-                const char* te = stop; while (te > p + e.seq && te[-1] == '\r') te--;
-                fe.view = p + e.seq; fe.viewLen = (size_t)(te - (p + e.seq)); fe.keep = mfp;
-                return;
-            }
-        }
-        fe.owned.reserve(e.end - e.seq);
-        for (const char* q = p + e.seq; q < p + e.end;) {
-            const char* le = (const char*)memchr(q, '\n', (size_t)(p + e.end - q)); const char* stop = le ? le : p + e.end;
-            const char* te = stop; while (te > q && te[-1] == '\r') te--;
-            fe.owned.append(q, (size_t)(te - q));
-            q = le ? le + 1 : p + e.end;
-        }
+static bool read_fasta(const std::string& path, const std::string* only, std::vector<FastaSeq>& out) {
+    std::shared_ptr<MappedFile> mf = std::make_shared<MappedFile>(); if (!mf->open(path, true)) return false;
+    const std::vector<FastaEntry> ents = scan_fasta(*mf, only);
+    const bool copy = getenv("CANVAS_TOOL_COPY_FASTA") != nullptr;
+    out.assign(ents.size(), FastaSeq());
+    parallel_for((int64_t)ents.size(), [&](int64_t k) {
+        const FastaEntry& e = ents[(size_t)k]; FastaSeq& fe = out[(size_t)k];
+        fe.name = e.name;
+        if (e.single && !copy) { fe.view = mf->p + e.seq; fe.viewLen = (size_t)e.len; fe.keep = mf; return; }
+        fe.owned.resize((size_t)e.len); unfold(mf->p + e.seq, mf->p + e.end, &fe.owned[0]);
     });
     return true;
 }
 
-// ---------------------------------------------------------------- BGZF / BAM / BAI
-// (Bgzf, bai_first_offset, BamHeader / read_bam_header: bam_io.hpp, shared with CanvasSNV)
+// ---------------------------------------------------------------- BGZF / BAM / BAI: bam_io.hpp
+// the BAM opened at a chromosome, a failure in CanvasBin's words; 0 ok, otherwise the exit code
+static int open_bam_at(const std::string& bam, const std::string& chrom, BamAt& b) {
+    switch (bam_open_at(bam, chrom, b)) {
+        case BamOpen::Ok: return 0;
+        case BamOpen::NotBam: fprintf(stderr, "CanvasBin: %s is not a BAM file\n", bam.c_str()); break;
+        case BamOpen::NoSuchRef: fprintf(stderr, "Unable to retrieve the reference sequence index for %s in %s.\n", chrom.c_str(), bam.c_str()); break;
+        case BamOpen::NoIndex: fprintf(stderr, "Fatal error: Bam index not found at %s.bai\n", bam.c_str()); break;
+        case BamOpen::BadIndex: fprintf(stderr, "CanvasBin: cannot read %s.bai\n", bam.c_str()); break;
+    }
+    return 1;
+}
+// the read loop stopped at a BGZF block that does not parse or inflate, or at a record shorter than its fixed fields: nothing is written
+static int damaged_bam(const std::string& bam) { fprintf(stderr, "CanvasBin: %s is truncated or damaged: a BGZF block or an alignment record of it cannot be read\n", bam.c_str()); return 1; }
 
 // LoadObservedAlignmentsBAM (CanvasBin.cs:207-275)
 static int load_bam(const std::string& bam, bool pairedEnd, const std::string& chrom, int mode, std::vector<uint8_t>& hits, std::vector<int16_t>& frag) {
-    if (!file_exists(bam + ".bai")) { fprintf(stderr, "Fatal error: Bam index not found at %s.bai\n", bam.c_str()); return 1; }
-    Bgzf z; if (!z.open(bam)) return 1;
-    char magic[4]; int32_t ltext, nref;
-    if (!z.read(magic, 4) || memcmp(magic, "BAM\1", 4) != 0 || !z.read(&ltext, 4)) { fprintf(stderr, "CanvasBin: %s is not a BAM file\n", bam.c_str()); return 1; }
-    { std::vector<char> t(ltext); if (ltext && !z.read(t.data(), ltext)) return 1; }
-    if (!z.read(&nref, 4)) return 1;
-    int desired = -1;
-    for (int r = 0; r < nref; r++) { int32_t ln; if (!z.read(&ln, 4)) return 1; std::vector<char> nm(ln); int32_t lref; if (!z.read(nm.data(), ln) || !z.read(&lref, 4)) return 1; if (chrom == nm.data()) desired = r; }
-    if (desired < 0) { fprintf(stderr, "Unable to retrieve the reference sequence index for %s in %s.\n", chrom.c_str(), bam.c_str()); return 1; }
-    uint64_t voff; bool any;
-    if (!bai_first_offset(bam + ".bai", desired, voff, any)) { fprintf(stderr, "CanvasBin: cannot read %s.bai\n", bam.c_str()); return 1; }
-    if (!any) return 0;                                   // no reads for this chromosome: not an error (:231-235)
-    if (!z.seek_virtual(voff)) return 1;
+    BamAt b; if (int rc = open_bam_at(bam, chrom, b)) return rc;
+    if (!b.any) return 0;                                 // no reads for this chromosome: not an error (:231-235)
+    Bgzf& z = b.z; const int desired = b.ref;
+    if (!z.seek_virtual(b.voff)) return 1;
     long readCount = 0, kept = 0;
     std::vector<uint8_t> rec;
-    for (;;) {
-        int32_t bs; if (!z.read(&bs, 4)) break;
-        rec.resize(bs); if (!z.read(rec.data(), bs)) break;
+    for (BamFixed a; read_bam_record(z, rec, a);) {
         readCount++;
-        int32_t refID, pos, lseq, tlen; uint8_t lname; uint16_t ncig, flag;
-        memcpy(&refID, &rec[0], 4); memcpy(&pos, &rec[4], 4); lname = rec[8]; memcpy(&ncig, &rec[12], 2); memcpy(&flag, &rec[14], 2); memcpy(&lseq, &rec[16], 4); memcpy(&tlen, &rec[28], 4);
-        (void)lseq;
+        const int32_t refID = a.refID, pos = a.pos, tlen = a.tlen; const uint16_t flag = a.flag;
         if (flag & 0x4) continue;                          // !IsMapped
         if (flag & 0x200) continue;                        // IsFailedQC
         if (flag & 0x400) continue;                        // IsDuplicate
         if (flag & 0x10) continue;                         // IsReverseStrand
         if (flag & 0x900) continue;                        // !IsMainAlignment
-        if (ncig == 0) continue;
-        uint32_t c0; memcpy(&c0, &rec[32 + lname], 4);
+        if (a.n_cigar == 0) continue;
+        uint32_t c0; memcpy(&c0, &rec[32 + a.l_read_name], 4);
         if ((c0 & 0xF) != 0 || (c0 >> 4) < 35) continue;   // must start with 35 bases of 'M'
         if (pairedEnd && !(flag & 0x2)) continue;          // IsProperPair
         if (refID != desired) break;
@@ -124,6 +86,7 @@ static int load_bam(const std::string& bam, bool pairedEnd, const std::string& c
         if (mode == CANVAS_MODE_BINARY) hits[pos] = 1; else hits[pos] = hits[pos] == 255 ? 255 : (uint8_t)(hits[pos] + 1);
         if (mode == CANVAS_MODE_GC_CONTENT_WEIGHTED) frag[pos] = (int16_t)std::max(std::min(32767, tlen), 0);
     }
+    if (z.bad) return damaged_bam(bam);
     printf("Kept %ld of %ld total reads\n", kept, readCount);
     return 0;
 }
@@ -137,20 +100,19 @@ struct Inter { std::string name; int64_t len = 0; std::vector<uint64_t> maskWord
 // ---------------------------------------------------------------- predefined bins: Utilities.LoadBedFile(path, gcIndex: 3) (CanvasCommon/Utilities.cs:793-829)
 struct PreBin { int start, stop, gc; float count; };
 static bool load_predefined_bins(const std::string& path, std::map<std::string, std::vector<PreBin>>& out, std::vector<std::string>& chromOrder, std::string& err) {
-    FILE* f = fopen(path.c_str(), "rb"); if (!f) { err = "cannot open " + path; return false; }
-    char buf[1 << 14];
-    while (fgets(buf, sizeof buf, f)) {
-        std::string s(buf); while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back();
+    const bool opened = for_each_line(path, [&](const std::string& s) {
         auto t = split_tab(s);
-        if (t.size() < 3) { fclose(f); err = "malformed BED line: " + s; return false; }
+        if (t.size() < 3) { err = "malformed BED line: " + s; return false; }
         PreBin b{atoi(t[1].c_str()), atoi(t[2].c_str()), 0, 0.0f};
-        if (b.start < 0) { fclose(f); err = "Start must be non-negative in a BED file: " + s; return false; }
-        if (b.start >= b.stop) { fclose(f); err = "Start must be less than Stop in a BED file: " + s; return false; }
+        if (b.start < 0) { err = "Start must be non-negative in a BED file: " + s; return false; }
+        if (b.start >= b.stop) { err = "Start must be less than Stop in a BED file: " + s; return false; }
         if (t.size() > 3) b.gc = atoi(t[3].c_str());
         if (!out.count(t[0])) chromOrder.push_back(t[0]);
         out[t[0]].push_back(b);
-    }
-    fclose(f); return true;
+        return true;
+    });
+    if (!opened) err = "cannot open " + path;
+    return err.empty();
 }
 
 // ---------------------------------------------------------------- Fragment mode: FragmentBinner.BinTask (FragmentBinner.cs:98-371)
@@ -196,26 +158,16 @@ static void bin_one_alignment(const FragAln& a, unsigned qualityThreshold, std::
 }
 // binFragments (:186-244) for one chromosome; 0 ok, 1 error (message printed)
 static int bin_fragments(const std::string& bam, const std::string& chrom, std::vector<PreBin>& bins, long& usableFragmentCount) {
-    if (!file_exists(bam + ".bai")) { fprintf(stderr, "Fatal error: Bam index not found at %s.bai\n", bam.c_str()); return 1; }
-    Bgzf z; if (!z.open(bam)) return 1;
-    BamHeader h; if (!read_bam_header(z, h)) { fprintf(stderr, "CanvasBin: %s is not a BAM file\n", bam.c_str()); return 1; }
-    int desired = -1; for (size_t r = 0; r < h.refNames.size(); r++) if (h.refNames[r] == chrom) desired = (int)r;
-    if (desired < 0) { fprintf(stderr, "Unable to retrieve the reference sequence index for %s in %s.\n", chrom.c_str(), bam.c_str()); return 1; }
-    uint64_t voff; bool any;
-    if (!bai_first_offset(bam + ".bai", desired, voff, any)) { fprintf(stderr, "CanvasBin: cannot read %s.bai\n", bam.c_str()); return 1; }
+    BamAt b; if (int rc = open_bam_at(bam, chrom, b)) return rc;
     usableFragmentCount = 0;
-    if (!any) return 0;                                        // no reads for this chromosome: not an error (:205-210)
-    if (!z.seek_virtual(voff)) return 1;
+    if (!b.any) return 0;                                      // no reads for this chromosome: not an error (:205-210)
+    Bgzf& z = b.z; const int desired = b.ref;
+    if (!z.seek_virtual(b.voff)) return 1;
     std::map<std::string, int> readNameToBinIndex; std::set<std::string> samePositionReadNames;
     int binIndexStart = 0, prevPosition = -1; long pairedAlignmentCount = 0;
     std::vector<uint8_t> rec;
-    for (;;) {
-        int32_t bs; if (!z.read(&bs, 4)) break;
-        rec.resize(bs); if (!z.read(rec.data(), bs)) break;
-        FragAln a; uint8_t lname;
-        memcpy(&a.refID, &rec[0], 4); memcpy(&a.pos, &rec[4], 4); lname = rec[8]; a.mapq = rec[9]; memcpy(&a.flag, &rec[14], 2);
-        memcpy(&a.mateRefID, &rec[20], 4); memcpy(&a.matePos, &rec[24], 4); memcpy(&a.tlen, &rec[28], 4);
-        a.name.assign((const char*)&rec[32], lname > 0 ? lname - 1 : 0);
+    for (BamFixed x; read_bam_record(z, rec, x);) {
+        const FragAln a{std::string((const char*)&rec[32], x.l_read_name > 0 ? x.l_read_name - 1 : 0), x.refID, x.pos, x.next_refID, x.next_pos, x.tlen, x.flag, x.mapq};
         if (a.refID != desired) break;
         if (a.refID == -1) continue;
         if (a.pos < prevPosition) { fprintf(stderr, "The alignment on %s are not properly sorted in %s: %s\n", chrom.c_str(), bam.c_str(), a.name.c_str()); return 1; }
@@ -223,6 +175,7 @@ static int bin_fragments(const std::string& bam, const std::string& chrom, std::
         if (a.flag & 0x1) pairedAlignmentCount++;
         bin_one_alignment(a, 3, readNameToBinIndex, samePositionReadNames, usableFragmentCount, bins, binIndexStart);
     }
+    if (z.bad) return damaged_bam(bam);
     if (pairedAlignmentCount == 0) { fprintf(stderr, "No paired alignments found for %s in %s\n", chrom.c_str(), bam.c_str()); return 1; }
     return 0;
 }
@@ -285,7 +238,7 @@ int main(int argc, char** argv) {
             for (auto& b : it->second) b.count = 0;                                   // InitializeBins
             bool gcAvailable = true; for (auto& b : it->second) if (b.gc < 0) gcAvailable = false;
             if (!gcAvailable) {                                                       // PopulateBinGC (:163-181)
-                std::vector<FastaEntry> fa; if (!read_fasta(ref, &chromName, fa) || fa.empty()) { fprintf(stderr, "CanvasBin: chromosome %s not found in %s\n", chromName.c_str(), ref.c_str()); return 1; }
+                std::vector<FastaSeq> fa; if (!read_fasta(ref, &chromName, fa) || fa.empty()) { fprintf(stderr, "CanvasBin: chromosome %s not found in %s\n", chromName.c_str(), ref.c_str()); return 1; }
                 const char* bases = fa[0].data(); const size_t nbases = fa[0].size();
                 for (auto& b : it->second) { double nt = 0, gcn = 0; for (int p = b.start; p < b.stop && p < (int)nbases; p++) { if (bases[p] == 'n') continue; nt++; const char ch = bases[p]; if (ch == 'C' || ch == 'c' || ch == 'G' || ch == 'g') gcn++; }
                     b.gc = nt > 0 ? (int)(100 * gcn / nt) : 0; }
@@ -305,11 +258,11 @@ int main(int argc, char** argv) {
     AsyncCtx actx;                                              // the context comes up while the intermediates and the FASTA file are read
     struct CtxGuard { AsyncCtx& a; ~CtxGuard() { if (canvas_ctx* c = a.get()) canvas_destroy(c); } } guard{actx};
     canvas_ctx* ctx = nullptr;
-    auto need_ctx = [&]() -> bool { ctx = actx.get(); if (!ctx) fprintf(stderr, "CanvasBin (MI355X): no usable GPU (this build has no CPU fallback)\n"); return ctx != nullptr; };
+    auto need_ctx = [&]() -> bool { return (ctx = actx.require("CanvasBin")) != nullptr; };
 
     if (inters.empty()) {
         // ---- phase 1: CalculateSampleHits / BinOneGenomicInterval (CanvasBin.cs:765-792)
-        std::vector<FastaEntry> fa;
+        std::vector<FastaSeq> fa;
         if (!read_fasta(ref, &chrom, fa) || fa.empty()) { fprintf(stderr, "CanvasBin: chromosome %s not found in %s\n", chrom.c_str(), ref.c_str()); return 1; }
         Inter d; d.name = chrom; d.len = (int64_t)fa[0].size();
         const int64_t L = d.len, words = (L + 63) / 64;
@@ -374,12 +327,12 @@ int main(int argc, char** argv) {
         }
     }
     ExitStamp es2("FASTA entries freed");
-    std::vector<FastaEntry> fa;
+    std::vector<FastaSeq> fa;
     if (!read_fasta(ref, nullptr, fa)) return 1;
     if (!need_ctx()) return 1;
     ph.mark("read");
     // chromosomes in FASTA order that have an intermediate (CanvasBin.cs:506-540)
-    std::vector<const FastaEntry*> order; std::vector<Inter*> data;
+    std::vector<const FastaSeq*> order; std::vector<Inter*> data;
     for (auto& e : fa) { auto it = byChrom.find(e.name); if (it == byChrom.end()) continue; if ((int64_t)e.size() != it->second->len) { fprintf(stderr, "CanvasBin: length of %s differs between the reference and the intermediate file\n", e.name.c_str()); return 1; } order.push_back(&e); data.push_back(it->second.get()); }
     const int nchr = (int)order.size();
     if (nchr == 0) { fprintf(stderr, "CanvasBin: no chromosome to bin\n"); return 1; }

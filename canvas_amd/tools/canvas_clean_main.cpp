@@ -42,8 +42,7 @@ int main(int argc, char** argv) {
     ph.mark("read");
     int64_t nOut = n; double localSd = -1.0;
     if (n > 0) {
-        canvas_ctx* ctx = actx.get();
-        if (!ctx) { fprintf(stderr, "CanvasClean (MI355X): no usable GPU (this build has no CPU fallback)\n"); return 1; }
+        canvas_ctx* ctx = actx.require("CanvasClean"); if (!ctx) return 1;
         { Dev dChr(ctx, n * 4), dStart(ctx, n * 4), dStop(ctx, n * 4), dCount(ctx, n * 4), dGc(ctx, n * 4);
           TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dChr.p, chr.data(), n * 4)); TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dStart.p, start.data(), n * 4));
           TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dStop.p, stop.data(), n * 4)); TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dCount.p, count.data(), n * 4));

@@ -119,7 +119,7 @@ int main(int argc, char** argv) {
     // PloidyInfo.LoadPloidyFromVcfFileNoSampleId (CanvasNormalizeUtilities.cs:35-41)
     std::map<std::string, std::vector<PloidyIv>> ploidyByChrom; const bool havePloidy = a.has("ploidyVcfFile");
     if (havePloidy) { std::string err; if (!load_ploidy_vcf(ploidyVcf, ploidyByChrom, err)) { fprintf(stderr, "CanvasNormalize: %s\n", err.c_str()); return 1; } }
-    auto need_ctx = [&]() -> canvas_ctx* { canvas_ctx* c = actx.get(); if (!c) fprintf(stderr, "CanvasNormalize (MI355X): no usable GPU (this build has no CPU fallback)\n"); return c; };
+    auto need_ctx = [&]() -> canvas_ctx* { return actx.require("CanvasNormalize"); };
 
     // ---- 1. the reference file
     if (mode == 0 || mode == 1) {

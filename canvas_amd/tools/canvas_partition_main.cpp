@@ -127,8 +127,7 @@ int main(int argc, char** argv) {
         for (size_t c = 0; c < S.chromNames.size(); c++) { S.start.insert(S.start.end(), st[c].begin(), st[c].end()); S.end.insert(S.end.end(), en[c].begin(), en[c].end()); S.cov.insert(S.cov.end(), cv[c].begin(), cv[c].end()); S.off.push_back((int64_t)S.start.size()); }
     }
     ph.mark("read");
-    canvas_ctx* ctx = actx.get();
-    if (!ctx) { fprintf(stderr, "CanvasPartition (MI355X): no usable GPU (this build has no CPU fallback)\n"); return 1; }
+    canvas_ctx* ctx = actx.require("CanvasPartition"); if (!ctx) return 1;
     // per sample: segments per chromosome as (start, end) genomic pairs
     typedef std::vector<std::pair<uint32_t, uint32_t>> Segs;
     std::vector<std::map<std::string, Segs>> segBySample(samples.size());

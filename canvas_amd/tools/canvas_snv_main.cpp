@@ -8,13 +8,10 @@
 // chromosome, BAM records) is refused with exit code 1: the reference's answer for it depends on its scan pointer, and this library has no host pileup to reproduce it.
 // The reference's VcfReader (Isas.SequencingFiles) is not part of the reference tree: records are parsed by the VCF specification.
 #include "tool_common.hpp"
-#include "bam_io.hpp"
 #include <memory>
 using namespace tool;
 
 struct Site { int32_t pos; std::string ref, alt; };
-
-static std::vector<std::string> split_ch(const std::string& s, char sep) { std::vector<std::string> r; size_t a = 0; for (;;) { size_t b = s.find(sep, a); r.push_back(s.substr(a, b == std::string::npos ? b : b - a)); if (b == std::string::npos) break; a = b + 1; } return r; }
 
 // the sample columns of the #CHROM line; false: the file cannot be read
 static bool vcf_samples(const std::string& path, std::vector<std::string>& samples) {
@@ -47,14 +44,13 @@ static int load_variants(const std::string& path, const std::string& chrom, int 
         if (c[3].size() != 1 || c[4].size() != 1) continue;                    // single-allele SNVs only (a second ALT brings a comma: length > 1)
         if (c.size() > 9) {
             if ((size_t)(9 + sampleIndex) >= c.size()) { fprintf(stderr, "CanvasSNV: VCF record at %s:%s has no column for the sample\n", c[0].c_str(), c[1].c_str()); return 255; }
-            auto keys = split_ch(c[8], ':'), vals = split_ch(c[9 + sampleIndex], ':');
-            auto find = [&](const char* k) -> const std::string* { for (size_t i = 0; i < keys.size() && i < vals.size(); i++) if (keys[i] == k) return &vals[i]; return nullptr; };
-            const std::string* ft = find("FT");
+            const VcfFormat fmt(c[8], c[9 + sampleIndex]);
+            const std::string* ft = fmt.find("FT");
             if (c[6] != "PASS" || (ft && *ft != "PASS")) continue;
-            const std::string* gt = find("GT"); if (!gt) continue;
+            const std::string* gt = fmt.find("GT"); if (!gt) continue;
             if (isSomatic) {
                 if (!het(*gt)) continue;
-                if (const std::string* gqx = find("GQX")) {
+                if (const std::string* gqx = fmt.find("GQX")) {
                     if (*gqx == ".") continue;
                     double v; if (!parse_decimal(*gqx, v)) { fprintf(stderr, "System.FormatException: GQX '%s' at %s:%s is not a number\n", gqx->c_str(), c[0].c_str(), c[1].c_str()); return 255; }
                     if (v < 30) continue;
@@ -78,26 +74,6 @@ static std::string format_double(double v) {
     std::string out = std::signbit(v) ? "-" : ""; out.push_back(d[0]); if (d.size() > 1) { out.push_back('.'); out += d.substr(1); }
     return out + "E-05";
 }
-
-struct Block { size_t in, clen; uint32_t isize; };
-// the BGZF block at file offset `at`: false = not a block / truncated
-static bool bgzf_block_at(const unsigned char* f, size_t n, size_t at, Block& b, size_t& next) {
-    if (at + 18 > n) return false;
-    const unsigned char* h = f + at;
-    if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return false;
-    const size_t xlen = (size_t)h[10] | ((size_t)h[11] << 8);
-    if (at + 12 + xlen > n) return false;
-    long bsize = -1;
-    for (size_t i = 0; i + 4 <= xlen;) { const size_t slen = (size_t)h[12 + i + 2] | ((size_t)h[12 + i + 3] << 8); if (h[12 + i] == 'B' && h[12 + i + 1] == 'C' && slen == 2 && i + 6 <= xlen) bsize = (long)h[12 + i + 4] | ((long)h[12 + i + 5] << 8); i += 4 + slen; }
-    if (bsize < 0 || (size_t)bsize + 1 < 12 + xlen + 8 || at + (size_t)bsize + 1 > n) return false;
-    b.in = at + 12 + xlen; b.clen = (size_t)bsize + 1 - 12 - xlen - 8;
-    const unsigned char* tr = f + at + bsize + 1 - 4;
-    b.isize = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-    if (b.isize > 65536) return false;
-    next = at + (size_t)bsize + 1;
-    return true;
-}
-static inline uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
 int main(int argc, char** argv) {
     printf(">>>Command-line arguments:\n"); for (int i = 1; i < argc; i++) printf("%s ", argv[i]); printf("\n");   // Utilities.LogCommandLine
@@ -131,13 +107,16 @@ int main(int argc, char** argv) {
             sampleIndex = (int)(it - samples.begin());
         } else if (samples.size() > 1) { fprintf(stderr, "System.ArgumentException: File '%s' contains >1 samples, name for a sample of interest must be provided\n", vcfPath.c_str()); return 255; }
     }
-    int refId = -1;
-    { Bgzf z; BamHeader bh; if (!z.open(bamPath) || !read_bam_header(z, bh)) { fprintf(stderr, "CanvasSNV: %s is not a BAM file\n", bamPath.c_str()); return 1; }
-      for (size_t r = 0; r < bh.refNames.size(); r++) if (bh.refNames[r] == chrom) { refId = (int)r; break; } }
-    if (refId < 0) { fprintf(stderr, "System.ArgumentException: Error: Chromosome name '%s' does not match bam file at '%s'\n", chrom.c_str(), bamPath.c_str()); return 255; }
-    if (!file_exists(bamPath + ".bai")) { fprintf(stderr, "Fatal error: Bam index not found at %s.bai\n", bamPath.c_str()); return 255; }
-    uint64_t voff = 0; bool anyReads = false;
-    if (!bai_first_offset(bamPath + ".bai", refId, voff, anyReads)) { fprintf(stderr, "CanvasSNV: cannot read %s.bai\n", bamPath.c_str()); return 1; }
+    int refId = -1; uint64_t voff = 0; bool anyReads = false;
+    { BamAt b;
+      switch (bam_open_at(bamPath, chrom, b)) {
+          case BamOpen::Ok: break;
+          case BamOpen::NotBam: fprintf(stderr, "CanvasSNV: %s is not a BAM file\n", bamPath.c_str()); return 1;
+          case BamOpen::NoSuchRef: fprintf(stderr, "System.ArgumentException: Error: Chromosome name '%s' does not match bam file at '%s'\n", chrom.c_str(), bamPath.c_str()); return 255;
+          case BamOpen::NoIndex: fprintf(stderr, "Fatal error: Bam index not found at %s.bai\n", bamPath.c_str()); return 255;
+          case BamOpen::BadIndex: fprintf(stderr, "CanvasSNV: cannot read %s.bai\n", bamPath.c_str()); return 1;
+      }
+      refId = b.ref; voff = b.voff; anyReads = b.any; }
     ph.mark("startup");
 
     AsyncCtx actx;                                               // the context comes up while the VCF is parsed
@@ -156,27 +135,26 @@ int main(int argc, char** argv) {
     long long overall = 0, chunks = 0, bytesUp = 0; double kernelMs = 0;
     canvas_ctx* ctx = nullptr;
     if (anyReads && nsites > 0) {          // (no site: the reference leaves its loop at the first read that passes the filters; no read: nothing to count)
-        MappedFileRO mf; if (!mf.open(bamPath)) { fprintf(stderr, "CanvasSNV: cannot map %s\n", bamPath.c_str()); return 1; }
-        const unsigned char* F = (const unsigned char*)mf.p; const size_t FN = mf.n;
+        MappedFile mf; if (!mf.open(bamPath)) { fprintf(stderr, "CanvasSNV: cannot map %s\n", bamPath.c_str()); return 1; }
+        const uint8_t* F = (const uint8_t*)mf.p; const size_t FN = mf.n;
         size_t chunkBytes = (size_t)32 << 20;
         if (const char* e = getenv("CANVAS_SNV_CHUNK_BYTES")) { const long long v = atoll(e); if (v >= 65536) chunkBytes = (size_t)v; }
         // blocks of the first chunk: sizes the buffers (a small file gets small ones: pinning costs time per megabyte)
         size_t fileAt = (size_t)(voff >> 16); size_t skip = (size_t)(voff & 0xFFFF);
-        std::vector<Block> blocks; bool eof = false;
+        std::vector<BgzfBlock> blocks; bool eof = false;          // (`in` made an offset in the file)
         auto collect = [&](size_t& total) -> bool {
             blocks.clear(); total = 0;
             while (total < chunkBytes) {
                 if (fileAt >= FN) { eof = true; break; }
-                Block b; size_t next;
-                if (!bgzf_block_at(F, FN, fileAt, b, next)) { fprintf(stderr, "CanvasSNV: %s: truncated or damaged BGZF block at byte %zu\n", bamPath.c_str(), fileAt); return false; }
-                blocks.push_back(b); total += b.isize; fileAt = next;
+                BgzfBlock b; const size_t size = bgzf_parse(F + fileAt, FN - fileAt, b);
+                if (size == 0 || size > FN - fileAt) { fprintf(stderr, "CanvasSNV: %s: truncated or damaged BGZF block at byte %zu\n", bamPath.c_str(), fileAt); return false; }
+                b.in += fileAt; blocks.push_back(b); total += b.isize; fileAt += size;
             }
             return true;
         };
         size_t total = 0; if (!collect(total)) return 1;
         const size_t cap = 2 * std::min(chunkBytes + 65536, std::max<size_t>(total, 65536)) + 2 * 65536, offCap = cap / 36 + 16;
-        ctx = actx.get();
-        if (!ctx) { fprintf(stderr, "CanvasSNV (MI355X): no usable GPU (this build has no CPU fallback)\n"); return 1; }
+        if (!(ctx = actx.require("CanvasSNV"))) return 1;
         const bool timing = getenv("CANVAS_TOOL_TIMING") != nullptr;
         if (timing) (void)canvas_profile_enable(ctx, 1);
         std::unique_ptr<uint8_t[]> hRec[2] = {std::unique_ptr<uint8_t[]>(new uint8_t[cap]), std::unique_ptr<uint8_t[]>(new uint8_t[cap])};
@@ -199,13 +177,8 @@ int main(int argc, char** argv) {
             for (size_t i = 0; i < blocks.size(); i++) pre[i + 1] = pre[i] + blocks[i].isize;
             std::atomic<bool> ok(true);
             parallel_for((int64_t)blocks.size(), [&](int64_t i) {
-                const Block& b = blocks[(size_t)i]; if (b.isize == 0) return;
-                z_stream zs; memset(&zs, 0, sizeof zs);
-                if (inflateInit2(&zs, -15) != Z_OK) { ok = false; return; }
-                zs.next_in = (Bytef*)(F + b.in); zs.avail_in = (uInt)b.clen; zs.next_out = buf + pre[(size_t)i]; zs.avail_out = b.isize;
-                const int rc = inflate(&zs, Z_FINISH);
-                if (rc != Z_STREAM_END || zs.avail_out != 0) ok = false;
-                inflateEnd(&zs);
+                const BgzfBlock& b = blocks[(size_t)i];
+                if (b.isize && !inflate_raw(F + b.in, b.clen, buf + pre[(size_t)i], b.isize)) ok = false;
             });
             if (!ok) { fprintf(stderr, "CanvasSNV: %s: a BGZF block does not inflate to its recorded size\n", bamPath.c_str()); return 1; }
             const size_t len = carry + total;
@@ -213,11 +186,11 @@ int main(int argc, char** argv) {
             size_t at = skip; skip = 0; int64_t nrec = 0;
             if (at > len) { fprintf(stderr, "CanvasSNV: %s.bai points behind the end of a block\n", bamPath.c_str()); return 1; }
             while (at + 4 <= len) {
-                const uint32_t bs = le32(buf + at);
-                if ((int32_t)bs < 32) { fprintf(stderr, "CanvasSNV: %s: malformed alignment record (block_size %d)\n", bamPath.c_str(), (int32_t)bs); return 1; }
-                if ((size_t)bs > len - at - 4) break;                                        // completed by the next chunk
-                const uint8_t* r = buf + at + 4;
-                const int32_t rid = (int32_t)le32(r), pos = (int32_t)le32(r + 4), lseq = (int32_t)le32(r + 16); const uint32_t lname = r[8], ncig = (uint32_t)r[12] | ((uint32_t)r[13] << 8);
+                const int32_t bs = (int32_t)le32(buf + at);
+                if (bs >= 32 && (size_t)bs > len - at - 4) break;                            // completed by the next chunk
+                const uint8_t* r = buf + at + 4; BamFixed fx;
+                if (!fx.decode(r, bs)) { fprintf(stderr, "CanvasSNV: %s: malformed alignment record (block_size %d)\n", bamPath.c_str(), bs); return 1; }
+                const int32_t rid = fx.refID, pos = fx.pos, lseq = fx.l_seq; const uint32_t lname = fx.l_read_name, ncig = fx.n_cigar;
                 if (lseq < 0 || 32ull + lname + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > (uint64_t)bs) { fprintf(stderr, "CanvasSNV: %s: malformed alignment record at position %d (its name, CIGAR and bases do not fit its block_size)\n", bamPath.c_str(), pos); return 1; }
                 if (rid < 0 || pos < 0 || rid > refId) { done = true; break; }               // past the chromosome of interest
                 if (rid == refId) {

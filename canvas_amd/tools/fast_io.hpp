@@ -16,6 +16,7 @@
 #include <string>
 #include <thread>
 #include <vector>
+#include "bam_io.hpp"
 
 namespace tool {
 
@@ -30,17 +31,17 @@ static void parallel_for(int64_t n, const Fn& fn, int threads = 0) {
     for (auto& t : th) t.join();
 }
 
-// ---- a file mapped read-only (the chunk reader below)
-struct MappedFileRO {
+// ---- a file mapped read-only; sequential: the whole file is read front to back (advice to the kernel's read-ahead)
+struct MappedFile {
     const char* p = nullptr; size_t n = 0; int fd = -1;
-    bool open(const std::string& path) {
+    bool open(const std::string& path, bool sequential = false) {
         fd = ::open(path.c_str(), O_RDONLY); if (fd < 0) return false;
         struct stat st; if (fstat(fd, &st) != 0) return false;
         n = (size_t)st.st_size; if (n == 0) { p = ""; return true; }
-        void* m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0); if (m == MAP_FAILED) { p = nullptr; return false; }
-        p = (const char*)m; return true;
+        void* m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0); if (m == MAP_FAILED) return false;
+        p = (const char*)m; if (sequential) madvise(m, n, MADV_SEQUENTIAL); return true;
     }
-    ~MappedFileRO() { if (p && n) munmap((void*)p, n); if (fd >= 0) ::close(fd); }
+    ~MappedFile() { if (p && n) munmap((void*)p, n); if (fd >= 0) ::close(fd); }
 };
 // ---- writing: rows [0, nrows) formatted by fmt(i, out) (appends the row WITHOUT the newline), chunks of rows compressed on several threads, one gzip member
 // The header carries an index of the chunks in a gzip "extra" subfield (RFC 1952 FEXTRA, id "CV": chunk count, then {compressed bytes, text bytes} per chunk — what BGZF
@@ -103,7 +104,7 @@ static inline void append_int(std::string& out, long long v) { if (v < 0) { out.
 // own: the writer compressed them independently) and its CRC checked from the chunks' CRCs; any other gzip file is inflated by one thread (a deflate stream is
 // sequential).  The lines are then parsed on several threads.
 static bool read_gz_indexed(const std::string& path, std::string& data) {
-    MappedFileRO mf; if (!mf.open(path) || mf.n < 18 + 10) return false;
+    MappedFile mf; if (!mf.open(path) || mf.n < 18 + 10) return false;
     const unsigned char* p = (const unsigned char*)mf.p;
     if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4) return false;                 // exactly the header the writer produces: FEXTRA and nothing else
     const size_t xlen = (size_t)p[10] | ((size_t)p[11] << 8);
@@ -121,13 +122,8 @@ static bool read_gz_indexed(const std::string& path, std::string& data) {
     data.resize(toff[nchunks]);
     std::vector<uLong> crcs((size_t)nchunks); std::atomic<bool> ok(true);
     parallel_for((int64_t)nchunks, [&](int64_t c) {
-        z_stream zs; memset(&zs, 0, sizeof zs);
-        if (inflateInit2(&zs, -15) != Z_OK) { ok = false; return; }
-        zs.next_in = (Bytef*)(p + zoff[(size_t)c]); zs.avail_in = (uInt)(zoff[(size_t)c + 1] - zoff[(size_t)c]);
-        zs.next_out = (Bytef*)&data[toff[(size_t)c]]; zs.avail_out = (uInt)(toff[(size_t)c + 1] - toff[(size_t)c]);
-        const int rc = inflate(&zs, Z_FINISH);               // (every chunk but the last ends at a sync flush, not at a final block: Z_BUF_ERROR / Z_OK with everything consumed is its normal end)
-        if (!(rc == Z_STREAM_END || rc == Z_OK || rc == Z_BUF_ERROR) || zs.avail_in != 0 || zs.avail_out != 0) ok = false;
-        inflateEnd(&zs);
+        // (every chunk but the last ends at a sync flush, not at a final block)
+        if (!inflate_raw(p + zoff[(size_t)c], zoff[(size_t)c + 1] - zoff[(size_t)c], &data[toff[(size_t)c]], toff[(size_t)c + 1] - toff[(size_t)c], true)) ok = false;
         crcs[(size_t)c] = crc32(crc32(0L, Z_NULL, 0), (const Bytef*)&data[toff[(size_t)c]], (uInt)(toff[(size_t)c + 1] - toff[(size_t)c]));
     });
     if (!ok) return false;
@@ -202,17 +198,50 @@ static bool read_text_rows(const std::string& path, int minFields, TextRows& out
     return true;
 }
 
-// ---- a file mapped read-only
-struct MappedFile {
-    const char* p = nullptr; size_t n = 0; int fd = -1;
-    bool open(const std::string& path) {
-        fd = ::open(path.c_str(), O_RDONLY); if (fd < 0) return false;
-        struct stat st; if (fstat(fd, &st) != 0) return false;
-        n = (size_t)st.st_size; if (n == 0) { p = ""; return true; }
-        void* m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0); if (m == MAP_FAILED) return false;
-        p = (const char*)m; madvise(m, n, MADV_SEQUENTIAL); return true;
+// ---- FASTA.  Every entry of a mapped file, or only those named *only: the name is what follows '>' up to the first blank or tab; [seq, end) are the sequence's bytes in
+// the file, line ends included; len is its length without them ('\n' and every '\r'); single: the sequence is one line, so [seq, seq + len) is the sequence itself
+struct FastaEntry { std::string name; size_t seq, end; int64_t len; bool single; };
+static std::vector<FastaEntry> scan_fasta(const MappedFile& mf, const std::string* only = nullptr) {
+    const char* p = mf.p; const size_t n = mf.n;
+    std::vector<size_t> hdr;
+    {   // '>' at the start of a line (scanned in slices on several threads, then put in order)
+        const int nt = io_threads();
+        std::vector<std::vector<size_t>> found((size_t)nt);
+        parallel_for(nt, [&](int64_t t) {
+            size_t a = n / (size_t)nt * (size_t)t, b = t == nt - 1 ? n : n / (size_t)nt * (size_t)(t + 1);
+            for (const char* q = p + a; q < p + b;) { q = (const char*)memchr(q, '>', (size_t)(p + b - q)); if (!q) break; if (q == p || q[-1] == '\n') found[(size_t)t].push_back((size_t)(q - p)); q++; }
+        });
+        for (auto& v : found) hdr.insert(hdr.end(), v.begin(), v.end());
     }
-    ~MappedFile() { if (p && n) munmap((void*)p, n); if (fd >= 0) ::close(fd); }
-};
+    std::vector<FastaEntry> ents;
+    for (size_t i = 0; i < hdr.size(); i++) {
+        const char* le = (const char*)memchr(p + hdr[i], '\n', n - hdr[i]);
+        const size_t lineEnd = le ? (size_t)(le - p) : n;
+        std::string name(p + hdr[i] + 1, lineEnd - hdr[i] - 1);
+        while (!name.empty() && name.back() == '\r') name.pop_back();
+        name = name.substr(0, name.find_first_of(" \t"));
+        if (!only || name == *only) ents.push_back({name, std::min(n, lineEnd + 1), i + 1 < hdr.size() ? hdr[i + 1] : n, 0, false});
+    }
+    parallel_for((int64_t)ents.size(), [&](int64_t k) {
+        FastaEntry& e = ents[(size_t)k]; const char* s = p + e.seq; const char* end = p + e.end;
+        const char* le = (const char*)memchr(s, '\n', (size_t)(end - s)); const char* te = le ? le : end;      // the first line, then without its trailing '\r's
+        while (te > s && te[-1] == '\r') te--;
+        e.single = !memchr(s, '\r', (size_t)(te - s));
+        for (const char* q = le ? le : end; e.single && q < end; q++) e.single = *q == '\n' || *q == '\r';                         // nothing but line ends behind it
+        e.len = te - s;
+        if (!e.single) { e.len = 0; for (const char* q = s; q < end; q++) e.len += *q != '\n' && *q != '\r'; }
+    });
+    return ents;
+}
+// the bytes of [begin, end) without their line ends; returns the end of what was written
+static char* unfold(const char* begin, const char* end, char* dst) {
+    for (const char* q = begin; q < end;) {
+        const char* le = (const char*)memchr(q, '\n', (size_t)(end - q)); const char* stop = le ? le : end;
+        if (!memchr(q, '\r', (size_t)(stop - q))) { memcpy(dst, q, (size_t)(stop - q)); dst += stop - q; }
+        else for (const char* r = q; r < stop; r++) if (*r != '\r') *dst++ = *r;
+        q = le ? le + 1 : end;
+    }
+    return dst;
+}
 
 }  // namespace tool

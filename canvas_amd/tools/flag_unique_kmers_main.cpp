@@ -4,40 +4,11 @@
 // message and exit code 1.  The flags come from canvas_flag_unique_kmers, the letter case from canvas_fasta_case_from_mask; there is no host implementation of either.
 // File layout (Isas.SequencingFiles' FastaReader / FastaWriter are not part of the reference tree): an entry's name is what follows '>' up to the first blank
 // or tab; '\r' and line folds of the input are dropped; the output is '>' + name, '\n', the whole sequence on ONE line, '\n' — the layout CanvasBin maps without a copy
-// (canvas_bin_main.cpp: read_fasta); an empty entry is its header and an empty line.
+// (canvas_bin_main.cpp: read_fasta; the scan both share: fast_io.hpp); an empty entry is its header and an empty line.
 // --table-gb X bounds the working table of the device (canvas_flag_unique_kmers' max_table_bytes); the output does not depend on it.
 #include "tool_common.hpp"
 #include <memory>
 using namespace tool;
-
-// the mapped-file FASTA scan of canvas_bin_main.cpp (read_fasta), with the entries copied straight to their place in one staging buffer instead of into strings
-struct FaEntry { std::string name; size_t seq, end; int64_t len = 0, at = 0; };        // [seq, end) of the mapped file; length without line ends; offset in the staging buffer
-static void scan_fasta(const MappedFile& mf, std::vector<FaEntry>& ents) {
-    const char* p = mf.p; const size_t n = mf.n;
-    {   // '>' at the start of a line (scanned in slices on several threads, then put in order)
-        const int nt = io_threads();
-        std::vector<std::vector<size_t>> found((size_t)nt);
-        parallel_for(nt, [&](int64_t t) {
-            size_t a = n / (size_t)nt * (size_t)t, b = t == nt - 1 ? n : n / (size_t)nt * (size_t)(t + 1);
-            for (const char* q = p + a; q < p + b;) { q = (const char*)memchr(q, '>', (size_t)(p + b - q)); if (!q) break; if (q == p || q[-1] == '\n') found[(size_t)t].push_back((size_t)(q - p)); q++; }
-        });
-        for (auto& v : found) for (size_t h : v) { FaEntry e; e.seq = h; e.end = n; ents.push_back(e); }
-    }
-    for (size_t i = 0; i < ents.size(); i++) {
-        const size_t hdr = ents[i].seq;
-        const char* le = (const char*)memchr(p + hdr, '\n', n - hdr);
-        const size_t lineEnd = le ? (size_t)(le - p) : n;
-        std::string name(p + hdr + 1, lineEnd - hdr - 1);
-        while (!name.empty() && (name.back() == '\r')) name.pop_back();
-        const size_t sp = name.find_first_of(" \t"); if (sp != std::string::npos) name = name.substr(0, sp);
-        ents[i].name = name; ents[i].seq = std::min(n, lineEnd + 1); ents[i].end = i + 1 < ents.size() ? ents[i + 1].seq : n;      // (the next entry's seq still holds its header offset here)
-    }
-    parallel_for((int64_t)ents.size(), [&](int64_t k) {
-        FaEntry& e = ents[(size_t)k]; int64_t len = 0;
-        for (const char* q = p + e.seq; q < p + e.end; q++) if (*q != '\n' && *q != '\r') len++;
-        e.len = len;
-    });
-}
 
 int main(int argc, char** argv) {
     std::vector<std::string> pos; double tableGb = 0; bool badOpt = false;
@@ -57,43 +28,34 @@ int main(int argc, char** argv) {
     Phases ph("FlagUniqueKmers");
     const double t0 = Phases::now();
     MappedFile mf;
-    if (!mf.open(inFile)) { fprintf(stderr, "FlagUniqueKmers: cannot read %s\n", inFile.c_str()); return 1; }
+    if (!mf.open(inFile, true)) { fprintf(stderr, "FlagUniqueKmers: cannot read %s\n", inFile.c_str()); return 1; }
     const int fd = ::open(outFile.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fd < 0) { fprintf(stderr, "FlagUniqueKmers: cannot write %s\n", outFile.c_str()); return 1; }
     AsyncCtx actx;                                              // the context comes up while the file is scanned
 
-    std::vector<FaEntry> ents;
-    scan_fasta(mf, ents);
+    const std::vector<FastaEntry> ents = scan_fasta(mf);
     const int nchr = (int)ents.size();
     // every contig starts at a multiple of 64 bytes of one staging buffer: its mask words then line up with the buffer's own (word i = bytes 64 i .. 64 i + 63), so
     // the case of the whole genome is set by ONE canvas_fasta_case_from_mask call over the buffer; the padding bytes are 0, no letters
-    int64_t words = 0;
-    for (auto& e : ents) {
-        if (e.len > 0x7FFFFFFFll) { fprintf(stderr, "FlagUniqueKmers: entry %s is longer than 2^31 - 1 bases\n", e.name.c_str()); return 1; }
-        e.at = words * 64; words += (e.len + 63) / 64;
+    int64_t words = 0; std::vector<int64_t> at((size_t)nchr);                // offset of every entry in the staging buffer
+    for (int c = 0; c < nchr; c++) {
+        if (ents[(size_t)c].len > 0x7FFFFFFFll) { fprintf(stderr, "FlagUniqueKmers: entry %s is longer than 2^31 - 1 bases\n", ents[(size_t)c].name.c_str()); return 1; }
+        at[(size_t)c] = words * 64; words += (ents[(size_t)c].len + 63) / 64;
     }
     std::vector<uint8_t> stage((size_t)words * 64, 0);
-    parallel_for(nchr, [&](int64_t k) {
-        const FaEntry& e = ents[(size_t)k]; uint8_t* dst = stage.data() + e.at;
-        for (const char* q = mf.p + e.seq; q < mf.p + e.end;) {
-            const char* le = (const char*)memchr(q, '\n', (size_t)(mf.p + e.end - q)); const char* stop = le ? le : mf.p + e.end;
-            for (const char* r = q; r < stop; r++) if (*r != '\r') *dst++ = (uint8_t)*r;
-            q = le ? le + 1 : mf.p + e.end;
-        }
-    });
+    parallel_for(nchr, [&](int64_t k) { unfold(mf.p + ents[(size_t)k].seq, mf.p + ents[(size_t)k].end, (char*)stage.data() + at[(size_t)k]); });
     ph.mark("read");
     const double t1 = Phases::now();
 
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (auto& e : ents) stats[0] += e.len;
     if (words > 0) {
-        canvas_ctx* ctx = actx.get();
-        if (!ctx) { fprintf(stderr, "FlagUniqueKmers (MI355X): no usable GPU (this build has no CPU fallback)\n"); return 1; }
+        canvas_ctx* ctx = actx.require("FlagUniqueKmers"); if (!ctx) return 1;
         Dev dBases(ctx, words * 64), dMask(ctx, words * 8);
         if (!dBases.p || !dMask.p) { fprintf(stderr, "FlagUniqueKmers: cannot allocate %lld bytes of device memory\n", (long long)(words * 72)); return 1; }
         TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dBases.p, stage.data(), words * 64));
         std::vector<const uint8_t*> pb((size_t)nchr); std::vector<uint64_t*> pm((size_t)nchr); std::vector<int64_t> lens((size_t)nchr);
-        for (int c = 0; c < nchr; c++) { pb[(size_t)c] = dBases.as<uint8_t>() + ents[(size_t)c].at; pm[(size_t)c] = dMask.as<uint64_t>() + ents[(size_t)c].at / 64; lens[(size_t)c] = ents[(size_t)c].len; }
+        for (int c = 0; c < nchr; c++) { pb[(size_t)c] = dBases.as<uint8_t>() + at[(size_t)c]; pm[(size_t)c] = dMask.as<uint64_t>() + at[(size_t)c] / 64; lens[(size_t)c] = ents[(size_t)c].len; }
         TOOL_TRY(ctx, canvas_flag_unique_kmers(ctx, nchr, pb.data(), lens.data(), pm.data(), (int64_t)(tableGb * 1073741824.0), stats));
         TOOL_TRY(ctx, canvas_fasta_case_from_mask(ctx, dBases.as<uint8_t>(), words * 64, dMask.as<uint64_t>()));
         TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, stage.data(), dBases.p, words * 64));
@@ -107,10 +69,10 @@ int main(int argc, char** argv) {
     std::atomic<bool> ok(true);
     auto put = [&](const void* src, size_t n, int64_t at) { const char* s = (const char*)src; while (n) { const ssize_t k = pwrite(fd, s, n, (off_t)at); if (k <= 0) { ok = false; return; } s += k; n -= (size_t)k; at += k; } };
     parallel_for(nchr, [&](int64_t k) {
-        const FaEntry& e = ents[(size_t)k];
+        const FastaEntry& e = ents[(size_t)k];
         const std::string hdr = ">" + e.name + "\n";
         put(hdr.data(), hdr.size(), off[(size_t)k]);
-        put(stage.data() + e.at, (size_t)e.len, off[(size_t)k] + (int64_t)hdr.size());
+        put(stage.data() + at[(size_t)k], (size_t)e.len, off[(size_t)k] + (int64_t)hdr.size());
         put("\n", 1, off[(size_t)k] + (int64_t)hdr.size() + e.len);
     });
     if (::close(fd) != 0 || !ok) { fprintf(stderr, "FlagUniqueKmers: cannot write %s\n", outFile.c_str()); return 1; }

@@ -1,4 +1,4 @@
-// Shared host code of the drop-in tool drivers (CanvasClean / CanvasPartition / CanvasNormalize): option parsing in the reference's NDesk OptionSet
+// Shared host code of the drop-in tool drivers (CanvasBin / CanvasClean / CanvasPartition / CanvasNormalize / CanvasSNV / FlagUniqueKmers): option parsing in the reference's NDesk OptionSet
 // style, gzip text I/O of the intermediate files (CanvasCommon/IO.cs), .NET Core 2.x number formatting, and the
 // IsAutosome assumption (Isas.SequencingFiles is not in /root/reference: "optional chr prefix + integer").
 // The drivers use ONLY the C ABI of include/canvas_hip.h (what the C# hosts would P/Invoke).
@@ -101,7 +101,18 @@ static std::atomic<int> g_open_writers{0};      // output objects that still hol
 struct GzWriter { gzFile f; explicit GzWriter(const std::string& path) { f = gzopen(path.c_str(), "wb"); if (f) g_open_writers++; } ~GzWriter() { close(); }
     bool ok() const { return f != nullptr; } void line(const std::string& s) { gzwrite(f, s.data(), (unsigned)s.size()); gzputc(f, '\n'); }
     void close() { if (f) { gzclose(f); f = nullptr; g_open_writers--; } } };
-static std::vector<std::string> split_tab(const std::string& s) { std::vector<std::string> r; size_t a = 0; for (;;) { size_t b = s.find('\t', a); r.push_back(s.substr(a, b == std::string::npos ? b : b - a)); if (b == std::string::npos) break; a = b + 1; } return r; }
+static std::vector<std::string> split(const std::string& s, char sep) { std::vector<std::string> r; size_t a = 0; for (;;) { size_t b = s.find(sep, a); r.push_back(s.substr(a, b == std::string::npos ? b : b - a)); if (b == std::string::npos) break; a = b + 1; } return r; }
+static std::vector<std::string> split_tab(const std::string& s) { return split(s, '\t'); }
+// the sample's value of a FORMAT key (VCF columns 9 and 10+: "GT:GQX" and "0/1:30"); nullptr: the record has no such key
+struct VcfFormat { std::vector<std::string> keys, vals; VcfFormat(const std::string& format, const std::string& sample) : keys(split(format, ':')), vals(split(sample, ':')) {}
+    const std::string* find(const char* k) const { for (size_t i = 0; i < keys.size() && i < vals.size(); i++) if (keys[i] == k) return &vals[i]; return nullptr; } };
+// every line of a text file without its line end, until fn returns false
+static bool for_each_line(const std::string& path, const std::function<bool(const std::string&)>& fn) {
+    FILE* f = fopen(path.c_str(), "rb"); if (!f) return false;
+    char buf[1 << 14]; bool go = true;
+    while (go && fgets(buf, sizeof buf, f)) { std::string s(buf); while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back(); go = fn(s); }
+    fclose(f); return true;
+}
 static bool file_exists(const std::string& p) { FILE* f = fopen(p.c_str(), "rb"); if (f) { fclose(f); return true; } return false; }
 
 // ---- .NET Core 2.x formatting: float "F2" (7 significant digits, then half-up at 2 decimals) and double "G15"
@@ -147,10 +158,7 @@ static bool is_autosome(std::string name) {
 
 // excluded intervals of a BED file (Utilities.LoadBedFile, CanvasCommon/Utilities.cs:793-829): chr -> (start, stop) in file order
 static bool load_bed(const std::string& path, std::map<std::string, std::vector<std::pair<int, int>>>& out) {
-    FILE* f = fopen(path.c_str(), "rb"); if (!f) return false;
-    char buf[1 << 14];
-    while (fgets(buf, sizeof buf, f)) { std::string s(buf); while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back(); auto t = split_tab(s); if (t.size() < 3) continue; out[t[0]].push_back({atoi(t[1].c_str()), atoi(t[2].c_str())}); }
-    fclose(f); return true;
+    return for_each_line(path, [&](const std::string& s) { auto t = split_tab(s); if (t.size() >= 3) out[t[0]].push_back({atoi(t[1].c_str()), atoi(t[2].c_str())}); return true; });
 }
 
 // PloidyInterval (PloidyInfo.cs:182-198): one-based Start = POS, End = INFO/END, Ploidy = the sample's CN field ("." = 2)
@@ -160,31 +168,27 @@ struct PloidyIv { int start, end, ploidy; };
 static bool load_ploidy_vcf(const std::string& path, std::map<std::string, std::vector<PloidyIv>>& out, std::string& err) {
     GzReader rd(path); if (!rd.ok()) { err = "cannot open ploidy VCF '" + path + "'"; return false; }
     std::string row; int samples = -1;
+    auto one_sample = [&]() {
+        if (samples < 0) err = "File '" + path + "' has no #CHROM header line";
+        else if (samples == 0) err = "File '" + path + "' does not contain any genotype column";
+        else if (samples > 1) err = "File '" + path + "' cannot have more than one genotype columns when no sample ID provided";
+        return samples == 1; };
     while (rd.line(row)) {
         if (row.empty()) continue;
         if (row[0] == '#') { if (row.rfind("#CHROM", 0) == 0) { auto h = split_tab(row); samples = (int)h.size() > 9 ? (int)h.size() - 9 : 0; } continue; }
-        if (samples < 0) { err = "File '" + path + "' has no #CHROM header line"; return false; }
-        if (samples == 0) { err = "File '" + path + "' does not contain any genotype column"; return false; }
-        if (samples > 1) { err = "File '" + path + "' cannot have more than one genotype columns when no sample ID provided"; return false; }
+        if (!one_sample()) return false;
         auto f = split_tab(row);
         if (f.size() < 10) { err = "malformed ploidy VCF record: " + row; return false; }
         PloidyIv iv; iv.start = atoi(f[1].c_str()); iv.end = -1; iv.ploidy = 2;
         bool haveEnd = false;
-        for (size_t a0 = 0; a0 <= f[7].size();) { size_t b = f[7].find(';', a0); std::string kv = f[7].substr(a0, b == std::string::npos ? b : b - a0);
-            if (kv.rfind("END=", 0) == 0) { iv.end = atoi(kv.c_str() + 4); haveEnd = true; } if (b == std::string::npos) break; a0 = b + 1; }
+        for (auto& kv : split(f[7], ';')) if (kv.rfind("END=", 0) == 0) { iv.end = atoi(kv.c_str() + 4); haveEnd = true; }
         if (!haveEnd) { err = "ploidy VCF record without INFO/END: " + row; return false; }            // InfoFields["END"] throws KeyNotFoundException
-        std::vector<std::string> keys, vals;
-        for (int which = 0; which < 2; which++) { const std::string& src = f[which == 0 ? 8 : 9]; auto& dst = which == 0 ? keys : vals;
-            for (size_t a0 = 0;;) { size_t b = src.find(':', a0); dst.push_back(src.substr(a0, b == std::string::npos ? b : b - a0)); if (b == std::string::npos) break; a0 = b + 1; } }
-        bool haveCn = false;
-        for (size_t k = 0; k < keys.size() && k < vals.size(); k++) if (keys[k] == "CN") { haveCn = true; iv.ploidy = vals[k] == "." ? 2 : atoi(vals[k].c_str()); }
-        if (!haveCn) { err = "File '" + path + "' must contain one genotype CN column!"; return false; }
+        const VcfFormat fmt(f[8], f[9]); const std::string* cn = fmt.find("CN");
+        if (!cn) { err = "File '" + path + "' must contain one genotype CN column!"; return false; }
+        iv.ploidy = *cn == "." ? 2 : atoi(cn->c_str());
         out[f[0]].push_back(iv);
     }
-    if (samples < 0) { err = "File '" + path + "' has no #CHROM header line"; return false; }
-    if (samples == 0) { err = "File '" + path + "' does not contain any genotype column"; return false; }
-    if (samples > 1) { err = "File '" + path + "' cannot have more than one genotype columns when no sample ID provided"; return false; }
-    return true;
+    return one_sample();
 }
 // PloidyInfo.GetReferenceCopyNumber of the bin [start, stop) (PloidyInfo.cs:56-75, through CanvasNormalizeUtilities.GetPloidy, :13-20): the copy number that
 // covers most bases, 2 on a chromosome the VCF does not list; -1: a ploidy outside 0..4 indexes past baseCounts (the reference throws)
@@ -248,6 +252,8 @@ struct AsyncCtx {
     explicit AsyncCtx(std::function<void(canvas_ctx*)> warm = nullptr) { th = std::thread([this, warm] { ctx = canvas_create(0); if (ctx && !getenv("CANVAS_TOOL_KEEP_PINNING")) (void)canvas_set_one_shot(ctx, 1);      // (one OS process per sample: nothing amortises pinned staging)
                                                                                               if (ctx && warm && !getenv("CANVAS_TOOL_NO_WARMUP")) warm(ctx); }); }
     canvas_ctx* get() { if (th.joinable()) th.join(); return ctx; }
+    // get(), with the one message of a tool that finds no device
+    canvas_ctx* require(const char* toolName) { if (!get()) fprintf(stderr, "%s (MI355X): no usable GPU (this build has no CPU fallback)\n", toolName); return ctx; }
     ~AsyncCtx() { if (th.joinable()) th.join(); }
 };
 // End of a successful run: every output file is closed by now; the process leaves without unwinding (freeing gigabytes of host vectors, the context's device buffers and

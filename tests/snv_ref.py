@@ -119,6 +119,65 @@ def write_bam(path, refs, reads, cut=3000):
     open(path + ".bai", "wb").write(bai)
 
 
+def bgzf_blocks(raw):
+    """[(offset, size)] of the blocks of a BGZF file as bgzf_block writes them (BC is the first subfield)"""
+    blocks, at = [], 0
+    while at < len(raw):
+        assert raw[at:at + 4] == b"\x1f\x8b\x08\x04" and raw[at + 12:at + 16] == b"BC\x02\x00"
+        size = struct.unpack_from("<H", raw, at + 16)[0] + 1
+        blocks.append((at, size)); at += size
+    return blocks
+
+
+def reblock_bam(src, dst):
+    """The BAM `src` (and its .bai) written again as `dst` with the same inflated stream in another BGZF form: every block carries a subfield of its own in front of BC
+    (XLEN 13 instead of 6), and an empty block (ISIZE 0) stands in the middle of the file.  The virtual offsets of the .bai move with their blocks."""
+    raw = open(src, "rb").read()
+    blocks = bgzf_blocks(raw)
+    extra = b"XY" + struct.pack("<H", 3) + b"abc"
+
+    def with_extra(block):
+        return block[:10] + struct.pack("<H", len(extra) + 6) + extra + b"BC" + struct.pack("<HH", 2, len(block) + len(extra) - 1) + block[18:]
+    out, moved = bytearray(), {}
+    for i, (at, size) in enumerate(blocks):
+        if i == len(blocks) // 2:
+            out += with_extra(bgzf_block(b""))
+        moved[at] = len(out)
+        out += with_extra(raw[at:at + size])
+    moved[len(raw)] = len(out)
+    assert bgzf_read_all(src) == zlib_stream(bytes(out))
+    open(dst, "wb").write(out)
+    bai = open(src + ".bai", "rb").read()
+    new, at = bytearray(bai[:8]), 8
+
+    def copy(n):
+        nonlocal at
+        new.extend(bai[at:at + n]); at += n
+        return struct.unpack_from("<i", bai, at - 4)[0]
+
+    def offsets(n):
+        nonlocal at
+        for v in struct.unpack_from("<%dQ" % n, bai, at):
+            new.extend(struct.pack("<Q", (moved[v >> 16] << 16) | (v & 0xFFFF)))
+        at += 8 * n
+    for _ in range(struct.unpack_from("<i", bai, 4)[0]):
+        for _ in range(copy(4)):                   # n_bin
+            offsets(2 * copy(8))                   # bin, n_chunk; chunk_beg, chunk_end
+        offsets(copy(4))                           # n_intv; ioffset
+    assert at == len(bai)
+    open(dst + ".bai", "wb").write(new)
+
+
+def zlib_stream(raw):
+    """the inflated stream of BGZF bytes whose blocks may carry any subfields (zlib's own gzip reader, member after member)"""
+    out = bytearray()
+    while raw:
+        d = zlib.decompressobj(31)
+        out += d.decompress(raw)
+        raw = d.unused_data
+    return bytes(out)
+
+
 def read_bam(path):
     """-> ([(name, length)], [record dict] in file order)"""
     buf = bgzf_read_all(path)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import snv_ref as SR
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -490,3 +491,90 @@ def test_canvasbin_on_the_references_own_bam(tmp_path):
     # the fixture holds nine chrM reads and every one of them starts with a soft clip: the reference's "first CIGAR operation is a match of 35 and more" rule keeps none
     assert len(reads) == 9 and len(kept) == 0 and int(got.sum()) == 0
     assert "Kept 0 of 9 total reads" in r.stdout
+
+
+def _small_sample(tmp_path):
+    """two contigs of a few thousand bases and a few hundred forward reads on each; the BAM is cut into blocks of 3000 bytes, so records span blocks"""
+    rng = np.random.RandomState(20261101)
+    refs = [("chr1", 6_001), ("chr2", 4_000)]
+    seqs = []
+    for _, ln in refs:
+        b = rng.choice(np.frombuffer(b"ACGTacgtn", np.uint8), ln)
+        seqs.append(b.tobytes())
+    reads = [dict(ref=ri, pos=int(p), flag=0x1 | 0x2 | 0x40, cigar=[(36, "M")], tlen=300) for ri, (_, ln) in enumerate(refs) for p in np.sort(rng.randint(0, ln - 40, 400))]
+    bam = str(tmp_path / "S.bam")
+    _write_bam(bam, refs, reads)
+    return refs, seqs, bam
+
+
+def _write_fasta_form(path, refs, seqs, width, eol, last_eol):
+    """an empty entry first, descriptions behind the names, the sequences folded at `width` with `eol`; last_eol = False: the last line has no line end"""
+    with open(path, "wb") as f:
+        f.write(b">chrNothing  an empty entry" + eol)
+        for i, ((name, _), s) in enumerate(zip(refs, seqs)):
+            f.write(b">" + name.encode() + b" AC:CM00066%d.2\tLN:%d" % (i, len(s)) + eol)
+            f.write(eol.join(s[k:k + width] for k in range(0, len(s), width)))
+            if last_eol or i + 1 < len(refs):
+                f.write(eol)
+
+
+def _dats(tmp_path, tag, bam, fa, refs):
+    out = []
+    for name, _ in refs:
+        dat = str(tmp_path / f"{tag}.{name}.dat")
+        r = subprocess.run([BIN, "-b", bam, "-r", fa, "-c", name, "-o", dat, "-d", "100", "-p"], capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout + r.stderr
+        out.append(open(dat, "rb").read())
+    return out
+
+
+def test_canvasbin_fasta_forms_give_the_same_dat(tmp_path):
+    """kmer.fa as one line per sequence with LF, folded at 60 with CRLF, and folded with the last line lacking its line end: CanvasBin -c writes the same bytes"""
+    from canvas_amd import build
+    build.build(); build.build_tools()
+    refs, seqs, bam = _small_sample(tmp_path)
+    got = []
+    for tag, width, eol, last_eol in (("single", 1 << 30, b"\n", True), ("crlf60", 60, b"\r\n", True), ("no_last_eol", 60, b"\n", False)):
+        fa = str(tmp_path / f"{tag}.fa")
+        _write_fasta_form(fa, refs, seqs, width, eol, last_eol)
+        got.append(_dats(tmp_path, tag, bam, fa, refs))
+    assert got[1] == got[0] and got[2] == got[0]
+    for (name, ln), dat in zip(refs, got[0]):
+        d = _decode_dat(dat)
+        assert len(d[2][name]) == ln and 0 < np.frombuffer(d[2][name], np.uint8).sum() <= 400          # real work: the observed alignments of the reads
+
+
+def test_canvasbin_bgzf_forms_give_the_same_dat(tmp_path):
+    """BGZF blocks with a subfield in front of BC and an empty block in the middle of the file, records spanning blocks: the same .dat bytes as from the BAM written plainly"""
+    from canvas_amd import build
+    build.build(); build.build_tools()
+    refs, seqs, bam = _small_sample(tmp_path)
+    fa = str(tmp_path / "kmer.fa")
+    _write_fasta_form(fa, refs, seqs, 1 << 30, b"\n", True)
+    assert len(SR.bgzf_blocks(open(bam, "rb").read())) > 20
+    other = str(tmp_path / "other_form.bam")
+    SR.reblock_bam(bam, other)
+    assert _dats(tmp_path, "other", other, fa, refs) == _dats(tmp_path, "plain", bam, fa, refs)
+
+
+@pytest.mark.parametrize("damage", ["cut_inside_a_block", "bsize_below_the_header"])
+def test_canvasbin_refuses_a_damaged_bam(tmp_path, damage):
+    """a BAM that ends inside a BGZF block, or one of whose blocks states a BSIZE smaller than its own header: exit code 1, the file named, no .dat (host code only)"""
+    from canvas_amd import build
+    build.build(); build.build_tools()
+    refs, seqs, bam = _small_sample(tmp_path)
+    fa = str(tmp_path / "kmer.fa")
+    _write_fasta_form(fa, refs, seqs, 1 << 30, b"\n", True)
+    raw = bytearray(open(bam, "rb").read())
+    at, size = SR.bgzf_blocks(raw)[3]                               # block 0 is the header; chr1's records fill more than ten blocks
+    if damage == "cut_inside_a_block":
+        raw = raw[:at + size // 2]
+    else:
+        struct.pack_into("<H", raw, at + 16, 10)
+    bad = str(tmp_path / "damaged.bam")
+    open(bad, "wb").write(raw)
+    open(bad + ".bai", "wb").write(open(bam + ".bai", "rb").read())
+    dat = str(tmp_path / "chr1.dat")
+    r = subprocess.run([BIN, "-b", bad, "-r", fa, "-c", "chr1", "-o", dat, "-d", "100"], capture_output=True, text=True)
+    assert r.returncode == 1 and bad in r.stderr, r.stdout + r.stderr
+    assert not os.path.exists(dat)

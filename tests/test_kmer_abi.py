@@ -51,3 +51,37 @@ def test_missing_input_exits_1(tmp_path):
     r = subprocess.run([exe, str(tmp_path / "missing.fa"), str(out)], capture_output=True, text=True, timeout=60)
     assert r.returncode == 1 and "cannot read" in r.stderr
     assert not out.exists()
+
+
+def test_a_touched_or_new_tool_header_makes_every_tool_stale(tmp_path, monkeypatch):
+    """build_tools() hashes every *.hpp of canvas_amd/tools: after a header changed, or a new one appeared, all six tools are compiled again with another embedded
+    hash; with nothing changed none is.  (The compiler is replaced by a stand-in that writes the hash marker a real binary carries: this is about staleness.)"""
+    import shutil
+    from canvas_amd import build
+    here = tmp_path / "canvas_amd"
+    shutil.copytree(os.path.join(build.HERE, "tools"), here / "tools")
+    monkeypatch.setattr(build, "HERE", str(here))
+    compiled = []
+
+    def stand_in(cmd):
+        out = cmd[cmd.index("-o") + 1]
+        define = [a for a in cmd if a.startswith("-DCANVAS_SRC_HASH=")][0]
+        open(out, "wb").write(build.HASH_MARKER + define.split("=", 1)[1].strip('"').encode())
+        compiled.append(out)
+    monkeypatch.setattr(build.subprocess, "check_call", stand_in)
+
+    def hashes():
+        compiled.clear()
+        outs = build.build_tools()
+        assert len(outs) == 6
+        return [build.embedded_hash(o) for o in outs], len(compiled)
+    first, n = hashes()
+    assert n == 6 and len(set(first)) == 6
+    assert hashes() == (first, 0)
+    with open(here / "tools" / "bam_io.hpp", "a") as f:
+        f.write("// touched\n")
+    second, n = hashes()
+    assert n == 6 and all(a != b for a, b in zip(first, second))
+    (here / "tools" / "a_new_header.hpp").write_text("#pragma once\n")
+    third, n = hashes()
+    assert n == 6 and all(a != b for a, b in zip(second, third))

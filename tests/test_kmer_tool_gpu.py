@@ -96,6 +96,19 @@ def test_tool_end_to_end(cv, tmp_path):
     assert open(out4, "rb").read() == want
 
 
+def test_tool_fasta_forms_with_an_empty_first_entry(cv, tmp_path):
+    """an empty entry FIRST, then contigs of a few thousand bases: one line per sequence with LF, folded at 60 with CRLF, folded with the last line lacking its line end"""
+    rng = np.random.RandomState(78)
+    names, seqs = ["chrNothing", "chrA", "chrB"], [b"", KC.rand_seq(rng, 3001), KC.rand_seq(rng, 2000)]
+    want = R.render_fasta(names, seqs, R.unique_flags_numpy(seqs))
+    for tag, width, eol, last_eol in (("single", 1 << 30, b"\n", True), ("crlf60", 60, b"\r\n", True), ("no_last_eol", 60, b"\n", False)):
+        src = str(tmp_path / (tag + ".fa")); out = str(tmp_path / (tag + ".kmer.fa"))
+        _write_fasta(src, names, seqs, width, eol, last_eol)
+        r = _run([src, out])
+        assert r.returncode == 0, r.stderr
+        assert open(out, "rb").read() == want, tag
+
+
 def test_tool_errors(tmp_path):
     src = str(tmp_path / "g.fa")
     open(src, "wb").write(b">a\n" + KC.rand_seq(np.random.RandomState(1), 500) + b"\n")

@@ -110,6 +110,20 @@ def test_many_chunks_give_the_same_files(synthetic, tmp_path):
     _check(tmp_path, synthetic["one"], synthetic["bam"], "chrB", env={"CANVAS_SNV_CHUNK_BYTES": "65536"})
 
 
+def test_bgzf_forms_give_the_same_files(synthetic, tmp_path):
+    """BGZF blocks with a subfield in front of BC and an empty block in the middle of the file (records span blocks in both): the files of the plainly written BAM"""
+    get_canvas()
+    other = str(tmp_path / "other_form.bam")
+    R.reblock_bam(synthetic["bam"], other)
+    got = []
+    for tag, bam in (("plain", synthetic["bam"]), ("other", other)):
+        out = tmp_path / (tag + ".txt.gz")
+        r = _run(["-c", "chrB", "-v", synthetic["one"], "-b", bam, "-o", out])
+        assert r.returncode == 0, r.stdout + r.stderr
+        got.append((open(out, "rb").read(), open(str(out) + ".baf", "rb").read()))
+    assert got[1] == got[0] and got[0][1].count(b"\n") > 100
+
+
 def test_somatic_dbsnp_sample_name_and_mapq(synthetic, tmp_path):
     _check(tmp_path, synthetic["one"], synthetic["bam"], "chrA", ["-s"], is_somatic=True)
     _check(tmp_path, synthetic["db"], synthetic["bam"], "chrA", ["-i"], is_dbsnp=True)
