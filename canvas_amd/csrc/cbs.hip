@@ -516,13 +516,21 @@ __device__ __forceinline__ int block_excl_scan_i32(int v, int* sh /*PG_T/64 + 1*
 #define PT_TILE 2048
 #define PT_HALO 32
 #define PT_PER (PT_TILE / PG_T)
-__device__ __forceinline__ void perm_stat_tail(const double* __restrict__ px, double* __restrict__ /*sx: not used any more*/, int n, int hk, int al0, double tss, double errBound, double* __restrict__ pstat, int b,
+// The rounding bound of a prefix-sum difference for ONE permutation, from the largest |prefix sum| pm the kernel has formed for it.  The host's bound (gamma_n * sum|x|
+// for either order of summation) holds for every permutation and grows with n^2; from a few hundred thousand bins on it makes the interval wider than the 1e-6 |exact| the
+// engine promises.  Per permutation: the reference adds sequentially, sx[k] = fl(sx[k - 1] + px[k]), so its sx[k] is off by at most k u max|sx| and any difference
+// sx[p] - sx[q] it forms (q < p <= n) by at most (n + 27) u max|sx| (u = 2^-53; for arcs inside the array the common part of the two errors cancels: (j + 2) u max|sx|).  A
+// prefix value of the kernels goes through at most 8 + 6 + 8 + 4 roundings inside its tile, every operand a sum of consecutive values (at most 2 max|sx|), and through the
+// carry of n / PT_TILE tile totals of at most 23 roundings each: less than (0.022 n + 52) u max|sx|, twice that plus one rounding for a difference.  (1.1 n + 256) u pm
+// is above the sum of the two with room for pm itself being a rounded maximum.
+__device__ __forceinline__ double perm_err_bound(double hostBound, double rn, double pm) { const double own = (1.1 * rn + 256.0) * 1.1102230246251565e-16 * pm; return own < hostBound ? own : hostBound; }
+__device__ __forceinline__ void perm_stat_tail(const double* __restrict__ px, double* __restrict__ /*sx: not used any more*/, int n, int hk, int al0, double tss, double errBound /* the host's bound for any permutation */, double* __restrict__ pstat, int b,
                                                double* shD /* [PG_T / 64 + 1] */, double (*shM)[PG_T / 64] /* [PG_MAXK + 1] */, double* sT /* [PT_TILE + PT_HALO] */, double* sEdge /* [2 * PT_HALO] */) {
     const int tid = threadIdx.x, w = tid >> 6;
     double m[PG_MAXK + 1];
 #pragma unroll
     for (int j = 0; j <= PG_MAXK; j++) m[j] = 0.0;
-    double dcarry = 0.0;
+    double dcarry = 0.0, pm = 0.0;                              // pm: the largest |prefix sum| this thread has formed (perm_err_bound)
     double nx[PT_PER];                                          // the next tile's values are requested while this tile is worked on
 #pragma unroll
     for (int r = 0; r < PT_PER; r++) { const int i = tid * PT_PER + r; nx[r] = i < n ? px[i] : 0.0; }
@@ -542,7 +550,7 @@ __device__ __forceinline__ void perm_stat_tail(const double* __restrict__ px, do
         for (int k = 0; k < PG_T / 64; k++) { const double t = shD[k]; if (k < w) wb += t; tot += t; }
         const double before = dcarry + wb + (inc - run);
 #pragma unroll
-        for (int r = 0; r < PT_PER; r++) sT[PT_HALO + tid * PT_PER + r] = before + v[r];
+        for (int r = 0; r < PT_PER; r++) { const double s = before + v[r]; sT[PT_HALO + tid * PT_PER + r] = s; pm = fmax(pm, fabs(s)); }
         dcarry += tot;
         __syncthreads();
         const int cnt = n - base < PT_TILE ? n - base : PT_TILE;          // prefix values of this tile: sT[PT_HALO, PT_HALO + cnt)
@@ -576,10 +584,15 @@ __device__ __forceinline__ void perm_stat_tail(const double* __restrict__ px, do
         for (int d = 32; d >= 1; d >>= 1) { const double oo = __hiloint2double(__shfl_xor(__double2hiint(vv), d), __shfl_xor(__double2loint(vv), d)); vv = oo > vv ? oo : vv; }
         if ((tid & 63) == 0) shM[j][tid >> 6] = vv;
     }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { const double oo = __hiloint2double(__shfl_xor(__double2hiint(pm), d), __shfl_xor(__double2loint(pm), d)); pm = oo > pm ? oo : pm; }
+    if ((tid & 63) == 0) shM[0][tid >> 6] = pm;                // (rows 0 and 1 hold no arc length)
     __syncthreads();
     if (tid == 0) {
         const double rn = (double)n;
         double hLo = 0.0, hHi = 0.0;
+        for (int k = 0; k < PG_T / 64; k++) pm = shM[0][k] > pm ? shM[0][k] : pm;
+        errBound = perm_err_bound(errBound, rn, pm);
         for (int j = al0; j <= hk && j <= PG_MAXK; j++) {
             double vv = 0.0; for (int k = 0; k < PG_T / 64; k++) vv = shM[j][k] > vv ? shM[j][k] : vv;
             const double rj = (double)j, c = rn / (rj * (rn - rj));
@@ -1146,7 +1159,7 @@ __device__ __noinline__ void rp_statistic(const PermReq& R, int w, int b, gptr<l
     int* sSrcOff = reinterpret_cast<int*>(sEdge + 2 * PT_HALO); uint32_t* sSrcBase = reinterpret_cast<uint32_t*>(sSrcOff + 4 * (RP_MAXK + 2));      // four tables each (tile & 3)
     const uint32_t* sInOff = RP_LDS(uint32_t, RPL_INOFF);
     const gptr<const PermReq> Rg = as_global(&R);                      // (the request table lies in global memory: read it through a typed pointer, once)
-    const double tss = Rg->tss, errBound = Rg->errBound; const uint32_t oOutOwn = Rg->rp.oOutOwn, oOutIn = Rg->rp.oOutIn; const gptr<double> pstat = as_global(Rg->pstat);
+    const double tss = Rg->tss; double errBound = Rg->errBound; const uint32_t oOutOwn = Rg->rp.oOutOwn, oOutIn = Rg->rp.oOutIn; const gptr<double> pstat = as_global(Rg->pstat);
     for (int t = tid; t <= nT; t += RP_T) sTab[t] = P.endsOwn[t];
     for (int d = 0; d < K - 1; d++) for (int t = tid; t <= nT; t += RP_T) sTab[(size_t)(d + 1) * (nT + 1) + t] = P.endsIn[(size_t)d * (nT + 1) + t];
     __syncthreads();
@@ -1186,7 +1199,7 @@ __device__ __noinline__ void rp_statistic(const PermReq& R, int w, int b, gptr<l
     double mx[RP_NJ];
 #pragma unroll
     for (int j = 0; j < RP_NJ; j++) mx[j] = 0.0;
-    double dcarry = 0.0;
+    double dcarry = 0.0, pm = 0.0;      // pm: the largest |prefix sum| this thread has formed (perm_err_bound)
     for (int base = 0, tau = 0; base < n; base += PT_TILE, tau++) {
         const int cnt = n - base < PT_TILE ? n - base : PT_TILE;
 #pragma unroll
@@ -1212,7 +1225,7 @@ __device__ __noinline__ void rp_statistic(const PermReq& R, int w, int b, gptr<l
         for (int kq = 0; kq < RP_T / 64; kq++) { const double tq = shD[kq]; if (kq < wv) wb += tq; tot += tq; }
         const double before = dcarry + wb + (inc - run);
 #pragma unroll
-        for (int r = 0; r < RP_PER; r++) sT[PT_HALO + tid * RP_PER + r] = before + v[r];
+        for (int r = 0; r < RP_PER; r++) { const double s = before + v[r]; sT[PT_HALO + tid * RP_PER + r] = s; pm = fmax(pm, fabs(s)); }
         dcarry += tot;
         __syncthreads();
         if (base == 0 && tid < PT_HALO) sEdge[tid] = sT[PT_HALO + tid];
@@ -1272,11 +1285,16 @@ __device__ __noinline__ void rp_statistic(const PermReq& R, int w, int b, gptr<l
         for (int d = 32; d >= 1; d >>= 1) { const double oo = __hiloint2double(__shfl_xor(__double2hiint(vv), d), __shfl_xor(__double2loint(vv), d)); vv = oo > vv ? oo : vv; }
         if ((tid & 63) == 0) shM[j][tid >> 6] = vv;
     }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { const double oo = __hiloint2double(__shfl_xor(__double2hiint(pm), d), __shfl_xor(__double2loint(pm), d)); pm = oo > pm ? oo : pm; }
+    if ((tid & 63) == 0) shD[tid >> 6] = pm;      // (the scan's wave totals were last read two barriers ago)
     lapc(7);
     const int anyBad = __syncthreads_or(bad);
     if (tid == 0) {
         const double rn = (double)n;
         double hLo = 0.0, hHi = 0.0;
+        for (int kq = 0; kq < RP_T / 64; kq++) pm = shD[kq] > pm ? shD[kq] : pm;
+        errBound = perm_err_bound(errBound, rn, pm);
         for (int j = RP_J0; j <= RP_J1; j++) {
             double vv = 0.0; for (int kq = 0; kq < RP_T / 64; kq++) vv = shM[j - RP_J0][kq] > vv ? shM[j - RP_J0][kq] : vv;
             const double rj = (double)j, c = rn / (rj * (rn - rj));
@@ -3430,8 +3448,8 @@ extern "C" int32_t canvas_cbs_seeds(int32_t nchr, int32_t* h_out, int32_t* h_var
 }
 // Diagnostic / test entry: ONE batch of nb permutations of the (centred) segment h_x[n] through the device permutation engine, exactly as FindChangePoints' hybrid test
 // runs it (XPerm + HTMaxP with hk = 25, al0 = 2; ChangePoint.cs:337-364,407-421; CBSTStatistic.cs:354-586) from a generator seeded with `seed`.  kernel: 0 = k_perm_stat,
-// 1 = k_perm_fy.  h_lohi[2 nb]: the interval of every permutation's statistic (the exact value lies inside); h_ms3: milliseconds of the generator's sequential part, of its
-// strided part and of the permutation + statistic kernel.  tests/test_cbs_gpu.py compares the intervals with the oracle's XPerm + HTMaxP; tools/perm_probe.py times the kernels.
+// 1 = k_perm_fy, 2 = k_perm_rp (n <= 524288).  h_lohi[2 nb]: the interval of every permutation's statistic (the exact value lies inside); h_ms3: milliseconds of the generator's sequential part, of its
+// strided part and of the permutation + statistic kernel.  tests/test_cbs_perm_kernels_gpu.py compares the intervals of all three with the oracle's XPerm + HTMaxP; tools/perm_probe.py times the kernels.
 extern "C" int32_t canvas_cbs_perm_probe(canvas_ctx* ctx, const double* h_x, int32_t n, uint32_t seed, int32_t nb, int32_t kernel, double tss, double* h_lohi, double* h_ms3) {
     if (!ctx) return CANVAS_ERR_INVALID;
     if (!h_x || !h_lohi || n < 1024 || nb < 1 || kernel < 0 || kernel > 2 || (long long)n * nb > (1ll << 30) || (kernel == 2 && n > PERM_RP_MAX_N)) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_perm_probe: bad arguments (n >= 1024, n * nb <= 2^30, kernel 0, 1 or 2 (n <= 524288))");

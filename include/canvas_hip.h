@@ -296,8 +296,10 @@ int32_t canvas_cbs_tailp_stats(canvas_ctx* ctx, int64_t* h_out2);
 int32_t canvas_cbs_tail_probe(canvas_ctx* ctx, const double* h_x, int32_t n, double tol, double* h_nu, int32_t* h_flag);
 /* Diagnostic / test entry: ONE batch of nb permutations of the centred segment h_x[n] (n >= 1024, n * nb <= 2^30) through the device permutation engine exactly as the hybrid test of
  * FindChangePoints runs it — XPerm (ChangePoint.cs:407-421) + HTMaxP with k = 25, minimum width 2 (CBSTStatistic.cs:354-586) — from MersenneTwister(seed).  kernel selects the
- * permutation kernel: 0 counting sort + pointer doubling, 1 block-wise simulation of the swaps in global memory, 2 range-partitioned simulation in LDS.  h_lohi[2 nb]: the interval
- * the engine returns for every permutation's statistic (the exact value lies inside; the stopping rule re-evaluates a permutation on the host only when the observed statistic does too).
+ * permutation kernel: 0 k_perm_stat (counting sort + pointer doubling), 1 k_perm_fy (block-wise simulation of the swaps in global memory), 2 k_perm_rp (range-partitioned simulation
+ * in LDS; n <= 524288, CANVAS_ERR_INVALID beyond).  h_lohi[2 nb]: the interval the engine returns for every permutation's statistic (the exact value lies inside; the stopping rule
+ * re-evaluates a permutation on the host only when the observed statistic does too; [-inf, inf]: the kernel gave the permutation up).  tests/test_cbs_perm_kernels_gpu.py compares
+ * the intervals of all three kernels with the oracle's XPerm + HTMaxP.
  * h_ms3 (optional): milliseconds of the generator's sequential part, its strided part, and the permutation + statistic kernel.  No reference counterpart: the engine's test bench. */
 int32_t canvas_cbs_perm_probe(canvas_ctx* ctx, const double* h_x, int32_t n, uint32_t seed, int32_t nb, int32_t kernel, double tss, double* h_lohi, double* h_ms3);
 /* Host-only (no context, no GPU): the sequential stopping boundary canvas_cbs uses for (nperm, alpha) — GetBoundary.ComputeBoundary (GetBoundary.cs:19-157) with eta = 0.05 as

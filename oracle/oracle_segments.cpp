@@ -281,6 +281,17 @@ void orc_xperm(const double* x, double* px, int n, uint32_t seed, int skip_perms
         for (int i = n - 1; i >= 0; i--) { double cc = r.next_double(); int j = (int)(cc * (i + 1)); j = (j > i) ? i : j; std::swap(px[i], px[j]); }
     }
 }
+// HTMaxP of the permutations 0 .. nb - 1 that ONE generator produces (every XPerm starts again from x: ChangePoint.cs:337-364,407-421) in a single pass of the
+// generator — orc_xperm restarts it for every skip, which makes a batch quadratic in nb
+void orc_htmaxp_batch(const double* x, int n, uint32_t seed, int nb, int k, double tss, int al0, double* out) {
+    MT19937 r(seed);
+    std::vector<double> px(n), sx(n);
+    for (int p = 0; p < nb; p++) {
+        for (int i = 0; i < n; i++) px[i] = x[i];
+        for (int i = n - 1; i >= 0; i--) { double cc = r.next_double(); int j = (int)(cc * (i + 1)); j = (j > i) ? i : j; std::swap(px[i], px[j]); }
+        out[p] = HTMaxP(k, tss, px.data(), n, sx.data(), al0);
+    }
+}
 // ChangePoints for one chromosome. stats: 7 int64 (CbsStats). Returns number of segments.
 // undoSD: the reference fixes it at 3 (CBSRunner.cs); the product's C ABI takes it, so the checker does too.
 int orc_cbs_chromosome_sd(const double* x, int n, int32_t seed, const uint32_t* sbdry, int nsbdry, double alpha, uint32_t nPerm, int undo,

@@ -372,6 +372,13 @@ def xperm(x, seed, skip=0):
     return px
 
 
+def htmaxp_batch(x, seed, nb, tss, k=25, al0=2):
+    """HTMaxP of the permutations 0 .. nb - 1 of x from MersenneTwister(seed), one pass of the generator (xperm(x, seed, b) + htmaxp for every b costs nb^2 / 2 permutations)"""
+    x = np.ascontiguousarray(x, np.float64); out = np.zeros(nb, np.float64)
+    lib.orc_htmaxp_batch(_p(x), len(x), C.c_uint32(seed & 0xFFFFFFFF), nb, k, C.c_double(tss), al0, _p(out))
+    return out
+
+
 def cbs_chromosome(x, seed, sbdry=None, alpha=0.01, n_perm=10000, undo=0, trimmed_sd=1.0):
     x = np.ascontiguousarray(x, np.float64)
     sb = cbs_boundary(n_perm, alpha) if sbdry is None else sbdry

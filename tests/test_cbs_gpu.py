@@ -143,6 +143,28 @@ def test_short_segments_run_on_the_device_with_the_references_own_statistic(monk
     assert [int(v) for v in stats[:5]] == [int(v) for v in stats2[:5]]
 
 
+def test_a_chromosome_of_more_than_524288_bins_takes_k_perm_fy(monkeypatch):
+    """A chromosome longer than k_perm_rp's largest segment (PERM_RP_MAX_N = 524 288 bins) is permuted by k_perm_fy, in production too; one call with one of 530 000, one of
+    20 000 and one of 500 bins makes the engine's one reservation serve k_perm_fy, k_perm_rp and k_perm_stat together.  The shift of 0.143 on the long chromosome puts its t
+    just past TailP's threshold, so the hybrid test permutes the whole 530 000-bin segment and the sequential rule leaves early; the oracle alone (nperm = 2000) reports 142
+    permutations of 530 000 bins (no change point), 457 of 20 000 (split at 7990) and 961 on the 500-bin chromosome and its pieces: 1560 in all.  The hook checks every
+    device interval against the statistic in the reference's order (contained, tight), _run the segments and the RNG consumption."""
+    cv = get_canvas()
+    x = np.random.RandomState(31).normal(100, 10, 530_000); x[265_000:] += 0.143
+    y = np.random.RandomState(32).normal(100, 10, 20_000); y[8000:] += 0.8
+    z = np.random.RandomState(33).normal(100, 10, 500); z[250:] += 3.0
+    parts = [np.round(v, 2) for v in (x, y, z)]
+    cov = np.concatenate(parts)
+    off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
+    monkeypatch.setenv("CANVAS_CBS_TEST_VERIFY", "1")
+    stats, exp = _run(cv, cov, off, nperm=2000)
+    d = cv.cbs_device_stats()
+    print("stats", [int(v) for v in stats], "device", d.tolist(), "segments", [e.tolist() for e in exp])
+    assert stats[2] > 0
+    assert stats[2] == 1560 and stats[3] >= 142 * 530_000          # permutations; permuted elements: the long segment was permuted whole
+    assert d[0] > 0 and d[4] >= d[0] and d[5] == 0, d
+
+
 def test_spiky_coverage_where_the_reference_search_leaves_arcs_out():
     """Coverage with isolated spikes puts a block's extremes next to each other; block_search then scans nothing of that block pair (CBSTStatistic.cs:233-326) and the reference's
     maximum can be below the maximum over every admissible arc.  The device arc search takes the latter and is only accepted when its maximiser is an arc the reference scans
