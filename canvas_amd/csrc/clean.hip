@@ -1074,6 +1074,82 @@ extern "C" int32_t canvas_clean_batch(canvas_ctx* ctx, int32_t nsamples, const i
     return rcAll;
 }
 
+// ---------------------------------------------------------------- canvas_select_probe: the order-statistics engine of select.hpp on its own (tests/test_select_gpu.py)
+__global__ void __launch_bounds__(256) k_keys_f32(const float* __restrict__ v, int64_t n, uint32_t* __restrict__ keys) {
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) keys[i] = key_of_float(v[i]);
+}
+// one workgroup per query, as k_run_mad and k_joint_median run it: wg_select2 over segment seg[q] for the rank pair ranks[2 q], ranks[2 q + 1]; both prefixes go out.
+// KEYED: the values are doubles and are keyed inside the key functor, as the production callers do; otherwise they are 64-bit keys already
+template <bool KEYED>
+__global__ void __launch_bounds__(1024) k_select_probe_wg(const void* __restrict__ values, const int64_t* __restrict__ segOff, const int32_t* __restrict__ seg,
+                                                          const unsigned long long* __restrict__ ranks, unsigned long long* __restrict__ out) {
+    __shared__ uint32_t sH[2][256];
+    __shared__ unsigned long long sPre[2], sK[2];
+    const int q = blockIdx.x;
+    const int64_t lo = segOff[seg[q]], hi = segOff[seg[q] + 1];
+    if (KEYED) { const double* v = (const double*)values; wg_select2([&](int64_t i) { return key_of_double(v[i]); }, lo, hi, ranks[2 * q], ranks[2 * q + 1], sH, sPre, sK); }
+    else { const unsigned long long* k = (const unsigned long long*)values; wg_select2([&](int64_t i) { return k[i]; }, lo, hi, ranks[2 * q], ranks[2 * q + 1], sH, sPre, sK); }
+    if (threadIdx.x < 2) out[2 * q + threadIdx.x] = sPre[threadIdx.x];      // (wg_select2 ends with a barrier)
+}
+extern "C" int32_t canvas_select_probe(canvas_ctx* ctx, int32_t variant, int32_t dtype, const void* d_values, int32_t nseg, const int64_t* h_seg_off, int32_t nq,
+                                       const int32_t* h_seg_lo, const int32_t* h_seg_hi, const int64_t* h_k, uint64_t* h_keys_out) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    if (variant < 0 || variant > 2 || dtype < 0 || dtype > 3 || nseg < 1 || nseg > (1 << 20) || !h_seg_off || nq < 0 || nq > (1 << 20) || (nq > 0 && (!h_seg_lo || !h_seg_hi || !h_k || !h_keys_out)))
+        CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_select_probe: bad arguments (variant 0..2, dtype 0..3, 1..2^20 segments, at most 2^20 queries)");
+    if (variant == 2 && dtype != 1 && dtype != 3) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_select_probe: wg_select2 works on 64-bit keys (dtype 1 or 3)");
+    if (h_seg_off[0] < 0) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_select_probe: negative segment offset");
+    for (int s = 0; s < nseg; s++) if (h_seg_off[s + 1] < h_seg_off[s]) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_select_probe: segment offsets decrease");
+    const int64_t n = h_seg_off[nseg];
+    if (n > (1ll << 30) || (n > 0 && !d_values)) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_select_probe: at most 2^30 keys");
+    const int per = variant == 2 ? 2 : 1;            // ranks per query
+    for (int q = 0; q < nq; q++) {
+        if (h_seg_lo[q] < 0 || h_seg_hi[q] >= nseg || h_seg_lo[q] > h_seg_hi[q] || (variant == 2 && h_seg_lo[q] != h_seg_hi[q])) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_select_probe: bad segment range of a query");
+        const int64_t cnt = h_seg_off[h_seg_hi[q] + 1] - h_seg_off[h_seg_lo[q]];
+        for (int j = 0; j < per; j++) if (h_k[(size_t)per * q + j] < 0 || h_k[(size_t)per * q + j] >= cnt) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_select_probe: rank outside the query's segments");
+    }
+    if (nq == 0) return CANVAS_OK;
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (variant == 2) {
+        WsSizer sz; sz.take<int64_t>(nseg + 1); sz.take<int32_t>(nq); sz.take<unsigned long long>(2 * (size_t)nq); sz.take<unsigned long long>(2 * (size_t)nq);
+        int32_t rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
+        WsCarver ws(ctx->ws);
+        int64_t* dOff = ws.take<int64_t>(nseg + 1); int32_t* dSeg = ws.take<int32_t>(nq); unsigned long long* dRank = ws.take<unsigned long long>(2 * (size_t)nq); unsigned long long* dOut = ws.take<unsigned long long>(2 * (size_t)nq);
+        rc = canvas_h2d_small(ctx, dOff, h_seg_off, (size_t)(nseg + 1) * 8); if (rc) return rc;
+        rc = canvas_h2d_small(ctx, dSeg, h_seg_lo, (size_t)nq * 4); if (rc) return rc;
+        rc = canvas_h2d_small(ctx, dRank, h_k, (size_t)nq * 16); if (rc) return rc;
+        if (dtype == 1) hipLaunchKernelGGL((k_select_probe_wg<true>), dim3(nq), dim3(1024), 0, ctx->stream, d_values, dOff, dSeg, dRank, dOut);
+        else hipLaunchKernelGGL((k_select_probe_wg<false>), dim3(nq), dim3(1024), 0, ctx->stream, d_values, dOff, dSeg, dRank, dOut);
+        CANVAS_HIP_TRY(ctx, hipGetLastError());
+        CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        CANVAS_HIP_TRY(ctx, hipMemcpy(h_keys_out, dOut, (size_t)nq * 16, hipMemcpyDeviceToHost));
+        return CANVAS_OK;
+    }
+    const void* dKeys = d_values;
+    if (dtype < 2 && n > 0) {
+        int32_t rc = canvas_ws_reserve(ctx, (size_t)n * 8 + 256); if (rc) return rc;
+        if (dtype == 0) hipLaunchKernelGGL(k_keys_f32, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, (const float*)d_values, n, (uint32_t*)ctx->ws);
+        else hipLaunchKernelGGL(k_keys_f64, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, (const double*)d_values, n, (unsigned long long*)ctx->ws);
+        dKeys = ctx->ws;
+    }
+    const std::vector<int64_t> segOff(h_seg_off, h_seg_off + nseg + 1);
+    std::vector<SelQuery> qs(nq);
+    for (int q = 0; q < nq; q++) qs[q] = SelQuery{h_seg_lo[q], h_seg_hi[q], h_k[q]};
+    std::vector<unsigned long long> res;
+    const unsigned long long* dRes = nullptr;
+    const bool wide = dtype == 1 || dtype == 3;
+    const int32_t rc = wide ? radix_select<unsigned long long>(ctx, (const unsigned long long*)dKeys, nseg, segOff, qs, res, variant == 1 ? &dRes : nullptr)
+                            : radix_select<uint32_t>(ctx, (const uint32_t*)dKeys, nseg, segOff, qs, res, variant == 1 ? &dRes : nullptr);
+    if (rc) return rc;
+    if (variant == 1) {        // the d_results contract: the results are on the device and the stream has not been waited for
+        if (!dRes) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_select_probe: no keys in any segment");
+        CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        CANVAS_HIP_TRY(ctx, hipGetLastError());
+        CANVAS_HIP_TRY(ctx, hipMemcpy(h_keys_out, dRes, (size_t)nq * 8, hipMemcpyDeviceToHost));
+    } else for (int q = 0; q < nq; q++) h_keys_out[q] = res[q];
+    return CANVAS_OK;
+}
+
 extern "C" int32_t canvas_clean(canvas_ctx* ctx, int64_t n, int32_t* d_chr, int32_t* d_start, int32_t* d_stop, float* d_count,
                                 int32_t* d_gc, int32_t nchr, const uint8_t* h_chr_is_autosome, uint32_t flags, int32_t min_bins_per_gc,
                                 double* h_local_sd_out, int64_t* h_n_out, int32_t* h_info) {

@@ -222,6 +222,8 @@ __device__ __forceinline__ double double_of_key(unsigned long long k) {
 struct SelQuery { int32_t segLo, segHi; int64_t k; };
 
 // Runs all queries; results (keys as u64) are returned in `out`.  segOff has nseg+1 entries (host).  One sync at the end.
+// Precondition: every query has 0 <= segLo <= segHi < nseg and 0 <= k < number of keys in segments segLo..segHi.  A rank outside that range is found in no digit's
+// count, so the pick leaves the query's prefix as it is: the result is whatever an earlier call left in that slot (canvas_select_probe checks the ranks on the host).
 template <typename K>
 static int32_t radix_select(canvas_ctx* ctx, const K* d_keys, int nseg, const std::vector<int64_t>& segOff,
                             const std::vector<SelQuery>& queries, std::vector<unsigned long long>& out, const unsigned long long** d_results = nullptr) {

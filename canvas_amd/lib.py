@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     "canvas_mask_from_fasta", "canvas_mask_exclude_intervals", "canvas_screen_hits",
     "canvas_bin_rates", "canvas_bin_size_from_rates", "canvas_bin_count_upper_bound", "canvas_bin_genome", "canvas_bin_sample", "canvas_bin_sample_gcweighted", "canvas_bin_predefined", "canvas_bin_predefined_gcweighted",
     "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_normalize_best_normal", "canvas_normalize_pca_reference", "canvas_sample_pipeline",
-    "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads",
+    "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads", "canvas_select_probe",
     "canvas_memcpy_h2d_async", "canvas_snv_count", "canvas_flag_unique_kmers", "canvas_fasta_case_from_mask",
 ]
 
@@ -451,6 +451,27 @@ class Canvas:
         lohi = np.zeros((nb, 2), np.float64); ms = np.zeros(3, np.float64)
         self._check(self.lib.canvas_cbs_perm_probe(self.ctx, _np_ptr(x), C.c_int32(len(x)), C.c_uint32(seed & 0xFFFFFFFF), C.c_int32(nb), C.c_int32(kernel), C.c_double(tss), _np_ptr(lohi), _np_ptr(ms)))
         return lohi, ms
+
+    def select_probe(self, variant, dtype, values, seg_off, seg_lo, seg_hi, k):
+        """the order-statistics engine of select.hpp on its own (canvas_select_probe).  values: numpy array of float32 / float64 / uint32 / uint64 for dtype 0 / 1 / 2 / 3;
+        variant 0 / 1: radix_select with host / device results, k[nq] -> keys u64[nq]; variant 2: wg_select2, k[nq, 2] -> keys u64[nq, 2]"""
+        want = (np.float32, np.float64, np.uint32, np.uint64)[dtype]
+        values = np.ascontiguousarray(values)
+        if values.dtype != want:
+            raise CanvasError(f"select_probe: dtype {dtype} takes {np.dtype(want).name} values, not {values.dtype.name}")
+        off = np.ascontiguousarray(seg_off, np.int64); lo = np.ascontiguousarray(seg_lo, np.int32); hi = np.ascontiguousarray(seg_hi, np.int32)
+        kk = np.ascontiguousarray(k, np.int64)
+        nq = len(lo)
+        if len(hi) != nq or kk.shape != ((nq, 2) if variant == 2 else (nq,)):
+            raise CanvasError("select_probe: one (seg_lo, seg_hi, k) per query; k is a pair per query with variant 2")
+        if len(off) < 2 or off.max() > len(values):
+            raise CanvasError("select_probe: the segment offsets reach past the values")
+        bits = values.view(np.int32 if values.itemsize == 4 else np.int64)             # (torch has no unsigned 32 / 64-bit tensors to speak of: the bits travel as signed)
+        dev = self.torch.from_numpy(bits if len(bits) else np.zeros(1, bits.dtype)).to(self.device)
+        out = np.zeros(kk.shape, np.uint64)
+        self._check(self.lib.canvas_select_probe(self.ctx, C.c_int32(variant), C.c_int32(dtype), C.c_void_p(dev.data_ptr()), C.c_int32(len(off) - 1), _np_ptr(off), C.c_int32(nq),
+                                                 _np_ptr(lo), _np_ptr(hi), _np_ptr(kk), _np_ptr(out)))
+        return out
 
     def stale_reads(self):
         """process-wide [pinned results looked at, looks that came before the result had arrived (polled until it did)] (canvas_stale_reads)"""

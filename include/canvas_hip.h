@@ -302,6 +302,16 @@ int32_t canvas_cbs_tail_probe(canvas_ctx* ctx, const double* h_x, int32_t n, dou
  * the intervals of all three kernels with the oracle's XPerm + HTMaxP.
  * h_ms3 (optional): milliseconds of the generator's sequential part, its strided part, and the permutation + statistic kernel.  No reference counterpart: the engine's test bench. */
 int32_t canvas_cbs_perm_probe(canvas_ctx* ctx, const double* h_x, int32_t n, uint32_t seed, int32_t nb, int32_t kernel, double tss, double* h_lohi, double* h_ms3);
+/* Diagnostic / test entry: the exact order-statistics engine behind every median and quartile of the library (csrc/select.hpp) on caller-supplied data.  d_values (device) holds
+ * h_seg_off[nseg] elements partitioned in nseg segments by h_seg_off[nseg + 1] (host, non-decreasing).  dtype: 0 float32 values keyed on the device (the CanvasClean / PerSampleHMM
+ * path, 32-bit keys), 1 float64 values keyed on the device (CanvasNormalize / LOESS, 64-bit keys), 2 / 3 raw uint32 / uint64 keys.  The key of a value is its order-preserving
+ * unsigned image: all bits flipped when the sign bit is set, the sign bit set otherwise.  variant: 0 radix_select, results through the host; 1 radix_select with its results left
+ * on the device (the probe synchronises and copies them, as that contract asks of the caller); 2 wg_select2, one workgroup of 1024 threads per query (dtype 1 or 3 only).
+ * Query q asks for the h_k[q]-th smallest key (0-based) of the union of segments h_seg_lo[q]..h_seg_hi[q] -> h_keys_out[q]; with variant 2 h_seg_lo[q] == h_seg_hi[q], h_k holds a
+ * PAIR of ranks per query and h_keys_out two keys per query.  CANVAS_ERR_INVALID for decreasing offsets, a segment range that is reversed or outside 0..nseg-1, a rank outside
+ * [0, keys in the query's segments), and (variants 0, 1) more than 16 queries on one segment: radix_select's own refusal.  tests/test_select_gpu.py compares every key with a sort. */
+int32_t canvas_select_probe(canvas_ctx* ctx, int32_t variant, int32_t dtype, const void* d_values, int32_t nseg, const int64_t* h_seg_off, int32_t nq,
+                            const int32_t* h_seg_lo, const int32_t* h_seg_hi, const int64_t* h_k, uint64_t* h_keys_out);
 /* Host-only (no context, no GPU): the sequential stopping boundary canvas_cbs uses for (nperm, alpha) — GetBoundary.ComputeBoundary (GetBoundary.cs:19-157) with eta = 0.05 as
  * CBSRunner passes it: maxOnes (maxOnes + 1) / 2 entries with maxOnes = floor(nperm alpha) + 1.  Returns the number of entries (or a negative error code).  The library
  * evaluates the table's scans on its host thread pool with the scans' own evaluations and comparisons; exposed so that the table can be checked without a device. */
