@@ -10,7 +10,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-result"]
-PRODUCT_SRC = ["ctx.hip", "prep.hip", "bin.hip", "clean.hip", "hmm.hip", "cbs.hip", "wavelets.hip", "evenness.hip", "normalize.hip", "pipeline.hip", "sharded.hip", "comm.hip", "snv.hip", "kmer.hip"]
+PRODUCT_SRC = ["ctx.hip", "prep.hip", "bin.hip", "clean.hip", "hmm.hip", "cbs.hip", "wavelets.hip", "evenness.hip", "normalize.hip", "pipeline.hip", "sharded.hip", "comm.hip", "snv.hip", "kmer.hip", "smooth.hip"]
 
 
 def _hipcc():
@@ -191,6 +191,7 @@ def build(force=False, verbose=False):
         assert embedded_hash(out) == source_hash(srcs), "libcanvas_hip.so does not carry the hash of its sources"
         _build_one(hipcc, s2, out2, [], force, verbose)
         build_tools(force=force, verbose=verbose)
+        build_more_tools(force=force, verbose=verbose)
     return out, out2
 
 
@@ -202,15 +203,13 @@ def _tool_hash(srcs):
     return h.hexdigest()[:32]
 
 
-def build_tools(force=False, verbose=False):
-    """drop-in tool drivers (plain C++ over the C ABI + zlib): canvas_amd/bin/CanvasBin, CanvasClean, CanvasPartition, CanvasNormalize, CanvasSNV, FlagUniqueKmers"""
+def _build_tool_set(tools, force, verbose):
     tdir = os.path.join(HERE, "tools")
     bdir = os.path.join(HERE, "bin")
     os.makedirs(bdir, exist_ok=True)
     tl = _torch_lib_dir()
     outs = []
-    for name, src in (("CanvasBin", "canvas_bin_main.cpp"), ("CanvasClean", "canvas_clean_main.cpp"), ("CanvasPartition", "canvas_partition_main.cpp"),
-                      ("CanvasNormalize", "canvas_normalize_main.cpp"), ("CanvasSNV", "canvas_snv_main.cpp"), ("FlagUniqueKmers", "flag_unique_kmers_main.cpp")):
+    for name, src in tools:
         out = os.path.join(bdir, name)
         srcs = [os.path.join(tdir, src)] + sorted(glob.glob(os.path.join(tdir, "*.hpp")))      # every header: a tool is stale when any of them changes
         th = _tool_hash(srcs)
@@ -226,6 +225,17 @@ def build_tools(force=False, verbose=False):
             os.replace(tmp_out, out)
         outs.append(out)
     return outs
+
+
+def build_tools(force=False, verbose=False):
+    """drop-in tool drivers (plain C++ over the C ABI + zlib): canvas_amd/bin/CanvasBin, CanvasClean, CanvasPartition, CanvasNormalize, CanvasSNV, FlagUniqueKmers"""
+    return _build_tool_set((("CanvasBin", "canvas_bin_main.cpp"), ("CanvasClean", "canvas_clean_main.cpp"), ("CanvasPartition", "canvas_partition_main.cpp"),
+                            ("CanvasNormalize", "canvas_normalize_main.cpp"), ("CanvasSNV", "canvas_snv_main.cpp"), ("FlagUniqueKmers", "flag_unique_kmers_main.cpp")), force, verbose)
+
+
+def build_more_tools(force=False, verbose=False):
+    """the drivers added after those six, by the same staleness rule (the hash covers every *.hpp of tools/ and the headers of include/): canvas_amd/bin/CanvasSmooth"""
+    return _build_tool_set((("CanvasSmooth", "canvas_smooth_main.cpp"),), force, verbose)
 
 
 if __name__ == "__main__":

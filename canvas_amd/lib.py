@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_normalize_best_normal", "canvas_normalize_pca_reference", "canvas_sample_pipeline",
     "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads", "canvas_select_probe",
     "canvas_memcpy_h2d_async", "canvas_snv_count", "canvas_flag_unique_kmers", "canvas_fasta_case_from_mask",
+    "canvas_smooth", "canvas_smooth_lengths", "canvas_smooth_plan",
 ]
 
 
@@ -133,6 +134,27 @@ def pack_hits2_host(hits, length, lo=None, hdr=None, extras=None, threads=0):
 def snv_allele_codes(alleles):
     """the site codes canvas_snv_count compares a read's 4-bit base code with: index of the allele's character in "=ACMGRSVTWYHKDBN", 255 for anything else"""
     return np.array([("=ACMGRSVTWYHKDBN".find(a) if len(a) == 1 else -1) & 0xFF for a in alleles], np.uint8)
+
+
+def smooth_lengths(n, max_half_window):
+    """canvas_smooth_lengths (plain host code, no GPU): the number of bins CanvasSmooth -w max_half_window leaves of chromosomes of n bins each (int64 array)"""
+    lib = load_library()
+    hn = np.ascontiguousarray(n, np.int64).reshape(-1)
+    out = np.zeros(len(hn), np.int64)
+    rc = lib.canvas_smooth_lengths(C.c_int32(len(hn)), _np_ptr(hn), C.c_int32(int(max_half_window)), _np_ptr(out))
+    if rc:
+        raise CanvasError(f"canvas_smooth_lengths: error {rc}")
+    return out
+
+
+def smooth_plan(max_half_window):
+    """canvas_smooth_plan (plain host code, no GPU): dict(fused, tile, halo, launches) — how Canvas.smooth runs for this half window"""
+    lib = load_library()
+    out = np.zeros(4, np.int64)
+    rc = lib.canvas_smooth_plan(C.c_int32(int(max_half_window)), _np_ptr(out))
+    if rc:
+        raise CanvasError(f"canvas_smooth_plan: error {rc}")
+    return dict(fused=bool(out[0]), tile=int(out[1]), halo=int(out[2]), launches=int(out[3]))
 
 
 class Canvas:
@@ -559,6 +581,23 @@ class Canvas:
         self._check(self.lib.canvas_fasta_case_from_mask(self.ctx, C.c_void_p(bases.data_ptr()), C.c_int64(int(length)), C.c_void_p(mask.data_ptr())))
         self.synchronize()
         return bases
+
+    def smooth(self, counts, chr_offset, max_half_window, out=None):
+        """RepeatedMedianSmoother.Smooth (CanvasSmooth.cs:46-77) of every chromosome: counts = float32 device tensor, chr_offset[nchr + 1] = where each chromosome's
+        bins start.  Returns (out, out_n): out[chr_offset[c] + k] for k < out_n[c] are the smoothed counts, the rest of `out` (created unless given) is not written;
+        out_n[c] < the chromosome's length where the reference drops bins (fewer than 2h + 1 bins at some pass)."""
+        torch = self.torch
+        off = np.ascontiguousarray(chr_offset, np.int64)
+        assert off.ndim == 1 and len(off) >= 1
+        assert counts.dtype == torch.float32 and counts.is_contiguous() and counts.dim() == 1 and (counts.numel() == 0 or counts.device == self.device), "smooth: counts must be a dense float32 tensor on the context's device"
+        assert int(off[-1]) <= counts.numel(), "smooth: the offsets reach past the counts"
+        if out is None:
+            out = torch.empty_like(counts)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 1 and out.numel() >= int(off[-1]) and (out.numel() == 0 or out.device == self.device)
+        out_n = np.zeros(max(len(off) - 1, 1), np.int64)
+        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        self._check(self.lib.canvas_smooth(self.ctx, C.c_int32(len(off) - 1), _np_ptr(off), C.c_void_p(counts.data_ptr()), C.c_int32(int(max_half_window)), C.c_void_p(out.data_ptr()), _np_ptr(out_n)))
+        return out, out_n[:len(off) - 1]
 
     def segment_ids(self, chr_offset, state, start, stop, max_inter_bin_dist=1000000, excluded=None, out=None, ploidy=None):
         """DeriveSegments + PostProcessSegments; excluded = per-chromosome list of (starts, stops) of the -b BED file; ploidy = per-chromosome list

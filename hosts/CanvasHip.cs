@@ -130,6 +130,11 @@ namespace CanvasHipInterop
         // Tools/FlagUniqueKmers (KmerChecker): unique-35-mer masks of all contigs at once (stats = long[8] or null), and the letter case of kmer.fa from a mask
         [DllImport(Lib)] public static extern int canvas_flag_unique_kmers(IntPtr ctx, int nchr, IntPtr[] dBases, long[] len, IntPtr[] dMask, long maxTableBytes, long[] stats);
         [DllImport(Lib)] public static extern int canvas_fasta_case_from_mask(IntPtr ctx, IntPtr dBases, long len, IntPtr dMask);
+        // CanvasSmooth: Utilities.MedianFilter with half window 1 .. maxHalfWindow over every chromosome (chrOffset = nchr + 1 bin offsets); outN[c] bins are left of chromosome c
+        // and nothing beyond them is written to dOut.  canvas_smooth_lengths / canvas_smooth_plan are plain host code (no context): the lengths alone, and {fused, tile, halo, launches}
+        [DllImport(Lib)] public static extern int canvas_smooth(IntPtr ctx, int nchr, long[] chrOffset, IntPtr dCount, int maxHalfWindow, IntPtr dOut, long[] outN);
+        [DllImport(Lib)] public static extern int canvas_smooth_lengths(int nchr, long[] n, int maxHalfWindow, long[] outN);
+        [DllImport(Lib)] public static extern int canvas_smooth_plan(int maxHalfWindow, long[] out4);
 
         /// <summary>Turns a non-zero status into the module's own failure convention (message on stderr, exit code 1).</summary>
         public static void Check(IntPtr ctx, int status, string what)

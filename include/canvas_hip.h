@@ -522,6 +522,21 @@ int32_t canvas_flag_unique_kmers(canvas_ctx* ctx, int32_t nchr, const uint8_t* c
 /* inverse of canvas_mask_from_fasta: ASCII letters of d_bases become upper case where the mask bit is 1 and lower case where it is 0, in place */
 int32_t canvas_fasta_case_from_mask(canvas_ctx* ctx, uint8_t* d_bases, int64_t len, const uint64_t* d_mask);
 
+/* ---- CanvasSmooth: repeated median filter of the bin counts (CanvasSmooth/CanvasSmooth.cs:46-77, CanvasCommon/Utilities.cs:767-791) -------------------- */
+/* CanvasSmooth (CanvasSmooth.cs:46-77, Utilities.MedianFilter): h = 1..max_half_window over each chromosome's counts.
+ * d_out[h_chr_offset[c] + k], k < h_out_n[c], = the smoothed counts; the rest of d_out is left untouched. d_out must not overlap d_count.
+ * A chromosome shorter than 2h + 1 at some pass comes out shorter (the reference's Enumerable.Zip drops the bins beyond the filter's output): h_out_n[c] is the
+ * length that is left, possibly 0.  max_half_window = 0 copies the counts.  Counts must be finite (CANVAS_ERR_INVALID names the first index that is not); -0.0
+ * compares equal to 0.0 and either may come out.  CANVAS_ERR_INVALID as well for a negative max_half_window, offsets that decrease, a chromosome of 2^31 bins or
+ * more, and a d_out that overlaps d_count.  The call waits for its result. */
+int32_t canvas_smooth(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_offset /* nchr+1 */, const float* d_count,
+                      int32_t max_half_window, float* d_out, int64_t* h_out_n /* nchr */);
+/* host only, no context: the output length of every chromosome: per pass h, n stays when n >= 2h + 1 and becomes max(0, n-h) + max(0, n-h-1) otherwise */
+int32_t canvas_smooth_lengths(int32_t nchr, const int64_t* h_n, int32_t max_half_window, int64_t* h_out_n);
+/* host only: how canvas_smooth will run for this W. h_out4 = { fused (0/1), tile payload in bins, halo in bins per side, launches }
+ * (per-pass path: launches = max_half_window, an upper bound: the passes end once every chromosome is empty; 0 = a copy) */
+int32_t canvas_smooth_plan(int32_t max_half_window, int64_t* h_out4);
+
 /* ---- profiling hooks (hipEvent pairs recorded on the context's stream around the named kernels) --------------------- */
 /* on: 0 off; 1 every named scope; 2 only the scopes around the dominant (HBM-bound) kernel of CanvasBin — "bin_summary", "bin_summary_packed", "bin_pass",
    "bin_tile_stats" — so that a timed pass carries two event records instead of a dozen (each scope costs two barrier packets on the stream) */
