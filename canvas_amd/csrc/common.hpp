@@ -105,6 +105,13 @@ struct ProfScope {
     }
 };
 
+// a named counter without a device time: one more "launch" of the slot, nothing on the stream (read with canvas_profile_get; every scope on, like any non-dominant scope)
+static inline void cvx_prof_count(canvas_ctx* c, const char* name) {
+    if (c->prof != 1) return;
+    for (auto& sl : c->slots) if (sl.name == name) { sl.launches++; return; }
+    c->slots.push_back({}); c->slots.back().name = name; c->slots.back().launches = 1;
+}
+
 #define CANVAS_HIP_TRY(ctx, expr)                                                                   \
     do {                                                                                            \
         hipError_t e_ = (expr);                                                                     \

@@ -421,19 +421,6 @@ __device__ __forceinline__ int wave_max_i32(int v) {
 }
 
 // block / chunk lists: entry i of a list with `per` steps per entry, from the per-chromosome first indices (binary search)
-template <typename T>
-__global__ void __launch_bounds__(256) k_make_blocks(const int32_t* __restrict__ first, int nchr, int n, int per, T* __restrict__ out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int lo = 0, hi = nchr - 1;
-    while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (first[mid] <= i) lo = mid; else hi = mid - 1; }
-    while (lo < nchr - 1 && first[lo + 1] <= i) lo++;        // chromosomes without blocks share an index
-    T b; b.chrom = lo; b.t0 = (i - first[lo]) * per;
-    out[i] = b;
-}
-
-// The data-independent tables of the stage in ONE launch: the three block / chunk lists (k_make_blocks), the per-chromosome result slots, and — PerSampleHMM — the
-// table index of every bin (k_hmm_index: it needs nothing but the threshold).  Round 3 issued them as seven launches / fills between two host round trips.
 template <typename T> __device__ __forceinline__ void make_block_entry(const int32_t* __restrict__ first, int nchr, int i, int per, T* __restrict__ out) {
     int lo = 0, hi = nchr - 1;
     while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (first[mid] <= i) lo = mid; else hi = mid - 1; }
@@ -441,6 +428,15 @@ template <typename T> __device__ __forceinline__ void make_block_entry(const int
     T b; b.chrom = lo; b.t0 = (i - first[lo]) * per;
     out[i] = b;
 }
+// one list on its own (canvas_hmm_backbone_probe: the chunk list without the rest of the stage)
+template <typename T>
+__global__ void __launch_bounds__(256) k_make_blocks(const int32_t* __restrict__ first, int nchr, int n, int per, T* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) make_block_entry(first, nchr, i, per, out);
+}
+
+// The data-independent tables of the stage in ONE launch: the three block / chunk lists (make_block_entry), the per-chromosome result slots, and — PerSampleHMM — the
+// table index of every bin (k_hmm_index: it needs nothing but the threshold).  Round 3 issued them as seven launches / fills between two host round trips.
 // the per-chromosome descriptors of the stage, BY VALUE (<= HMM_BYVAL chromosomes: the argument block is copied at launch, no H2D copy in front of the stage)
 #define HMM_BYVAL 64
 struct HmmDescPack { HmmChrom chroms[HMM_BYVAL]; int64_t off[HMM_BYVAL + 1]; int32_t first[HMM_BYVAL + 1], firstChunk[HMM_BYVAL + 1], firstS[HMM_BYVAL + 1], firstGroup[HMM_BYVAL + 1]; };
@@ -624,7 +620,10 @@ __global__ void __launch_bounds__(64) k_vit_backbone(const HmmChrom* __restrict_
 // a1 if it is odd", and such functions compose associatively: a block scan gives every k exactly.  The step that leaves the
 // binade is done with one real FP64 add and the scan restarts behind it with the new u.  One workgroup per chromosome, 8192 steps
 // per iteration.  Anything outside the assumptions (NaN, infinities, positive increments) flags the chromosome for the
-// sequential k_viterbi; k_vit_verify re-checks D bit for bit in any case.
+// sequential k_viterbi.  k_vit_verify does NOT re-check these sums: a block starts from carry[ts] and checks delta_t(s_t) == D_t against
+// the D it builds from that carry itself, and nothing compares the D a block ends on with the carry the next one starts from.  That
+// carry[] holds the sequential sum bit for bit is guaranteed by the construction above and guarded by tests/test_hmm_backbone_gpu.py
+// (canvas_hmm_backbone_probe), for all three forms of the backbone.
 #define BS_T 1024
 #define BS_I 8
 struct ParFn { unsigned long long a0, a1; };     // amount added to k when the incoming k is even / odd
@@ -661,7 +660,8 @@ __global__ void __launch_bounds__(BS_T) k_vit_backbone_scan(const HmmChrom* __re
                 const double v = Vc[p];
                 const unsigned long long vb = (unsigned long long)__double_as_longlong(v);
                 if (((vb >> 52) & 0x7ffull) == 0x7ffull || (!(vb >> 63) && (vb << 1) != 0ull)) { sBad = 1; fail[blockIdx.x] = 1; }
-                else { const double acc = -M + v; if (((p + 1) & 63) == 0 && p + 1 < C.T) carry[p + 1] = acc; sM = -acc; sP = p + 1; }
+                // (0.0 - M, not -M: the sequential sum starts at +0.0 and stays there over increments of -0.0, where -M + v would give -0.0)
+                else { const double acc = (0.0 - M) + v; if (((p + 1) & 63) == 0 && p + 1 < C.T) carry[p + 1] = acc; sM = -acc; sP = p + 1; }
             }
             __syncthreads();
             continue;
@@ -976,7 +976,7 @@ __global__ void __launch_bounds__(256) k_bb_emit(const BbChunk* __restrict__ chu
     if (t + 1 >= C.T) return;
     const unsigned long long MANT = (1ull << 52) - 1ull;
     const uint32_t rk = at64Rank[i];
-    const uint32_t rank = rk & 0x7fu;
+    const uint32_t rank = (rk & 0x7fu) > (uint32_t)BB_MAXC ? (uint32_t)BB_MAXC : (rk & 0x7fu);      // more crossings than a chunk keeps: the chromosome is given up (fail word), stay inside post[]
     unsigned long long bits = rank == 0 ? chunkBits[c] : post[(size_t)c * BB_MAXC + (rank - 1)].bits;
     if (!(rk & 0x80u)) {
         const ParFn f = at64Fn[i];
@@ -1138,8 +1138,9 @@ __global__ void __launch_bounds__(64) k_vit_verify(const VitBlock* __restrict__ 
 }
 
 // test hook (CANVAS_HMM_TEST_CORRUPT): flips one guessed back-pointer so that tests can prove k_vit_verify catches a wrong guess
-__global__ void k_vit_corrupt(uint16_t* __restrict__ psi, int64_t at) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { uint32_t v = psi[at], p = (v >> 6) & 7u; psi[at] = (uint16_t)((v & ~(7u << 6)) | (((p + 1u) % 5u) << 6)); }
+// (the pointer of state j at one step becomes the next state, modulo 5: always another value than the guess)
+__global__ void k_vit_corrupt(uint16_t* __restrict__ psi, int64_t at, int j) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) { const uint32_t sh = 3u * (uint32_t)j; uint32_t v = psi[at], p = (v >> sh) & 7u; psi[at] = (uint16_t)((v & ~(7u << sh)) | (((p + 1u) % 5u) << sh)); }
 }
 
 // ---- backtracking as function composition over the VB-step blocks: state[t-1] = psi_t[state[t]]
@@ -1515,6 +1516,101 @@ static void quartile_val(int64_t n, const float* v, float& q1, float& q2, float&
 
 static inline unsigned nblk2(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
+// The per-chromosome lists of the stage (host side): chromosomes of at most ten bins are skipped by the reference and own no block, chunk or group.
+struct HmmLists {
+    std::vector<HmmChrom> chroms;
+    std::vector<int32_t> firstBlock, firstGroup, firstS, firstChunk;      // nchr + 1 entries each
+    int nblocks = 0, ngroups = 0, nblocksS = 0, nchunks = 0;
+};
+static HmmLists hmm_lists(int32_t nchr, const int64_t* h_chr_offset) {
+    HmmLists L;
+    // VB-step blocks (speculation, verification and backtrack share them)
+    L.chroms.resize(nchr); L.firstBlock.resize(nchr + 1);
+    for (int c = 0; c < nchr; c++) {
+        L.chroms[c].begin = h_chr_offset[c]; L.chroms[c].T = h_chr_offset[c + 1] - h_chr_offset[c];
+        L.firstBlock[c] = L.nblocks;
+        if (L.chroms[c].T > 10) L.nblocks += (int)((L.chroms[c].T + VB - 1) / VB);
+    }
+    L.firstBlock[nchr] = L.nblocks;
+    L.firstGroup.resize(nchr + 1);                  // groups of 64 blocks for the backtrack (counted from the end of each chromosome)
+    for (int c = 0; c < nchr; c++) { L.firstGroup[c] = L.ngroups; L.ngroups += (L.firstBlock[c + 1] - L.firstBlock[c] + 63) / 64; }
+    L.firstGroup[nchr] = L.ngroups;
+    L.firstS.resize(nchr + 1);                      // blocks of the speculative pass (VBS steps)
+    for (int c = 0; c < nchr; c++) { L.firstS[c] = L.nblocksS; if (L.chroms[c].T > 10) L.nblocksS += (int)((L.chroms[c].T + VBS - 1) / VBS); }
+    L.firstS[nchr] = L.nblocksS;
+    L.firstChunk.resize(nchr + 1);                  // BB_CHUNK-step chunks of the exact backbone
+    for (int c = 0; c < nchr; c++) {
+        L.firstChunk[c] = L.nchunks;
+        if (L.chroms[c].T > 10) L.nchunks += (int)((L.chroms[c].T + BB_CHUNK - 1) / BB_CHUNK);
+    }
+    L.firstChunk[nchr] = L.nchunks;
+    return L;
+}
+
+// B1: the exact backbone in one of its three forms, as hmm_pipeline and canvas_hmm_backbone_probe enqueue it.  V: the increments; carry[t] = D_{t-1} at every multiple of 64
+// of every chromosome of more than ten bins.  fail[c] is set (never cleared) when the scan or the pieces give chromosome c up; the chain has no such word.
+enum { BB_MODE_CHAIN = 0, BB_MODE_SCAN = 1, BB_MODE_PIECES = 2 };
+struct BbWork { double* chunkSum; double* chunkBase; BbChunkOut* chunkOut; BbCross* cross; ParFn* at64Fn; uint8_t* at64Rank; unsigned long long* chunkBits; BbPost* post; };
+// (a chunk keeps BB_MAXC crossings: one with more sets the fail word, and k_bb_emit clamps the rank it reads to the records that exist)
+static void bb_work_size(WsSizer& sz, int nchunks) {
+    sz.take<double>(nchunks + 1); sz.take<double>(nchunks + 1); sz.take<BbChunkOut>(nchunks + 1);
+    sz.take<BbCross>((size_t)nchunks * BB_MAXC + 1); sz.take<ParFn>((size_t)nchunks * 16 + 1); sz.take<uint8_t>((size_t)nchunks * 16 + 8);
+    sz.take<unsigned long long>(nchunks + 1); sz.take<BbPost>((size_t)nchunks * BB_MAXC + 1);
+}
+static BbWork bb_work_carve(WsCarver& ws, int nchunks) {
+    BbWork W;
+    W.chunkSum = ws.take<double>(nchunks + 1); W.chunkBase = ws.take<double>(nchunks + 1); W.chunkOut = ws.take<BbChunkOut>(nchunks + 1);
+    W.cross = ws.take<BbCross>((size_t)nchunks * BB_MAXC + 1); W.at64Fn = ws.take<ParFn>((size_t)nchunks * 16 + 1); W.at64Rank = ws.take<uint8_t>((size_t)nchunks * 16 + 8);
+    W.chunkBits = ws.take<unsigned long long>(nchunks + 1); W.post = ws.take<BbPost>((size_t)nchunks * BB_MAXC + 1);
+    return W;
+}
+static void enqueue_backbone(canvas_ctx* ctx, int mode, int nchr, int nchunks, const HmmChrom* dChroms, const BbChunk* dBChunks, const int32_t* dFirstChunk, const double* dV,
+                             double* dCarry, int32_t* dFail, const int32_t* dTodo, const BbWork& W) {
+    if (mode == BB_MODE_CHAIN) hipLaunchKernelGGL(k_vit_backbone, dim3(nchr), dim3(64), 0, ctx->stream, dChroms, dV, dCarry, dTodo);
+    else if (mode == BB_MODE_SCAN) hipLaunchKernelGGL(k_vit_backbone_scan, dim3(nchr), dim3(BS_T), 0, ctx->stream, dChroms, dV, dCarry, dFail);
+    else {
+        hipLaunchKernelGGL(k_bb_sums, dim3(nchunks), dim3(256), 0, ctx->stream, dBChunks, dChroms, dV, W.chunkSum, dFail);
+        hipLaunchKernelGGL(k_bb_bases, dim3(nchr), dim3(64), 0, ctx->stream, dFirstChunk, W.chunkSum, W.chunkBase);
+        hipLaunchKernelGGL(k_bb_pieces, dim3(nchunks), dim3(256), 0, ctx->stream, dBChunks, dChroms, dV, W.chunkBase, W.chunkOut, W.cross, W.at64Fn, W.at64Rank, dFail);
+        hipLaunchKernelGGL(k_bb_walk, dim3(nchr), dim3(64), 0, ctx->stream, dFirstChunk, W.chunkOut, W.cross, W.chunkBits, W.post, dFail);
+        hipLaunchKernelGGL(k_bb_emit, dim3(nblk2((int64_t)nchunks * 16, 256)), dim3(256), 0, ctx->stream, dBChunks, nchunks, dChroms, W.chunkBits, W.post, W.at64Fn, W.at64Rank, dCarry);
+    }
+}
+
+// CANVAS_HMM_TEST_CORRUPT (test hook): which guessed back-pointer is flipped behind k_vit_spec, and in how many attempts.
+//   "1"        state 2 at step T / 2 of chromosome 0, first attempt, no retry: the chromosome goes to the sequential kernel
+//   "c:t:j"    state j at chromosome-relative step t >= 1 of chromosome c, first attempt, no retry
+//   "c:t:j:k"  the same in attempts 0 .. k-1 (k = 1 .. 5), and the retries run: attempt k is the first one left alone
+struct VitCorrupt { bool on = false, retry = false; int chrom = 0; int64_t t = 0; int state = 2; int attempts = 0; };
+static int32_t vit_corrupt_parse(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_offset, VitCorrupt& K) {
+    const char* s = cvx_hook("CANVAS_HMM_TEST_CORRUPT");
+    if (!s) return CANVAS_OK;
+    K.on = true;
+    if (!strcmp(s, "1")) {
+        const int64_t T = h_chr_offset[1] - h_chr_offset[0];
+        K.chrom = 0; K.t = T / 2; K.state = 2; K.attempts = T > 10 ? 1 : 0;
+        return CANVAS_OK;
+    }
+    long long v[4] = {0, 0, 0, 0}; int nf = 0; const char* p = s;
+    for (;;) {
+        char* end = nullptr;
+        if (nf == 4 || *p < '0' || *p > '9') { nf = -1; break; }
+        v[nf++] = strtoll(p, &end, 10);
+        if (end - p > 12) { nf = -1; break; }
+        if (*end == 0) break;
+        if (*end != ':') { nf = -1; break; }
+        p = end + 1;
+    }
+    if (nf != 3 && nf != 4) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "CANVAS_HMM_TEST_CORRUPT: 1, c:t:j or c:t:j:k");
+    if (v[0] >= nchr) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "CANVAS_HMM_TEST_CORRUPT: no such chromosome");
+    const int64_t T = h_chr_offset[v[0] + 1] - h_chr_offset[v[0]];
+    if (T <= 10 || v[1] < 1 || v[1] >= T) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "CANVAS_HMM_TEST_CORRUPT: the step must be 1 .. T-1 of a chromosome of more than ten bins");
+    if (v[2] >= NSTATE) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "CANVAS_HMM_TEST_CORRUPT: the state must be 0 .. 4");
+    if (nf == 4 && (v[3] < 1 || v[3] > 5)) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "CANVAS_HMM_TEST_CORRUPT: 1 .. 5 corrupted attempts");
+    K.chrom = (int)v[0]; K.t = v[1]; K.state = (int)v[2]; K.attempts = nf == 4 ? (int)v[3] : 1; K.retry = nf == 4;
+    return CANVAS_OK;
+}
+
 // Shared Viterbi driver of the per-sample and the joint mode.  `prepare` fills the emission source after the common workspace has been
 // carved: idx[N] (table index per bin), the log-emission table dTab ([5][P.tableLen]) and P.  Everything after that — speculation,
 // backtrack, exact backbone, verification, sequential fallback — is mode independent: the likelihood of a step is
@@ -1530,36 +1626,15 @@ template <class PrepareA, class PrepareB>
 static int32_t hmm_pipeline(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_offset, size_t extraBytes, PrepareA prepareA, PrepareB prepareB, int32_t* d_state, SegPost* seg = nullptr,
                             bool descByValue = false /* prepareA launches nothing that reads the descriptor tables: they may arrive with the set-up kernel */) {
     const int64_t N = h_chr_offset[nchr];
-    // VB-step blocks (speculation, verification and backtrack share them)
-    std::vector<HmmChrom> chroms(nchr);
-    std::vector<int32_t> firstBlock(nchr + 1);
-    int nblocks = 0;
-    for (int c = 0; c < nchr; c++) {
-        chroms[c].begin = h_chr_offset[c]; chroms[c].T = h_chr_offset[c + 1] - h_chr_offset[c];
-        firstBlock[c] = nblocks;
-        if (chroms[c].T > 10) nblocks += (int)((chroms[c].T + VB - 1) / VB);
-    }
-    firstBlock[nchr] = nblocks;
-    std::vector<int32_t> firstGroup(nchr + 1);                  // groups of 64 blocks for the backtrack (counted from the end of each chromosome)
-    int ngroups = 0;
-    for (int c = 0; c < nchr; c++) { firstGroup[c] = ngroups; ngroups += (firstBlock[c + 1] - firstBlock[c] + 63) / 64; }
-    firstGroup[nchr] = ngroups;
-    std::vector<int32_t> firstS(nchr + 1);                      // blocks of the speculative pass (VBS steps)
-    int nblocksS = 0;
-    for (int c = 0; c < nchr; c++) { firstS[c] = nblocksS; if (chroms[c].T > 10) nblocksS += (int)((chroms[c].T + VBS - 1) / VBS); }
-    firstS[nchr] = nblocksS;
-    std::vector<int32_t> firstChunk(nchr + 1);
-    int nchunks = 0;
-    for (int c = 0; c < nchr; c++) {
-        firstChunk[c] = nchunks;
-        if (chroms[c].T > 10) nchunks += (int)((chroms[c].T + BB_CHUNK - 1) / BB_CHUNK);
-    }
-    firstChunk[nchr] = nchunks;
+    VitCorrupt corrupt;                  // (test hook, refused before anything is launched when it does not name a back-pointer of this call)
+    { int32_t rcc = vit_corrupt_parse(ctx, nchr, h_chr_offset, corrupt); if (rcc) return rcc; }
+    const HmmLists L = hmm_lists(nchr, h_chr_offset);
+    const std::vector<HmmChrom>& chroms = L.chroms;
+    const std::vector<int32_t>&firstBlock = L.firstBlock, &firstGroup = L.firstGroup, &firstS = L.firstS, &firstChunk = L.firstChunk;
+    const int nblocks = L.nblocks, ngroups = L.ngroups, nblocksS = L.nblocksS, nchunks = L.nchunks;
     const int nbSeg = (int)nblk2(N, 2048);
     WsSizer sz;
-    sz.take<BbChunk>(nchunks + 1); sz.take<int32_t>(nchr + 1); sz.take<double>(nchunks + 1); sz.take<double>(nchunks + 1); sz.take<BbChunkOut>(nchunks + 1);
-    sz.take<BbCross>((size_t)nchunks * BB_MAXC + 1); sz.take<ParFn>((size_t)nchunks * 16 + 1); sz.take<uint8_t>((size_t)nchunks * 16 + 8);
-    sz.take<unsigned long long>(nchunks + 1); sz.take<BbPost>((size_t)nchunks * BB_MAXC + 1);
+    sz.take<BbChunk>(nchunks + 1); sz.take<int32_t>(nchr + 1); bb_work_size(sz, nchunks);
     sz.take<uint16_t>(N + 8); sz.take<HmmChrom>(nchr); sz.take<int32_t>(nchr);
     sz.take<int32_t>(nchr + 1); sz.take<uint16_t>(nblocks + 8); sz.take<int8_t>(nblocks + 8);
     sz.take<int64_t>(nchr + 1); sz.take<VitBlock>(nblocks + 1); sz.take<double>(N); sz.take<double>(N + 64); sz.take<int32_t>(nchr); sz.take<int32_t>(nchr);
@@ -1580,9 +1655,7 @@ static int32_t hmm_pipeline(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_
     int8_t* dGentry = ws.take<int8_t>(ngroups + 8);
     VitBlock* dSBlocks = ws.take<VitBlock>(nblocksS + 1); uint16_t* dMapsS = ws.take<uint16_t>(nblocksS + 8); int32_t* dFirstS = ws.take<int32_t>(nchr + 1);
     BbChunk* dBChunks = ws.take<BbChunk>(nchunks + 1); int32_t* dFirstChunk = ws.take<int32_t>(nchr + 1);
-    double* dChunkSum = ws.take<double>(nchunks + 1); double* dChunkBase = ws.take<double>(nchunks + 1); BbChunkOut* dChunkOut = ws.take<BbChunkOut>(nchunks + 1);
-    BbCross* dCross = ws.take<BbCross>((size_t)nchunks * BB_MAXC + 1); ParFn* dAt64Fn = ws.take<ParFn>((size_t)nchunks * 16 + 1); uint8_t* dAt64Rank = ws.take<uint8_t>((size_t)nchunks * 16 + 8);
-    unsigned long long* dChunkBits = ws.take<unsigned long long>(nchunks + 1); BbPost* dPost = ws.take<BbPost>((size_t)nchunks * BB_MAXC + 1);
+    const BbWork bbWork = bb_work_carve(ws, nchunks);
     uint8_t* segFlags = nullptr; uint32_t* segBlockCnt = nullptr; unsigned long long* segTot = nullptr;
     if (seg) { segFlags = ws.take<uint8_t>(N + 16); segBlockCnt = ws.take<uint32_t>(nbSeg + 1); segTot = ws.take<unsigned long long>(1); seg->valid = false; }
 
@@ -1660,12 +1733,13 @@ static int32_t hmm_pipeline(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_
         // How fast the paths merge goes with how well the states are separated, i.e. with the sample's relative dispersion r = IQR / median of the coverage (known on the host:
         // the emission model is built from the same quartiles).  Share of randomised PerSampleHMM calls that needed the second attempt (tools/soak.py, SOAK_DISPERSION=1):
         // r < 0.20: 0 % at 16 steps; 0.20-0.30: 8-34 % at 16, 4-7 % at 32, 0.2 % at 64; r >= 0.30: most at 16 / 32, 5 % (r < 0.4) to 25-90 % at 64 — those keep 128
-        static const int vwEnv = cvx_hook("CANVAS_HMM_LEAD") ? atoi(cvx_hook("CANVAS_HMM_LEAD")) : 0;      // (test hook: the first attempt's cold-start lead-in)
+        const int vwEnv = cvx_hook("CANVAS_HMM_LEAD") ? atoi(cvx_hook("CANVAS_HMM_LEAD")) : 0;      // (test hook: the first attempt's cold-start lead-in; read per call, so that a test can set it)
         const int vw0 = vwEnv > 0 ? vwEnv : (ctx->hmm_dispersion < 0.20 ? VW0 : (ctx->hmm_dispersion < 0.30 ? 64 : VW));
         const int nAttempts = 5;
         for (int attempt = 0; attempt < nAttempts; attempt++) {
             const int mult = attempt <= 1 ? 1 : (attempt == 2 ? 8 : (attempt == 3 ? 64 : 512));
             const int leadSpec = attempt == 0 ? vw0 : mult * VW, leadVer = mult * VW2;
+            cvx_prof_count(ctx, "viterbi_attempt");                                                      // (host side: no event pair)
             if (attempt > 0) CANVAS_HIP_TRY(ctx, hipMemsetAsync(dFail, 0, nchr * 4, ctx->stream));      // (attempt 0: cleared by the set-up kernel)
             const dim3 gs((unsigned)((nblocksS + 63) / 64));
             // (the last two attempts run the recurrence in the reference's own form: the two-constant form of the transition term rounds differently, and a near-tie that it
@@ -1676,26 +1750,20 @@ static int32_t hmm_pipeline(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_
             else if (twoValued) hipLaunchKernelGGL((k_vit_spec<false, true>), gs, dim3(64), 0, ctx->stream, dSBlocks, nblocksS, dChroms, idx, dTab, P, psi, dMapsS, dLast, leadSpec, dTodo, VBS);
             else hipLaunchKernelGGL((k_vit_spec<false, false>), gs, dim3(64), 0, ctx->stream, dSBlocks, nblocksS, dChroms, idx, dTab, P, psi, dMapsS, dLast, leadSpec, dTodo, VBS);
             hipLaunchKernelGGL(k_pair_maps, dim3(nblk2(nblocks, 256)), dim3(256), 0, ctx->stream, dVBlocks, nblocks, dChroms, dFirstS, dMapsS, dMaps, dTodo);
-            if (attempt == 0 && cvx_hook("CANVAS_HMM_TEST_CORRUPT")) hipLaunchKernelGGL(k_vit_corrupt, dim3(1), dim3(64), 0, ctx->stream, psi, chroms[0].begin + chroms[0].T / 2);
+            if (attempt < corrupt.attempts) hipLaunchKernelGGL(k_vit_corrupt, dim3(1), dim3(64), 0, ctx->stream, psi, chroms[corrupt.chrom].begin + corrupt.t, corrupt.state);
             backtrack(true);
             hipLaunchKernelGGL(k_vit_increments, dim3(nblk2(N, 256)), dim3(256), 0, ctx->stream, dChroms, nchr, dOffDev, idx, dTab, P, d_state, N, dD);
             const char* bbMode = cvx_hook("CANVAS_HMM_BACKBONE");      // "chain" | "scan" | default: predicted pieces
             // (a retry takes the plain chain for its backbone: the predicted pieces below give up on increments they cannot bracket — more binade crossings in a chunk than
             // they keep, exponents that do not behave — and no longer lead-in changes that; the chain is one FP64 add per step, 1.5 ms for a chr1-size chromosome)
-            if ((bbMode && !strcmp(bbMode, "chain")) || (attempt > 1 && !bbMode)) hipLaunchKernelGGL(k_vit_backbone, dim3(nchr), dim3(64), 0, ctx->stream, dChroms, dD, dCarry, dTodo);
-            else if (bbMode && !strcmp(bbMode, "scan")) hipLaunchKernelGGL(k_vit_backbone_scan, dim3(nchr), dim3(BS_T), 0, ctx->stream, dChroms, dD, dCarry, dFail);
-            else {
-                hipLaunchKernelGGL(k_bb_sums, dim3(nchunks), dim3(256), 0, ctx->stream, dBChunks, dChroms, dD, dChunkSum, dFail);
-                hipLaunchKernelGGL(k_bb_bases, dim3(nchr), dim3(64), 0, ctx->stream, dFirstChunk, dChunkSum, dChunkBase);
-                hipLaunchKernelGGL(k_bb_pieces, dim3(nchunks), dim3(256), 0, ctx->stream, dBChunks, dChroms, dD, dChunkBase, dChunkOut, dCross, dAt64Fn, dAt64Rank, dFail);
-                hipLaunchKernelGGL(k_bb_walk, dim3(nchr), dim3(64), 0, ctx->stream, dFirstChunk, dChunkOut, dCross, dChunkBits, dPost, dFail);
-                hipLaunchKernelGGL(k_bb_emit, dim3(nblk2((int64_t)nchunks * 16, 256)), dim3(256), 0, ctx->stream, dBChunks, nchunks, dChroms, dChunkBits, dPost, dAt64Fn, dAt64Rank, dCarry);
-            }
+            const int bb = ((bbMode && !strcmp(bbMode, "chain")) || (attempt > 1 && !bbMode)) ? BB_MODE_CHAIN : ((bbMode && !strcmp(bbMode, "scan")) ? BB_MODE_SCAN : BB_MODE_PIECES);
+            enqueue_backbone(ctx, bb, nchr, nchunks, dChroms, dBChunks, dFirstChunk, dD, dCarry, dFail, dTodo, bbWork);
             if (lds) hipLaunchKernelGGL((k_vit_verify<true>), dim3(laneGrid), dim3(64), lds, ctx->stream, dVBlocks, nblocks, dChroms, idx, dTab, P, psi, d_state, dD, dCarry, dLast, dFail, leadVer, dTodo);
             else hipLaunchKernelGGL((k_vit_verify<false>), dim3(laneGrid), dim3(64), 0, ctx->stream, dVBlocks, nblocks, dChroms, idx, dTab, P, psi, d_state, dD, dCarry, dLast, dFail, leadVer, dTodo);
             CANVAS_HIP_TRY(ctx, hipMemcpyAsync(hFail, dFail, nchr * 4, hipMemcpyDeviceToHost, ctx->stream));
-            if (seg && attempt == 0 && !cvx_hook("CANVAS_HMM_TEST_CORRUPT")) {
+            if (seg && attempt == 0 && (!corrupt.on || corrupt.retry)) {
                 // the states are final unless a chromosome fails its verification (rare): the segment ids are derived now, under the same synchronisation
+                // (the c:t:j:k form of the corruption hook keeps this: the ids of the corrupted first attempt must then be thrown away like those of any retried call)
                 (void)segTot;
                 segSeq = cvx_mail_arm(ctx, hSegSeq);
                 enqueue_segment_ids(ctx, dOffDev, nchr, d_state, seg->d_start, seg->d_stop, N, seg->maxDist, segFlags, segBlockCnt, hSegTot /* pinned: the count is written straight to the host */, seg->d_segment_id, hSegSeq, segSeq);
@@ -1705,7 +1773,7 @@ static int32_t hmm_pipeline(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_
             redo.clear();
             for (int c = 0; c < nchr; c++) if (hFail[c] && chroms[c].T > 10) redo.push_back(c);
             if (!redo.empty() && cvx_hook("CANVAS_HMM_DEBUG_FAIL")) { fprintf(stderr, "viterbi attempt %d (lead-in x%d):", attempt, mult); for (int c : redo) fprintf(stderr, " chr%d(T=%lld, why=0x%x)", c, (long long)chroms[c].T, (unsigned)hFail[c]); fprintf(stderr, "\n"); }
-            if (redo.empty() || cvx_hook("CANVAS_HMM_TEST_CORRUPT") || cvx_hook("CANVAS_HMM_NO_RETRY")) break;
+            if (redo.empty() || (corrupt.on && !corrupt.retry) || cvx_hook("CANVAS_HMM_NO_RETRY")) break;
             if (attempt < nAttempts - 1) {       // the failed chromosomes become the to-do mask of the next attempt (dRedo doubles as the mask: nchr entries)
                 if (attempt == 0) { ctx->hmm_retry = (int)redo.size(); { ProfScope pr(ctx, "viterbi_retry"); } }     // counted for the tests / bench
                 int32_t rcq = canvas_h2d_small(ctx, dRedo, hFail, nchr * 4); if (rcq) return rcq;
@@ -1993,9 +2061,36 @@ extern "C" int32_t canvas_hmm_joint(canvas_ctx* ctx, int32_t nsamples, int32_t n
     return hmm_pipeline(ctx, nchr, h_chr_offset, ex.off, prepare, [](WsCarver&, HmmParams&, HmmEmis&) -> int32_t { return CANVAS_OK; }, d_state);
 }
 
-extern "C" {
+// ---------------------------------------------------------------- canvas_hmm_backbone_probe: the exact backbone on caller-supplied increments (tests/test_hmm_backbone_gpu.py)
+extern "C" int32_t canvas_hmm_backbone_probe(canvas_ctx* ctx, int32_t mode, int32_t nchr, const int64_t* h_chr_offset, const double* d_V, double* d_carry, int32_t* h_fail) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    if (mode < BB_MODE_CHAIN || mode > BB_MODE_PIECES || nchr < 1 || nchr > (1 << 20) || !h_chr_offset || !h_fail)
+        CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_hmm_backbone_probe: bad arguments (mode 0..2, 1..2^20 chromosomes)");
+    if (h_chr_offset[0] != 0) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_hmm_backbone_probe: the offsets start at 0");
+    for (int c = 0; c < nchr; c++) if (h_chr_offset[c + 1] < h_chr_offset[c] || h_chr_offset[c + 1] > (1ll << 30)) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_hmm_backbone_probe: the offsets decrease or pass 2^30 steps");
+    const int64_t N = h_chr_offset[nchr];
+    if (N > 0 && (!d_V || !d_carry)) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_hmm_backbone_probe: no increments / no room for the carries");
+    for (int c = 0; c < nchr; c++) h_fail[c] = 0;
+    const HmmLists L = hmm_lists(nchr, h_chr_offset);
+    const int nchunks = L.nchunks;
+    if (nchunks == 0) return CANVAS_OK;                // every chromosome is skipped (at most ten steps)
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    WsSizer sz; sz.take<HmmChrom>(nchr); sz.take<int32_t>(nchr + 1); sz.take<BbChunk>(nchunks + 1); sz.take<int32_t>(nchr); bb_work_size(sz, nchunks);
+    int32_t rc = canvas_ws_reserve(ctx, sz.off + 65536); if (rc) return rc;
+    WsCarver ws(ctx->ws);
+    HmmChrom* dChroms = ws.take<HmmChrom>(nchr); int32_t* dFirstChunk = ws.take<int32_t>(nchr + 1); BbChunk* dBChunks = ws.take<BbChunk>(nchunks + 1); int32_t* dFail = ws.take<int32_t>(nchr);
+    const BbWork W = bb_work_carve(ws, nchunks);
+    rc = canvas_h2d_small(ctx, dChroms, L.chroms.data(), (size_t)nchr * sizeof(HmmChrom)); if (rc) return rc;
+    rc = canvas_h2d_small(ctx, dFirstChunk, L.firstChunk.data(), (size_t)(nchr + 1) * 4); if (rc) return rc;
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(dFail, 0, (size_t)nchr * 4, ctx->stream));
+    hipLaunchKernelGGL((k_make_blocks<BbChunk>), dim3(nblk2(nchunks, 256)), dim3(256), 0, ctx->stream, dFirstChunk, nchr, nchunks, BB_CHUNK, dBChunks);
+    enqueue_backbone(ctx, mode, nchr, nchunks, dChroms, dBChunks, dFirstChunk, d_V, d_carry, dFail, nullptr, W);
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(h_fail, dFail, (size_t)nchr * 4, hipMemcpyDeviceToHost));
+    return CANVAS_OK;
+}
 
-}  // extern "C"
 static void enqueue_segment_ids(canvas_ctx* ctx, const int64_t* dOff, int nchr, const int32_t* d_state, const int32_t* d_start, const int32_t* d_stop, int64_t N, int32_t maxDist,
                                 uint8_t* flags, uint32_t* blockCnt, unsigned long long* dTot, int32_t* d_segment_id, unsigned* totSeq, unsigned seq) {
     const int nb = (int)nblk2(N, 2048);

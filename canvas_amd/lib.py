@@ -20,10 +20,13 @@ ABI_SYMBOLS = [
     "canvas_mask_from_fasta", "canvas_mask_exclude_intervals", "canvas_screen_hits",
     "canvas_bin_rates", "canvas_bin_size_from_rates", "canvas_bin_count_upper_bound", "canvas_bin_genome", "canvas_bin_sample", "canvas_bin_sample_gcweighted", "canvas_bin_predefined", "canvas_bin_predefined_gcweighted",
     "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_normalize_best_normal", "canvas_normalize_pca_reference", "canvas_sample_pipeline",
-    "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads", "canvas_select_probe",
+    "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads", "canvas_select_probe", "canvas_hmm_backbone_probe",
     "canvas_memcpy_h2d_async", "canvas_snv_count", "canvas_flag_unique_kmers", "canvas_fasta_case_from_mask",
     "canvas_smooth", "canvas_smooth_lengths", "canvas_smooth_plan",
 ]
+
+
+BACKBONE_PROBE_UNTOUCHED = 0x7FF8C0DEC0DEC0DE      # bits of the carries canvas_hmm_backbone_probe leaves alone (a quiet NaN no sum produces)
 
 
 class CanvasError(RuntimeError):
@@ -494,6 +497,25 @@ class Canvas:
         self._check(self.lib.canvas_select_probe(self.ctx, C.c_int32(variant), C.c_int32(dtype), C.c_void_p(dev.data_ptr()), C.c_int32(len(off) - 1), _np_ptr(off), C.c_int32(nq),
                                                  _np_ptr(lo), _np_ptr(hi), _np_ptr(kk), _np_ptr(out)))
         return out
+
+    def backbone_probe(self, mode, v, chr_offset):
+        """the exact backbone of the speculative Viterbi pass on its own (canvas_hmm_backbone_probe).  v: numpy float64 increments, chr_offset: the chromosomes' offsets into
+        them; mode 0 chain / 1 parity scan / 2 predicted pieces -> (carry float64[len(v)], fail int32[nchr]): carry[begin + t] is the running sum in front of step t for every
+        multiple t of 64 of a chromosome of more than ten steps, every other element keeps the NaN pattern BACKBONE_PROBE_UNTOUCHED"""
+        v = np.ascontiguousarray(v)
+        if v.dtype != np.float64:
+            raise CanvasError(f"backbone_probe: float64 increments, not {v.dtype.name}")
+        off = np.ascontiguousarray(chr_offset, np.int64)
+        if len(off) < 2 or off[0] != 0 or off[-1] != len(v) or (np.diff(off) < 0).any():
+            raise CanvasError("backbone_probe: the offsets start at 0, do not decrease and end at len(v)")
+        torch = self.torch
+        n = len(v)
+        dv = torch.from_numpy(v.view(np.int64) if n else np.zeros(1, np.int64)).to(self.device)             # (the bits travel as integers: NaN payloads stay as they are)
+        dc = torch.full((max(n, 1),), BACKBONE_PROBE_UNTOUCHED, dtype=torch.int64, device=self.device)
+        torch.cuda.synchronize(self.device)      # the library runs on its own stream
+        fail = np.zeros(len(off) - 1, np.int32)
+        self._check(self.lib.canvas_hmm_backbone_probe(self.ctx, C.c_int32(mode), C.c_int32(len(off) - 1), _np_ptr(off), C.c_void_p(dv.data_ptr()), C.c_void_p(dc.data_ptr()), _np_ptr(fail)))
+        return dc.cpu().numpy()[:n].view(np.float64), fail
 
     def stale_reads(self):
         """process-wide [pinned results looked at, looks that came before the result had arrived (polled until it did)] (canvas_stale_reads)"""

@@ -312,6 +312,15 @@ int32_t canvas_cbs_perm_probe(canvas_ctx* ctx, const double* h_x, int32_t n, uin
  * [0, keys in the query's segments), and (variants 0, 1) more than 16 queries on one segment: radix_select's own refusal.  tests/test_select_gpu.py compares every key with a sort. */
 int32_t canvas_select_probe(canvas_ctx* ctx, int32_t variant, int32_t dtype, const void* d_values, int32_t nseg, const int64_t* h_seg_off, int32_t nq,
                             const int32_t* h_seg_lo, const int32_t* h_seg_hi, const int64_t* h_k, uint64_t* h_keys_out);
+/* Diagnostic / test entry: the exact backbone of the speculative Viterbi pass (csrc/hmm.hip, stage B1) on caller-supplied increments.  d_V (device) holds h_chr_offset[nchr]
+ * doubles partitioned in nchr chromosomes by h_chr_offset[nchr + 1] (host, starting at 0, non-decreasing, at most 2^30).  For every chromosome of more than ten steps the entry
+ * enqueues exactly the kernels the HMM stage runs for mode 0 (the plain chain), 1 (the parity scan) or 2 (the predicted pieces, the default of the stage) and leaves in
+ * d_carry[begin + t] (device, as long as d_V) the sequential FP64 sum of the chromosome's increments 0 .. t-1 for every t = 0, 64, 128, ... below its length; no other element of
+ * d_carry is written.  h_fail[nchr]: non-zero where modes 1 / 2 gave the chromosome up (an increment that is positive, infinite or NaN; mode 2: more than 16 binade
+ * crossings inside 1024 steps, a predicted binade that turned out wrong) - its carries are then undefined, and the stage recomputes such a chromosome sequentially; mode 0 has
+ * no such word and leaves zeros.  CANVAS_ERR_INVALID for a mode outside 0..2, offsets that do not start at 0, decrease or pass 2^30, and missing arrays.
+ * tests/test_hmm_backbone_gpu.py compares every carry with the plain sequential sum, bit for bit.  No reference counterpart. */
+int32_t canvas_hmm_backbone_probe(canvas_ctx* ctx, int32_t mode, int32_t nchr, const int64_t* h_chr_offset, const double* d_V, double* d_carry, int32_t* h_fail);
 /* Host-only (no context, no GPU): the sequential stopping boundary canvas_cbs uses for (nperm, alpha) — GetBoundary.ComputeBoundary (GetBoundary.cs:19-157) with eta = 0.05 as
  * CBSRunner passes it: maxOnes (maxOnes + 1) / 2 entries with maxOnes = floor(nperm alpha) + 1.  Returns the number of entries (or a negative error code).  The library
  * evaluates the table's scans on its host thread pool with the scans' own evaluations and comparisons; exposed so that the table can be checked without a device. */

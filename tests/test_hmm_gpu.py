@@ -185,3 +185,53 @@ def test_sample_whose_median_coverage_is_zero_takes_the_sequential_kernel():
     st = cv.hmm_per_sample(torch.from_numpy(cov).to(cv.device), off).cpu().numpy()
     assert (st == paths[0]).all()
     assert cv.profile_get("viterbi_sequential")[1] == 1
+
+
+# ---- lengths and paths chosen on purpose (low-noise coverage, IQR / median < 0.2: the first speculative attempt verifies, nothing may reach the sequential kernel)
+def _check_first_attempt(cv, bins, cov, off):
+    import hmm_synth
+    assert hmm_synth.dispersion(cov) < 0.2
+    cv.profile_enable(True)
+    for name in ("viterbi_sequential", "viterbi_retry", "viterbi_attempt"):
+        cv.profile_get(name, reset=True)
+    got = _check(cv, bins, cov, off)
+    assert cv.profile_get("viterbi_sequential")[1] == 0
+    assert cv.profile_get("viterbi_attempt")[1] == 1 and cv.profile_get("viterbi_retry")[1] == 0      # (the soak's 0 % second attempts at this dispersion)
+    return got
+
+
+def test_chromosome_lengths_on_the_block_chunk_and_group_edges():
+    """one block is 128 steps (64 in the speculative pass), one backbone chunk 1024, one scan iteration 8192; at most ten bins: skipped; empty chromosomes in between"""
+    import hmm_synth
+    cv = get_canvas()
+    lengths = [11, 12, 63, 64, 65, 127, 128, 129, 191, 192, 193, 1023, 1024, 1025, 8191, 8192, 8193, 10, 1, 0]
+    bins, cov, off = hmm_synth.coverage(20260927 + 300, lengths)
+    got = _check_first_attempt(cv, bins, cov, off)
+    assert (got[off[17]:] == -1).all() and len(np.unique(got[:off[17]])) >= 3
+
+
+def test_one_chromosome_of_more_than_64_backtrack_groups():
+    """524 288 + 129 bins are 4 098 blocks = 65 groups of 64: k_bt_gchain takes a second iteration (no default-bin-size chromosome is that long)"""
+    import hmm_synth
+    cv = get_canvas()
+    bins, cov, off = hmm_synth.coverage(20260927 + 301, [524_288 + 129, 300])
+    got = _check_first_attempt(cv, bins, cov, off)
+    assert len(np.unique(got)) >= 3
+
+
+def test_emission_table_too_large_for_lds(monkeypatch):
+    """a sample whose median coverage is about 600 has an emission table of 5 x 1511 doubles, above the 48 KB the kernels stage in LDS: the <false, *> forms of k_vit_spec
+    and k_vit_verify read the table from memory.  The default path runs the two-constant recurrence; with the first three attempts corrupted the fourth runs the reference's
+    five-constant form."""
+    import hmm_synth
+    cv = get_canvas()
+    bins, cov, off = hmm_synth.coverage(20260927 + 302, [3000, 1500, 129], median=600.0, sd=20.0)
+    per = [np.ascontiguousarray(cov[off[c]:off[c + 1]]) for c in range(3)]
+    median, _ = O.hmm_global_params(per)
+    table_len = int(np.rint(median / 2.0 * 5)) + 10 + 1          # HiddenMarkovModelsRunner.cs:111-152: maxValue = 5 x the haploid mean, + 10, + the zero
+    assert 5 * table_len * 8 > 48 * 1024
+    base = _check_first_attempt(cv, bins, cov, off)
+    monkeypatch.setenv("CANVAS_HMM_TEST_CORRUPT", "1:700:2:3")
+    got = _check(cv, bins, cov, off)
+    assert (got == base).all()
+    assert cv.profile_get("viterbi_attempt")[1] == 4 and cv.profile_get("viterbi_retry")[1] == 1 and cv.profile_get("viterbi_sequential")[1] == 0
