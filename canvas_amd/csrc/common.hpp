@@ -76,6 +76,7 @@ struct canvas_ctx {
     void* wv_fgh = nullptr; int wv_fgh_len = 0;          // canvas_wavelets: the step coefficients of every (node length, position) of the short nodes, computed once  // canvas_wavelets: streams confined to disjoint sets of compute units (the exact chains keep theirs to themselves)
     int wv_streams_tried = 0; unsigned wv_calls = 1;
     void* wv_pin = nullptr; size_t wv_pin_bytes = 0;   // pinned arena of canvas_wavelets (host copy of the coverage + staging lists), kept between calls
+    std::shared_ptr<void> wv_inputs;           // wavelets.hip: cv, factor-of-three values, per-chromosome median / sigma / keepAbove of the last canvas_wavelets call (canvas_wavelets_inputs)
     long long wv_stats[4] = {0, 0, 0, 0};     // ... long nodes decided from the closed form / sent to the chain undecided / chained for their coefficient; closed form in use
     unsigned mail_seq = 0;      // sequence numbers of the results kernels write straight into pinned host memory (cvx_mail_*, below)
     unsigned covq_seq = 0;      // ... the one the pending quartile result (covq_pin) will carry

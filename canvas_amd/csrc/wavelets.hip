@@ -520,6 +520,39 @@ struct WvPart { double lw, t, b, u1, u2; int32_t idx, i1; };
 struct WvSlot { WvDNode nd; int32_t chunkBase, arrived; };      // a node of the current level + where its chunks start + how many of them are done
 __device__ __forceinline__ void wv_st_f64(double* p, double v) { __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void wv_st_i32(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// What k_wv_level needs of a node before it looks at an element: the exact sums in front of it and over it (100 S_n, 100 R_1)
+struct WvNodeSums { long long n, s, cbase, pm1, qm1, Ktot, KR1; double dn, invN; };
+__device__ __forceinline__ WvNodeSums wv_node_sums(const long long* __restrict__ P1, const long long* __restrict__ P2, const long long* __restrict__ off, const WvDNode& nd) {
+    WvNodeSums h;
+    h.n = nd.len; h.s = nd.start; h.cbase = off[nd.chrom];
+    h.pm1 = h.s > h.cbase ? P1[h.s - 1] : 0; h.qm1 = h.s > h.cbase ? P2[h.s - 1] : 0;       // sums in front of the node
+    h.Ktot = P1[h.s + h.n - 1] - h.pm1; h.KR1 = h.Ktot - (P1[h.s] - h.pm1);
+    h.dn = (double)h.n; h.invN = 1.0 / h.dn;
+    return h;
+}
+// T[m] and B[m] of element m = 0 .. n-2 of a node, in units of 100 x (the closed form and its rounding-error bound, see above): the inner loop of k_wv_level, and
+// k_wv_bound_probe, which stores the pair for canvas_wavelets_bound_probe
+__device__ __forceinline__ void wv_bound_eval(const long long* __restrict__ P1, const long long* __restrict__ P2, const WvNodeSums& h, long long m, double& T, double& B) {
+    const double u = 1.1102230246251565e-16;
+    const long long Kp = P1[h.s + m] - h.pm1, Kr = h.Ktot - Kp;
+    const long long KS = m > 0 ? (P2[h.s + m - 1] - h.qm1) - m * h.pm1 : 0;          // 100 SS_m
+    const long long KRR = m * h.Ktot - KS;               // 100 RR_m
+    const double sp = (double)Kp, sr = (double)Kr, dm1 = (double)(m + 1), dr = (double)(h.n - m - 1);
+    // A_m = sqrt((n-m-1) / ((m+1) n)), C_m = 1 / (n A_m): one division, one square root and one more division per element (2.6 u and 4.6 u off the exact
+    // square roots: with the products and the subtraction below, T is within 6.6 u (I+* + I-*) of its exact value — the 9 u of the bound); n / (n-m-1) only
+    // enters the bound and is taken from the single-precision reciprocal, rounded up
+    const double a = sqrt((dr / dm1) * h.invN), c = 1.0 / (h.dn * a);
+    const double ip = a * sp, im = c * sr;
+    T = ip - im;
+    const double ndr = h.dn * (double)(__frcp_rn((float)dr) * 1.000001f) * 1.000001;
+    B = u * (a * (4.02 * (double)KS + (3.0 + ndr) * sp) + c * ((h.dn + 1.01) * (double)h.KR1 + 4.03 * (double)KRR + (3.5 + 0.5 * ndr) * sp) + 9.0 * (ip + im)) * 1.01;
+}
+__global__ void __launch_bounds__(256) k_wv_bound_probe(const WvDNode* __restrict__ nodes, const long long* __restrict__ outOff, const long long* __restrict__ P1, const long long* __restrict__ P2,
+                                                        const long long* __restrict__ off, double* __restrict__ outT, double* __restrict__ outB) {
+    const WvDNode nd = nodes[blockIdx.x];
+    const WvNodeSums ns = wv_node_sums(P1, P2, off, nd);
+    for (long long m = threadIdx.x; m < ns.n - 1; m += 256) { double T, B; wv_bound_eval(P1, P2, ns, m, T, B); outT[outOff[blockIdx.x] + m] = T; outB[outOff[blockIdx.x] + m] = B; }
+}
 // appends a long node to replica r of a level's list: slot, chunk range, chunk -> slot map (global numbers: replica x capacity + local)
 __device__ __forceinline__ void wv_push_long(WvSlot* __restrict__ list, int32_t* __restrict__ chunkNode, WvDev* __restrict__ dev, WvCn* __restrict__ cnLevel /* [WV_REP] of the level */, unsigned r,
                                              unsigned listCap, unsigned chCap, const WvDNode& nd) {
@@ -559,27 +592,16 @@ __global__ void __launch_bounds__(256) k_wv_level(WvSlot* __restrict__ cur, cons
         const int slot = curChunkNode[ch];
         const WvDNode nd = cur[slot].nd;
         const int cbIdx = cur[slot].chunkBase;
-        const long long n = nd.len, s = nd.start, cbase = off[nd.chrom];
-        const long long pm1 = s > cbase ? P1[s - 1] : 0, qm1 = s > cbase ? P2[s - 1] : 0;       // sums in front of the node
-        const long long Ktot = P1[s + n - 1] - pm1, KR1 = Ktot - (P1[s] - pm1);
-        const double dn = (double)n, invN = 1.0 / dn;
+        const WvNodeSums ns = wv_node_sums(P1, P2, off, nd);
+        const long long n = ns.n, s = ns.s, cbase = ns.cbase, Ktot = ns.Ktot;
+        const double dn = ns.dn;
         // ---- the chunk's m: T, B; the thread keeps its best lower bound and its two largest upper bounds
         double bLw = -1.0e300, bT = 0.0, bB = 0.0; int32_t bIdx = 0x7FFFFFFF;
         double u1 = -1.0e300, u2 = -1.0e300; int32_t i1 = -1;
         const long long m0 = (long long)(ch - (unsigned)cbIdx) * WV_CH, m1 = min<long long>(m0 + WV_CH, n - 1);
         for (long long m = m0 + threadIdx.x; m < m1; m += 256) {
-            const long long Kp = P1[s + m] - pm1, Kr = Ktot - Kp;
-            const long long KS = m > 0 ? (P2[s + m - 1] - qm1) - m * pm1 : 0;          // 100 SS_m
-            const long long KRR = m * Ktot - KS;                                       // 100 RR_m
-            const double sp = (double)Kp, sr = (double)Kr, dm1 = (double)(m + 1), dr = (double)(n - m - 1);
-            // A_m = sqrt((n-m-1) / ((m+1) n)), C_m = 1 / (n A_m): one division, one square root and one more division per element (2.6 u and 4.6 u off the exact
-            // square roots: with the products and the subtraction below, T is within 6.6 u (I+* + I-*) of its exact value — the 9 u of the bound); n / (n-m-1) only
-            // enters the bound and is taken from the single-precision reciprocal, rounded up
-            const double a = sqrt((dr / dm1) * invN), c = 1.0 / (dn * a);
-            const double ip = a * sp, im = c * sr;
-            const double T = ip - im;
-            const double ndr = dn * (double)(__frcp_rn((float)dr) * 1.000001f) * 1.000001;
-            const double B = u * (a * (4.02 * (double)KS + (3.0 + ndr) * sp) + c * ((dn + 1.01) * (double)KR1 + 4.03 * (double)KRR + (3.5 + 0.5 * ndr) * sp) + 9.0 * (ip + im)) * 1.01;
+            double T, B;
+            wv_bound_eval(P1, P2, ns, m, T, B);
             const double at = fabs(T), lw = at - B, up = at + B;
             if (lw > bLw) { bLw = lw; bT = T; bB = B; bIdx = (int32_t)m; }
             if (up > u1) { u2 = u1; u1 = up; i1 = (int32_t)m; } else if (up > u2) u2 = up;
@@ -1030,7 +1052,99 @@ template <typename T> struct PinVec {
     T* begin() { return p; } T* end() { return p + n; } const T* begin() const { return p; } const T* end() const { return p + n; }
 };
 struct ChromTree { std::vector<int> counts; std::vector<Cand> cands; double sigma = 0, keepAbove = 0; };
+// the inputs of the last canvas_wavelets call, kept by the context next to wv_stats (canvas_wavelets_inputs reads them out; nothing is computed for them)
+struct CallInputs { bool valid = false; int hasCV = 0; int paths = 0 /* which code computed them: canvas_hip.h */; double cv = 0; double f3[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; std::vector<uint8_t> isRoot; std::vector<double> median, sigma, keepAbove; };
 }  // namespace wv
+
+// ------------------------------------------------------------------------------------------------ launch sets shared by canvas_wavelets and the probe entries
+// capacities of the device-side lists for a coverage of N bins in nchr chromosomes (see WvCn for the replicas)
+struct WvCaps { size_t maxLong, maxChunks, maxRoots, maxCh, listCap, chCap, rootCap, maxList2; };
+static WvCaps wv_caps(int64_t N, int nchr, int wvLong) {
+    WvCaps c;
+    c.maxLong = (size_t)N / wvLong + (size_t)nchr + 16; c.maxChunks = 3 * (size_t)N / WV_CS + c.maxLong + 16; c.maxRoots = (size_t)N / 2 + (size_t)nchr + 16;
+    c.maxCh = (size_t)N / WV_CH + c.maxLong + 16;
+    // the level loop's lists are WV_REP replicas (see WvCn): a replica takes an eighth of the worst case of the whole level (twice its even share; whoever appends is picked
+    // by the chunk's number, which deals the appends out evenly) — but never less than one node can need
+    c.listCap = c.maxLong / 8 + 1024; c.chCap = std::max(c.maxCh / 8, (size_t)N / WV_CH + 16) + 4096; c.rootCap = c.maxRoots / 8 + 4096;
+    c.maxList2 = (size_t)N / 8 + 1024;                          // nodes of ALL levels that wait for the exact chain
+    return c;
+}
+// k = 100 x as integers with the two `bad` words, and (P1 given) the exact prefix sums of the closed-form decisions: k_wv_prefix_tiles + k_wv_prefix_apply over tiles of WV_PT bins
+static int32_t wv_prefix_enqueue(canvas_ctx* ctx, int nchr, const int64_t* off, const double* dX, long long* dOff, int32_t* dTile0P, uint32_t* dK32, long long* dAgg, long long* dP1, long long* dP2, int* dBad) {
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dOff, off, (nchr + 1) * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(dBad, 0, 4 * sizeof(int), ctx->stream));
+    std::vector<int32_t> t0((size_t)nchr + 1, 0);
+    for (int c = 0; c < nchr; c++) t0[(size_t)c + 1] = t0[(size_t)c] + (int32_t)((off[c + 1] - off[c] + WV_PT - 1) / WV_PT);
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dTile0P, t0.data(), ((size_t)nchr + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (t0[(size_t)nchr] > 0) {
+        hipLaunchKernelGGL(k_wv_prefix_tiles, dim3((unsigned)t0[(size_t)nchr]), dim3(WV_PT), 0, ctx->stream, dX, dOff, dTile0P, nchr, dK32, dAgg, dBad);
+        if (dP1) hipLaunchKernelGGL(k_wv_prefix_apply, dim3((unsigned)t0[(size_t)nchr]), dim3(WV_PT), 0, ctx->stream, dK32, dOff, dTile0P, nchr, dAgg, dP1, dP2, dBad);
+    }
+    return CANVAS_OK;
+}
+// medians of up to WV_MED_MAXR stretches (start, length) of the coverage from its integers, three launches on the main stream; the results stay in `out` (device)
+struct WvMedBufs { const uint32_t* K32; long long *start, *len; int32_t* tile0; WvMedState* state; uint32_t *hist, *tick; };
+static int32_t wv_medians_enqueue(canvas_ctx* ctx, const WvMedBufs& M, const std::vector<long long>& st, const std::vector<long long>& ln, double* out) {
+    const size_t nr = st.size();
+    std::vector<int32_t> t0(nr + 1, 0);
+    for (size_t r = 0; r < nr; r++) t0[r + 1] = t0[r] + (int32_t)((ln[r] + WV_MT - 1) / WV_MT);
+    if (t0[nr] == 0) return CANVAS_OK;
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(M.start, st.data(), nr * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(M.len, ln.data(), nr * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(M.tile0, t0.data(), (nr + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(M.hist, 0, nr * 2 * WV_MD * sizeof(uint32_t), ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(M.tick, 0, nr * sizeof(uint32_t), ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(out, 0, nr * sizeof(double), ctx->stream));      // (an empty stretch has no tile: its median is 0)
+    for (int pass = 0; pass < 3; pass++)
+        hipLaunchKernelGGL(k_wv_rmed_pass, dim3((unsigned)t0[nr]), dim3(1024), 0, ctx->stream, M.K32, M.start, M.len, M.tile0, (int)nr, pass, M.state, M.hist, M.tick, out);
+    return CANVAS_OK;
+}
+// medians of n non-empty stretches ((start << 32) | length, on the device) over the doubles, one workgroup per stretch
+static void wv_segment_median_launch(hipStream_t st, const double* dX, const unsigned long long* dSegs, size_t n, double* out) {
+    hipLaunchKernelGGL(k_wv_segment_median, dim3((unsigned)n), dim3(1024), 0, st, dX, dSegs, out);
+}
+// the kernels of one level for the long nodes in B.list / B.base (chain = the shortcut or the IEEE division)
+static int32_t wv_long_pass(canvas_ctx* ctx, hipStream_t st, const LongBufs& B, size_t nLong, int nChunks, bool fast, const double* dX, WvOps* dOps, const long long* opsOff, const int32_t* lim) {
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(B.flag, 0, nLong * sizeof(int32_t), st));
+    if (nChunks > 0) hipLaunchKernelGGL(k_wv_coeff, dim3((unsigned)nChunks), dim3(64), 0, st, B.nodes, B.list, B.base, (int)nLong, dX, dOps, opsOff, lim);
+    { ProfScope ps(ctx, "wavelet_chain", false, st);
+      if (fast) hipLaunchKernelGGL((k_wv_chain_long<true>), dim3((unsigned)nLong), dim3(64), 0, st, B.nodes, B.list, B.base, dX, dOps, B.ck, B.head, opsOff, lim);
+      else hipLaunchKernelGGL((k_wv_chain_long<false>), dim3((unsigned)nLong), dim3(64), 0, st, B.nodes, B.list, B.base, dX, dOps, B.ck, B.head, opsOff, lim); }
+    if (nChunks > 0) hipLaunchKernelGGL(k_wv_chunks, dim3((unsigned)((nChunks + 63) / 64)), dim3(64), 0, st, B.nodes, B.list, B.base, (int)nLong, nChunks, dOps, B.ck, B.best, B.flag, opsOff, lim);
+    hipLaunchKernelGGL(k_wv_reduce, dim3((unsigned)nLong), dim3(64), 0, st, B.list, B.base, B.head, B.best, B.flag, B.out);
+    return CANVAS_OK;
+}
+// chunks of a list of long nodes, as the chain kernels count them: base[i + 1] - base[i] = chunks of node list[i] (lim: the chains stop after step lim[i])
+static int32_t wv_chunk_count(int32_t len, const int32_t* lim) { const int32_t last = lim ? std::min<int32_t>(len - 2, *lim) : len - 2; return (int32_t)((last + WV_CS - 1) / WV_CS); }
+// the level loop: what its launches work on, and the two launches themselves (the host's list becomes the list of iteration 0; iteration `it` of a batch)
+struct WvLevelBufs { WvSlot *listA, *listB; int32_t *chA, *chB; WvPart* parts; WvDev* dev; WvCn *cn, *rootCn; unsigned listCap, chCap, maxList2; const long long *P1, *P2, *off; const double* keep;
+                     WvRoot* roots; unsigned rootCap; WvDNode* exact; int32_t* exactInd; WvDNode* undec; int32_t* counts; int wvLong; };
+static unsigned wv_level_grid() {      // (2 048 workgroups of 256 = eight waves per SIMD: levels 13.6-14.6 -> 13.0-13.2 ms against 1 024; 4 096: 12.7)
+    static const unsigned levelGrid = [] { const char* e = cvx_hook("CANVAS_WV_LEVEL_GRID"); const int v = e ? atoi(e) : 2048; return (unsigned)(v >= 64 && v <= 8192 ? v : 2048); }();
+    return levelGrid;
+}
+static void wv_list_init_launch(hipStream_t st, const WvLevelBufs& L, const WvDNode* dListIn, int nIn) {
+    hipLaunchKernelGGL(k_wv_list_init, dim3((unsigned)((nIn + 255) / 256)), dim3(256), 0, st, dListIn, nIn, L.listA, L.chA, L.dev, L.cn, L.listCap, L.chCap);
+}
+static void wv_level_launch(hipStream_t st, const WvLevelBufs& L, int it) {
+    hipLaunchKernelGGL(k_wv_level, dim3(wv_level_grid()), dim3(256), 0, st, (it & 1) ? L.listB : L.listA, (it & 1) ? L.chB : L.chA, (it & 1) ? L.listA : L.listB, (it & 1) ? L.chA : L.chB, L.parts,
+                       L.dev, L.cn, L.rootCn, it, L.listCap, L.chCap, L.maxList2, L.P1, L.P2, L.off, L.keep, L.roots, L.rootCap, L.exact, L.exactInd, L.undec, L.counts, L.wvLong);
+}
+// the subtree walkers of nr roots (the stretches of the root array in sg), one lane each
+struct WvSubBufs { const WvRoot* roots; const double* X; const double* keep; uint32_t* stack; int32_t* counts; WvCand* cands; unsigned long long* ncand; unsigned long long capCand; int32_t* overflow; const WvFgh* fgh; int fghLen; };
+static void wv_subtree_launch(hipStream_t st, const WvSubBufs& S, const WvRootSegs& sg, size_t nr) {
+    hipLaunchKernelGGL(k_wv_subtree, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, st, S.roots, sg, S.X, S.keep, S.stack, S.counts, S.cands, S.ncand, S.capCand, S.overflow, S.fgh, S.fghLen);
+}
+// the table of step coefficients for nodes of up to L elements, kept by the context
+static int32_t wv_fgh_ensure(canvas_ctx* ctx, int L) {
+    if (ctx->wv_fgh_len == L) return CANVAS_OK;
+    if (ctx->wv_fgh) { (void)hipFree(ctx->wv_fgh); ctx->wv_fgh = nullptr; ctx->wv_fgh_len = 0; }
+    CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->wv_fgh, (size_t)(L + 1) * (size_t)(L + 1) * sizeof(WvFgh)));
+    hipLaunchKernelGGL(k_wv_fgh_table, dim3((unsigned)(L + 1)), dim3(256), 0, ctx->stream, (WvFgh*)ctx->wv_fgh, L);
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->wv_fgh_len = L;
+    return CANVAS_OK;
+}
 
 extern "C" int32_t canvas_wavelets(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int32_t is_germline,
                                    double threshold_lower, double threshold_upper, double mad_factor, int32_t variability_window, int32_t min_size,
@@ -1047,6 +1161,9 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
     const double tEntry = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     if (nchr <= 0 || !d_cov || !h_chr_offset || !h_breakpoints || !h_bp_offset || variability_window <= 0) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_wavelets: bad arguments");
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->wv_inputs) ctx->wv_inputs = std::make_shared<wv::CallInputs>();
+    wv::CallInputs& callInputs = *(wv::CallInputs*)ctx->wv_inputs.get();
+    callInputs.valid = false;
     int32_t rc0 = CANVAS_OK;
     const int64_t N = h_chr_offset[nchr] - h_chr_offset[0];
     if (N <= 0 || N > 0x7FFFFFF0ll) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_wavelets: bin count out of range");
@@ -1103,13 +1220,7 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
     }
     rc0 = canvas_side_init(ctx); if (rc0) return rc0;
     if (!ctx->wv_sub2) CANVAS_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->wv_sub2, hipStreamNonBlocking));
-    if (ctx->wv_fgh_len != WV_LONG) {
-        if (ctx->wv_fgh) { (void)hipFree(ctx->wv_fgh); ctx->wv_fgh = nullptr; ctx->wv_fgh_len = 0; }
-        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->wv_fgh, (size_t)(WV_LONG + 1) * (size_t)(WV_LONG + 1) * sizeof(WvFgh)));
-        hipLaunchKernelGGL(k_wv_fgh_table, dim3((unsigned)(WV_LONG + 1)), dim3(256), 0, ctx->stream, (WvFgh*)ctx->wv_fgh, WV_LONG);
-        CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->wv_fgh_len = WV_LONG;
-    }
+    rc0 = wv_fgh_ensure(ctx, WV_LONG); if (rc0) return rc0;
     const WvFgh* dFgh = cvx_hook("CANVAS_WV_NO_TABLE") ? nullptr : (const WvFgh*)ctx->wv_fgh; const int fghLen = dFgh ? WV_LONG : 0;
     if (!ctx->wv_sub) CANVAS_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->wv_sub, hipStreamNonBlocking));      // the subtree walkers of the roots a batch of levels leaves: next to the following levels and to the chains
     if (ctx->wv_main && ctx->wv_chain) CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (the masked streams start from a finished producer)
@@ -1126,11 +1237,8 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
     std::thread f3Thread([&]() { if (f3OnDevice && !f3Check) return; (void)hipEventSynchronize(ctx->wv_ev_x); const double a = now(); f3 = factor_of_three(nchr, X.data(), off.data()); f3Seconds = now() - a; });
     struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } f3Join{f3Thread};      // joined on every exit path
     // ---- device buffers
-    const size_t maxLong = (size_t)N / WV_LONG + (size_t)nchr + 16, maxChunks = 3 * (size_t)N / WV_CS + maxLong + 16, maxRoots = (size_t)N / 2 + (size_t)nchr + 16;
-    const size_t maxCh = (size_t)N / WV_CH + maxLong + 16;
-    // the level loop's lists are WV_REP replicas (see WvCn): a replica takes an eighth of the worst case of the whole level (twice its even share; whoever appends is picked
-    // by the chunk's number, which deals the appends out evenly) — but never less than one node can need
-    const size_t listCap = maxLong / 8 + 1024, chCap = std::max(maxCh / 8, (size_t)N / WV_CH + 16) + 4096, rootCap = maxRoots / 8 + 4096, nCn = (size_t)(WV_LB + 3) * WV_REP;
+    const WvCaps caps = wv_caps(N, nchr, WV_LONG);
+    const size_t maxLong = caps.maxLong, maxChunks = caps.maxChunks, maxRoots = caps.maxRoots, listCap = caps.listCap, chCap = caps.chCap, rootCap = caps.rootCap, nCn = (size_t)(WV_LB + 3) * WV_REP;
     if (maxRoots + WV_REP * rootCap > 0x7FFFFFF0ull || WV_REP * chCap > 0x7FFFFFF0ull) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_wavelets: bin count out of range");      // (the replicas' stretches are addressed with 32-bit numbers)
     const unsigned long long capCand = (unsigned long long)N + 16;
     WsSizer sz;
@@ -1138,7 +1246,7 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
     sz.take<WvOps>(opsCap); sz.take<WvNode>(maxLong); sz.take<WvOut>(maxLong); sz.take<int32_t>(maxLong);
     sz.take<int32_t>(maxLong + 1); sz.take<int32_t>(maxLong); sz.take<WvHead>(maxLong); sz.take<WvCk>(maxChunks); sz.take<WvBest>(maxChunks);
     sz.take<WvRoot>(maxRoots + WV_REP * rootCap); sz.take<uint32_t>((size_t)N); sz.take<int32_t>((size_t)N); sz.take<WvCand>((size_t)capCand); sz.take<double>(nchr); sz.take<unsigned long long>(2);
-    const size_t maxList2 = (size_t)N / 8 + 1024;                          // nodes of ALL levels that wait for the exact chain
+    const size_t maxList2 = caps.maxList2;
     sz.take<long long>((size_t)N); sz.take<long long>((size_t)N); sz.take<long long>(nchr + 1); sz.take<int>(4); sz.take<WvSlot>(WV_REP * listCap); sz.take<WvSlot>(WV_REP * listCap); sz.take<WvCn>(nCn); sz.take<WvDNode>(maxList2); sz.take<int32_t>(maxList2);
     sz.take<int32_t>(WV_REP * chCap); sz.take<int32_t>(WV_REP * chCap); sz.take<WvPart>(WV_REP * chCap); sz.take<WvDNode>(maxLong);
     sz.take<WvDNode>(maxList2); sz.take<WvDev>(1); sz.take<long long>(maxLong); sz.take<int32_t>(maxLong);
@@ -1174,37 +1282,15 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
     uint32_t* dK32 = ws.take<uint32_t>((size_t)N); long long* dAgg = ws.take<long long>(2 * prefTiles); int32_t* dTile0P = ws.take<int32_t>(nchr + 2);
     long long* dMedStart = ws.take<long long>(medR); long long* dMedLen = ws.take<long long>(medR); int32_t* dMedTile0 = ws.take<int32_t>(medR + 2); WvMedState* dMedState = ws.take<WvMedState>(medR);
     uint32_t* dMedHist = ws.take<uint32_t>(medR * 2 * WV_MD); uint32_t* dMedTick = ws.take<uint32_t>(medR);
-    // medians of up to WV_MED_MAXR stretches (start, length) of the coverage from its integers, three launches on the main stream; the results stay in `out` (device)
-    auto medians_enqueue = [&](const std::vector<long long>& st, const std::vector<long long>& ln, double* out) -> int32_t {
-        const size_t nr = st.size();
-        std::vector<int32_t> t0(nr + 1, 0);
-        for (size_t r = 0; r < nr; r++) t0[r + 1] = t0[r] + (int32_t)((ln[r] + WV_MT - 1) / WV_MT);
-        if (t0[nr] == 0) return CANVAS_OK;
-        CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dMedStart, st.data(), nr * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-        CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dMedLen, ln.data(), nr * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-        CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dMedTile0, t0.data(), (nr + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        CANVAS_HIP_TRY(ctx, hipMemsetAsync(dMedHist, 0, nr * 2 * WV_MD * sizeof(uint32_t), ctx->stream));
-        CANVAS_HIP_TRY(ctx, hipMemsetAsync(dMedTick, 0, nr * sizeof(uint32_t), ctx->stream));
-        CANVAS_HIP_TRY(ctx, hipMemsetAsync(out, 0, nr * sizeof(double), ctx->stream));      // (an empty stretch has no tile: its median is 0)
-        for (int pass = 0; pass < 3; pass++)
-            hipLaunchKernelGGL(k_wv_rmed_pass, dim3((unsigned)t0[nr]), dim3(1024), 0, ctx->stream, dK32, dMedStart, dMedLen, dMedTile0, (int)nr, pass, dMedState, dMedHist, dMedTick, out);
-        return CANVAS_OK;
-    };
+    const WvMedBufs medBufs{dK32, dMedStart, dMedLen, dMedTile0, dMedState, dMedHist, dMedTick};
+    auto medians_enqueue = [&](const std::vector<long long>& st, const std::vector<long long>& ln, double* out) -> int32_t { return wv_medians_enqueue(ctx, medBufs, st, ln, out); };
     // what does not depend on the thresholds starts now, next to the host's order statistics: counters cleared, the exact prefix sums of the closed-form decisions
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dCounts, 0, (size_t)N * sizeof(int32_t), ctx->stream));
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dNcand, 0, 2 * sizeof(unsigned long long), ctx->stream));
     const bool tryClosedForm = !cvx_hook("CANVAS_WV_CHAIN_ONLY");
     int hBad[2] = {0, 0};
     if (tryClosedForm) {
-        CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dOff, off.data(), (nchr + 1) * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-        CANVAS_HIP_TRY(ctx, hipMemsetAsync(dBad, 0, 4 * sizeof(int), ctx->stream));
-        std::vector<int32_t> t0((size_t)nchr + 1, 0);
-        for (int c = 0; c < nchr; c++) t0[(size_t)c + 1] = t0[(size_t)c] + (int32_t)((off[c + 1] - off[c] + WV_PT - 1) / WV_PT);
-        CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dTile0P, t0.data(), ((size_t)nchr + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        if (t0[(size_t)nchr] > 0) {
-            hipLaunchKernelGGL(k_wv_prefix_tiles, dim3((unsigned)t0[(size_t)nchr]), dim3(WV_PT), 0, ctx->stream, dX, dOff, dTile0P, nchr, dK32, dAgg, dBad);
-            hipLaunchKernelGGL(k_wv_prefix_apply, dim3((unsigned)t0[(size_t)nchr]), dim3(WV_PT), 0, ctx->stream, dK32, dOff, dTile0P, nchr, dAgg, dP1, dP2, dBad);
-        }
+        int32_t rcp = wv_prefix_enqueue(ctx, nchr, off.data(), dX, dOff, dTile0P, dK32, dAgg, dP1, dP2, dBad); if (rcp) return rcp;
         CANVAS_HIP_TRY(ctx, hipMemcpyAsync(hBad, dBad, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));      // [0] not two-decimal values, [1] not finite: looked at behind the next synchronisation
     } else { rc = host_finite_check(); if (rc) return rc; }
     // ---- SegmentationInput.GetCoverageVariability (Segmentation.cs:308-328): the per-window statistics come from the device (CANVAS_WV_VAR_HOST=1: the host threads;
@@ -1368,6 +1454,7 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
     long long levels = 0, redone = 0;
     // short nodes leave the level loop with their whole subtree: one lane each, on the side stream (nothing waits for them until the end)
     // (kernels on one stream run one after the other and a subtree lane is latency-bound, so the roots of many levels share a launch)
+    const WvSubBufs subBufs{dRoots, dX, dKeep, dStack, dCounts, dCands, dNcand, capCand, dOverflow, dFgh, fghLen};
     auto flush_roots = [&](bool force) -> int32_t {
         if (hRoots.empty() || (!force && hRoots.size() < 4096)) return CANVAS_OK;
         if (rootsUsed + hRoots.size() > maxRoots) CANVAS_FAIL(ctx, CANVAS_ERR_HIP, "canvas_wavelets: root list overflow");
@@ -1375,7 +1462,7 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
         const std::vector<WvRoot>& B = rootBatches.back();
         CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dRoots + rootsUsed, B.data(), B.size() * sizeof(WvRoot), hipMemcpyHostToDevice, ctx->side));
         { WvRootSegs sg; memset(&sg, 0, sizeof sg); sg.n = 1; sg.start[0] = (int)rootsUsed; sg.count[0] = (int)B.size();
-          hipLaunchKernelGGL(k_wv_subtree, dim3((unsigned)((B.size() + 63) / 64)), dim3(64), 0, ctx->side, dRoots, sg, dX, dKeep, dStack, dCounts, dCands, dNcand, capCand, dOverflow, dFgh, fghLen); }
+          wv_subtree_launch(ctx->side, subBufs, sg, B.size()); }
         rootsUsed += B.size();
         return CANVAS_OK;
     };
@@ -1391,16 +1478,7 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
         rc = flush_roots(false); if (rc) return rc;
     }
     // the kernels of one level for the long nodes in dLong / dBase (chain = the shortcut or the IEEE division)
-    auto long_pass_on = [&](hipStream_t st, const LongBufs& B, size_t nLong, int nChunks, bool fast, const long long* opsOff, const int32_t* lim) -> int32_t {
-        CANVAS_HIP_TRY(ctx, hipMemsetAsync(B.flag, 0, nLong * sizeof(int32_t), st));
-        if (nChunks > 0) hipLaunchKernelGGL(k_wv_coeff, dim3((unsigned)nChunks), dim3(64), 0, st, B.nodes, B.list, B.base, (int)nLong, dX, dOps, opsOff, lim);
-        { ProfScope ps(ctx, "wavelet_chain", false, st);
-          if (fast) hipLaunchKernelGGL((k_wv_chain_long<true>), dim3((unsigned)nLong), dim3(64), 0, st, B.nodes, B.list, B.base, dX, dOps, B.ck, B.head, opsOff, lim);
-          else hipLaunchKernelGGL((k_wv_chain_long<false>), dim3((unsigned)nLong), dim3(64), 0, st, B.nodes, B.list, B.base, dX, dOps, B.ck, B.head, opsOff, lim); }
-        if (nChunks > 0) hipLaunchKernelGGL(k_wv_chunks, dim3((unsigned)((nChunks + 63) / 64)), dim3(64), 0, st, B.nodes, B.list, B.base, (int)nLong, nChunks, dOps, B.ck, B.best, B.flag, opsOff, lim);
-        hipLaunchKernelGGL(k_wv_reduce, dim3((unsigned)nLong), dim3(64), 0, st, B.list, B.base, B.head, B.best, B.flag, B.out);
-        return CANVAS_OK;
-    };
+    auto long_pass_on = [&](hipStream_t st, const LongBufs& B, size_t nLong, int nChunks, bool fast, const long long* opsOff, const int32_t* lim) -> int32_t { return wv_long_pass(ctx, st, B, nLong, nChunks, fast, dX, dOps, opsOff, lim); };
     LongBufs M; M.nodes = dNodes; M.out = dOut; M.list = dLong; M.base = dBase; M.flag = dFlag; M.head = dHead; M.ck = dCk; M.best = dBest;
     auto long_pass = [&](size_t nLong, int nChunks, bool fast, const long long* opsOff = nullptr, const int32_t* lim = nullptr) -> int32_t { return long_pass_on(ctx->stream, M, nLong, nChunks, fast, opsOff, lim); };
     auto upload_long = [&](const PinVec<int32_t>& list, const std::vector<int32_t>* lim = nullptr) -> int {                // returns the number of chunks
@@ -1441,7 +1519,7 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
                 if (have > devRootsLaunched[r]) { sg.start[sg.n] = (int)(maxRoots + (size_t)r * rootCap + devRootsLaunched[r]); sg.count[sg.n] = (int)(have - devRootsLaunched[r]); nr += have - devRootsLaunched[r]; sg.n++; devRootsLaunched[r] = have; }
             }
             if (nr == 0) return;
-            hipLaunchKernelGGL(k_wv_subtree, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, (subLaunches++ & 1) ? ctx->wv_sub2 : ctx->wv_sub, dRoots, sg, dX, dKeep, dStack, dCounts, dCands, dNcand, capCand, dOverflow, dFgh, fghLen);      // (a launch lasts as long as its slowest lane: two streams take turns)
+            wv_subtree_launch((subLaunches++ & 1) ? ctx->wv_sub2 : ctx->wv_sub, subBufs, sg, nr);      // (a launch lasts as long as its slowest lane: two streams take turns)
         };
         if (firstRoots.size() + rootsUsed > maxRoots) CANVAS_FAIL(ctx, CANVAS_ERR_HIP, "canvas_wavelets: root list overflow");
         if (!firstRoots.empty()) CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dRoots + rootsUsed, firstRoots.data(), firstRoots.size() * sizeof(WvRoot), hipMemcpyHostToDevice, ctx->stream));
@@ -1544,7 +1622,8 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
             exactSeen += k;
             return CANVAS_OK;
         };
-        static const unsigned levelGrid = [] { const char* e = cvx_hook("CANVAS_WV_LEVEL_GRID"); const int v = e ? atoi(e) : 2048; return (unsigned)(v >= 64 && v <= 8192 ? v : 2048); }();      // (2 048 workgroups of 256 = eight waves per SIMD: levels 13.6-14.6 -> 13.0-13.2 ms against 1 024; 4 096: 12.7)
+        const WvLevelBufs levelBufs{dListA, dListB, dChA, dChB, dParts, dDev, dCn, dRootCn, (unsigned)listCap, (unsigned)chCap, (unsigned)maxList2, dP1, dP2, dOff, dKeep,
+                                    dRoots + maxRoots, (unsigned)rootCap, dExact, dExactInd, dUndec, dCounts, WV_LONG};
         while (!hList.empty()) {
             if (hList.size() > maxLong) CANVAS_FAIL(ctx, CANVAS_ERR_HIP, "canvas_wavelets: long-node list overflow");
             const int nIn = (int)hList.size();
@@ -1556,15 +1635,13 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
             *hdevIn = hdev;
             CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dDev, hdevIn, sizeof hdev, hipMemcpyHostToDevice, ctx->stream));
             CANVAS_HIP_TRY(ctx, hipMemsetAsync(dCn, 0, (size_t)(WV_LB + 2) * WV_REP * sizeof(WvCn), ctx->stream));
-            hipLaunchKernelGGL(k_wv_list_init, dim3((unsigned)((nIn + 255) / 256)), dim3(256), 0, ctx->stream, dListIn, nIn, dListA, dChA, dDev, dCn, (unsigned)listCap, (unsigned)chCap);
+            wv_list_init_launch(ctx->stream, levelBufs, dListIn, nIn);
             hipEvent_t ev[2] = {ctx->side_ev, ctx->side_ev2};
             static const int firstBatch = [] { const char* e = cvx_hook("CANVAS_WV_FIRST_BATCH"); const int v = e ? atoi(e) : 16; return v >= 2 && v <= 64 && !(v & 1) ? v : 16; }();
             int lbOf[2] = {0, 0}, lbNext = firstBatch; unsigned seqOf[2] = {0, 0};       // (16, 32, 64 ... levels.  Smaller first batches start the longest chain earlier but split the chains over several launches of ONE in-order stream, which then run one after the other: 2, 4, 8 ... was 9 ms slower)
             auto enqueue_batch = [&](int slot) -> int32_t {
                 const int lb = lbNext; lbOf[slot] = lb; lbNext = std::min(64, lbNext * 2);
-                for (int it = 0; it < lb; it++)
-                    hipLaunchKernelGGL(k_wv_level, dim3(levelGrid), dim3(256), 0, ctx->stream, (it & 1) ? dListB : dListA, (it & 1) ? dChB : dChA, (it & 1) ? dListA : dListB, (it & 1) ? dChA : dChB, dParts,
-                                       dDev, dCn, dRootCn, it, (unsigned)listCap, (unsigned)chCap, (unsigned)maxList2, dP1, dP2, dOff, dKeep, dRoots + maxRoots, (unsigned)rootCap, dExact, dExactInd, dUndec, dCounts, WV_LONG);
+                for (int it = 0; it < lb; it++) wv_level_launch(ctx->stream, levelBufs, it);
                 hipLaunchKernelGGL(k_wv_batch_end, dim3(1), dim3(256), 0, ctx->stream, dDev, dCn, dRootCn, lb, dExact, dExactInd, hdevRep[slot], hExactPin[slot], hExactIndPin[slot], (unsigned)maxLong, ++batchSeq);
                 seqOf[slot] = batchSeq;
                 CANVAS_HIP_TRY(ctx, hipEventRecord(ev[slot], ctx->stream));
@@ -1879,7 +1956,7 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
                 rc = medians_enqueue(st, ln, dSegMed); if (rc) return rc;
             } else {
                 CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dVarStart, segs.data(), segs.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-                hipLaunchKernelGGL(k_wv_segment_median, dim3((unsigned)segs.size()), dim3(1024), 0, ctx->stream, dX, (const unsigned long long*)dVarStart, dSegMed);
+                wv_segment_median_launch(ctx->stream, dX, (const unsigned long long*)dVarStart, segs.size(), dSegMed);
             }
             CANVAS_HIP_TRY(ctx, hipMemcpyAsync(segMed.data(), dSegMed, segs.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
             CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1900,6 +1977,16 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
         for (int v : bpOf[(size_t)c]) h_breakpoints[total++] = v;
     }
     h_bp_offset[nchr] = total;
+    {   // what the thresholds and the healing step were computed from (canvas_wavelets_inputs)
+        callInputs.hasCV = hasCV ? 1 : 0; callInputs.cv = cv;
+        callInputs.paths = (f3OnDevice ? 1 : 0) | (hasCV && varOnDevice ? 2 : 0) | (medOnDevice ? 4 : 0) | (medFromIntegers && !hBad[0] ? 8 : 0);
+        for (size_t i = 0; i < 9; i++) callInputs.f3[i] = i < f3.size() ? f3[i] : 0.0;
+        callInputs.isRoot.assign(isRoot.begin(), isRoot.end()); callInputs.median = chromMedian;
+        for (int c = 0; c < nchr; c++) if (!isRoot[(size_t)c]) callInputs.median[(size_t)c] = 0.0;      // (a call without any root launches no median kernel: the device array was never written)
+        callInputs.sigma.resize((size_t)nchr); callInputs.keepAbove.resize((size_t)nchr);
+        for (int c = 0; c < nchr; c++) { callInputs.sigma[(size_t)c] = trees[c].sigma; callInputs.keepAbove[(size_t)c] = trees[c].keepAbove; }
+        callInputs.valid = true;
+    }
     if (timing) fprintf(stderr, "canvas_wavelets: %.4f s from the entry to the host copy of the coverage\n", t0 - tEntry);
     if (timing) fprintf(stderr, "canvas_wavelets: variability %.3f s, decomposition %.3f s (%lld levels), thresholds/reconstruction/healing %.3f s\n", t1 - t0, t2 - t1, levels, now() - t2);
     return CANVAS_OK;
@@ -1913,5 +2000,348 @@ extern "C" int32_t canvas_wavelets_stats(canvas_ctx* ctx, int64_t* h_out2) {
 extern "C" int32_t canvas_wavelets_decisions(canvas_ctx* ctx, int64_t* h_out4) {
     if (!ctx || !h_out4) return CANVAS_ERR_INVALID;
     for (int i = 0; i < 4; i++) h_out4[i] = ctx->wv_stats[i];
+    return CANVAS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ probe entries: the kernels above on caller-supplied nodes (tests/test_wavelets_kernels_gpu.py)
+// Every entry enqueues the product's kernels through the launch sets canvas_wavelets uses (wv_prefix_enqueue, wv_list_init_launch + wv_level_launch, wv_long_pass, wv_subtree_launch,
+// wv_medians_enqueue); the only kernel of their own is k_wv_bound_probe, which stores what wv_bound_eval hands to k_wv_level.
+namespace {
+#define WV_PROBE_FAIL(ctx, who, what) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, std::string(who) + ": " + (what))
+int32_t probe_offsets(canvas_ctx* ctx, const char* who, int32_t nchr, const double* d_cov, const int64_t* h_off, int64_t& N) {
+    if (nchr < 1 || nchr > (1 << 20) || !d_cov || !h_off) WV_PROBE_FAIL(ctx, who, "bad arguments (1..2^20 chromosomes, coverage, offsets)");
+    if (h_off[0] != 0) WV_PROBE_FAIL(ctx, who, "the offsets start at 0");
+    for (int c = 0; c < nchr; c++) if (h_off[c + 1] < h_off[c]) WV_PROBE_FAIL(ctx, who, "the offsets decrease");
+    N = h_off[nchr];
+    if (N < 1 || N > 0x7FFFFFF0ll) WV_PROBE_FAIL(ctx, who, "bin count out of range");
+    return CANVAS_OK;
+}
+// a node (start, len) of chromosome chrom: at least two bins, inside its chromosome
+bool probe_node_ok(int32_t nchr, const int64_t* off, int64_t start, int64_t len, int64_t chrom) {
+    return chrom >= 0 && chrom < nchr && len >= 2 && start >= off[chrom] && start + len <= off[chrom + 1];
+}
+// (start, len) pairs that share no bin
+bool probe_disjoint(std::vector<std::pair<int64_t, int64_t>> v) {
+    std::sort(v.begin(), v.end());
+    for (size_t i = 1; i < v.size(); i++) if (v[i].first < v[i - 1].first + v[i - 1].second) return false;
+    return true;
+}
+struct PrefixBufs { long long* off; int32_t* tile0; uint32_t* K32; long long* agg; long long *P1, *P2; int* bad; };
+void prefix_size(WsSizer& sz, int64_t N, int nchr, bool sums) {
+    sz.take<long long>(nchr + 1); sz.take<int32_t>(nchr + 2); sz.take<uint32_t>((size_t)N); sz.take<long long>(2 * ((size_t)N / WV_PT + (size_t)nchr + 1)); sz.take<int>(4);
+    if (sums) { sz.take<long long>((size_t)N); sz.take<long long>((size_t)N); }
+}
+PrefixBufs prefix_carve(WsCarver& ws, int64_t N, int nchr, bool sums) {
+    PrefixBufs p; p.off = ws.take<long long>(nchr + 1); p.tile0 = ws.take<int32_t>(nchr + 2); p.K32 = ws.take<uint32_t>((size_t)N); p.agg = ws.take<long long>(2 * ((size_t)N / WV_PT + (size_t)nchr + 1)); p.bad = ws.take<int>(4);
+    p.P1 = sums ? ws.take<long long>((size_t)N) : nullptr; p.P2 = sums ? ws.take<long long>((size_t)N) : nullptr;
+    return p;
+}
+}  // namespace
+
+extern "C" int32_t canvas_wavelets_prefix_probe(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int64_t* h_p1, int64_t* h_p2, int32_t* h_bad2) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    const char* who = "canvas_wavelets_prefix_probe";
+    int64_t N = 0;
+    int32_t rc = probe_offsets(ctx, who, nchr, d_cov, h_chr_offset, N); if (rc) return rc;
+    if (!h_p1 || !h_p2 || !h_bad2) WV_PROBE_FAIL(ctx, who, "no room for the results");
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    WsSizer sz; prefix_size(sz, N, nchr, true);
+    rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    WsCarver ws(ctx->ws);
+    const PrefixBufs P = prefix_carve(ws, N, nchr, true);
+    rc = wv_prefix_enqueue(ctx, nchr, h_chr_offset, d_cov, P.off, P.tile0, P.K32, P.agg, P.P1, P.P2, P.bad); if (rc) return rc;
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(h_p1, P.P1, (size_t)N * 8, hipMemcpyDeviceToHost));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(h_p2, P.P2, (size_t)N * 8, hipMemcpyDeviceToHost));
+    int bad[2] = {0, 0};
+    CANVAS_HIP_TRY(ctx, hipMemcpy(bad, P.bad, sizeof bad, hipMemcpyDeviceToHost));
+    h_bad2[0] = bad[0]; h_bad2[1] = bad[1];
+    return CANVAS_OK;
+}
+
+extern "C" int32_t canvas_wavelets_bound_probe(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int32_t nnodes, const int32_t* h_nodes3, double* h_t, double* h_b) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    const char* who = "canvas_wavelets_bound_probe";
+    int64_t N = 0;
+    int32_t rc = probe_offsets(ctx, who, nchr, d_cov, h_chr_offset, N); if (rc) return rc;
+    if (nnodes < 1 || nnodes > (1 << 20) || !h_nodes3 || !h_t || !h_b) WV_PROBE_FAIL(ctx, who, "1..2^20 nodes and room for their results");
+    std::vector<WvDNode> nodes((size_t)nnodes); std::vector<long long> outOff((size_t)nnodes + 1, 0);
+    for (int i = 0; i < nnodes; i++) {
+        const int32_t* q = h_nodes3 + 3 * (size_t)i;
+        if (!probe_node_ok(nchr, h_chr_offset, q[0], q[1], q[2])) WV_PROBE_FAIL(ctx, who, "a node has fewer than two bins or leaves its chromosome");
+        nodes[(size_t)i] = WvDNode{q[0], q[1], q[2], 0}; outOff[(size_t)i + 1] = outOff[(size_t)i] + q[1] - 1;
+    }
+    const size_t total = (size_t)outOff[(size_t)nnodes];
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    WsSizer sz; prefix_size(sz, N, nchr, true); sz.take<WvDNode>(nnodes); sz.take<long long>(nnodes + 1); sz.take<double>(total); sz.take<double>(total);
+    rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    WsCarver ws(ctx->ws);
+    const PrefixBufs P = prefix_carve(ws, N, nchr, true);
+    WvDNode* dNodes = ws.take<WvDNode>(nnodes); long long* dOutOff = ws.take<long long>(nnodes + 1); double* dT = ws.take<double>(total); double* dB = ws.take<double>(total);
+    rc = wv_prefix_enqueue(ctx, nchr, h_chr_offset, d_cov, P.off, P.tile0, P.K32, P.agg, P.P1, P.P2, P.bad); if (rc) return rc;
+    int bad[2] = {1, 1};
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(bad, P.bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dNodes, nodes.data(), (size_t)nnodes * sizeof(WvDNode), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dOutOff, outOff.data(), ((size_t)nnodes + 1) * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad[0] || bad[1]) WV_PROBE_FAIL(ctx, who, "the coverage is not made of non-negative two-decimal values below 2e7 (no exact sums: canvas_wavelets takes the chains)");
+    hipLaunchKernelGGL(k_wv_bound_probe, dim3((unsigned)nnodes), dim3(256), 0, ctx->stream, dNodes, dOutOff, P.P1, P.P2, P.off, dT, dB);
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(h_t, dT, total * 8, hipMemcpyDeviceToHost));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(h_b, dB, total * 8, hipMemcpyDeviceToHost));
+    return CANVAS_OK;
+}
+
+extern "C" int32_t canvas_wavelets_level_probe(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int32_t nnodes, const int32_t* h_nodes4, const double* h_keep_above,
+                                               int32_t wv_long, int32_t* h_status, int32_t* h_ind, int32_t* h_next4, int64_t* h_nnext, int32_t* h_roots6, int64_t* h_nroots, int32_t* h_counts,
+                                               int32_t* h_overflow) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    const char* who = "canvas_wavelets_level_probe";
+    int64_t N = 0;
+    int32_t rc = probe_offsets(ctx, who, nchr, d_cov, h_chr_offset, N); if (rc) return rc;
+    if (nnodes < 1 || !h_nodes4 || !h_keep_above || !h_status || !h_ind || !h_next4 || !h_nnext || !h_roots6 || !h_nroots || !h_counts || !h_overflow) WV_PROBE_FAIL(ctx, who, "missing arrays");
+    if (wv_long < 8 || wv_long > WV_LONG_MAX) WV_PROBE_FAIL(ctx, who, "wv_long outside 8..256");
+    const WvCaps caps = wv_caps(N, nchr, wv_long);
+    // the list of iteration 0 must fit (k_wv_list_init deals node i to replica i % WV_REP): that part is exact.  What the level APPENDS (at most 2 nnodes children) is held to the
+    // share wv_caps itself assumes for a replica, twice the even one (2 nnodes / WV_REP x 2 = nnodes / 4): an assumption, as in canvas_wavelets, and no guarantee — which replica a
+    // child goes to depends on the chunk that arrives last, so a list that passes here could in principle still fill one.  k_wv_level checks every append against listCap / chCap /
+    // rootCap and sets dev->overflow, which the caller gets back; one level reads no entry of the lists it appends to.
+    std::vector<WvDNode> nodes((size_t)nnodes); std::vector<std::pair<int64_t, int64_t>> spans((size_t)nnodes);
+    size_t repNodes[WV_REP], repChunks[WV_REP], chunks = 0;
+    for (int r = 0; r < WV_REP; r++) repNodes[r] = repChunks[r] = 0;
+    for (int i = 0; i < nnodes; i++) {
+        const int32_t* q = h_nodes4 + 4 * (size_t)i;
+        if (!probe_node_ok(nchr, h_chr_offset, q[0], q[1], q[2])) WV_PROBE_FAIL(ctx, who, "a node has fewer than two bins or leaves its chromosome");
+        const int64_t L = h_chr_offset[q[2] + 1] - h_chr_offset[q[2]];
+        if (q[3] < 0 || q[3] + 1 >= L) WV_PROBE_FAIL(ctx, who, "a node's level and its children's must lie inside the chromosome's slice of the counters");
+        nodes[(size_t)i] = WvDNode{q[0], q[1], q[2], q[3]}; spans[(size_t)i] = {q[0], q[1]};
+        const size_t nch = (size_t)((q[1] - 1 + WV_CH - 1) / WV_CH);
+        repNodes[i % WV_REP]++; repChunks[i % WV_REP] += nch; chunks += nch;
+    }
+    if (!probe_disjoint(spans)) WV_PROBE_FAIL(ctx, who, "the nodes of a level share no bin");
+    for (int r = 0; r < WV_REP; r++) if (repNodes[r] > caps.listCap || repChunks[r] > caps.chCap) WV_PROBE_FAIL(ctx, who, "the node list does not fit the list / chunk capacity of a replica");
+    if ((size_t)nnodes > caps.maxLong || (size_t)nnodes > caps.maxList2 || (size_t)nnodes / 4 + 1 > caps.listCap || (chunks + 2 * (size_t)nnodes) / 8 + 1 > caps.chCap || (size_t)nnodes / 4 + 1 > caps.rootCap)
+        WV_PROBE_FAIL(ctx, who, "the node list (or what it can append) does not fit the capacities canvas_wavelets allocates for this coverage");
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nCn = (size_t)(WV_LB + 3) * WV_REP;
+    WsSizer sz; prefix_size(sz, N, nchr, true);
+    sz.take<WvSlot>(WV_REP * caps.listCap); sz.take<WvSlot>(WV_REP * caps.listCap); sz.take<int32_t>(WV_REP * caps.chCap); sz.take<int32_t>(WV_REP * caps.chCap); sz.take<WvPart>(WV_REP * caps.chCap);
+    sz.take<WvCn>(nCn); sz.take<WvDev>(1); sz.take<WvDNode>(caps.maxList2); sz.take<int32_t>(caps.maxList2); sz.take<WvDNode>(caps.maxList2); sz.take<WvRoot>(WV_REP * caps.rootCap);
+    sz.take<int32_t>((size_t)N); sz.take<double>(nchr); sz.take<WvDNode>(nnodes);
+    rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    WsCarver ws(ctx->ws);
+    const PrefixBufs P = prefix_carve(ws, N, nchr, true);
+    WvLevelBufs L;
+    L.listA = ws.take<WvSlot>(WV_REP * caps.listCap); L.listB = ws.take<WvSlot>(WV_REP * caps.listCap); L.chA = ws.take<int32_t>(WV_REP * caps.chCap); L.chB = ws.take<int32_t>(WV_REP * caps.chCap);
+    L.parts = ws.take<WvPart>(WV_REP * caps.chCap); L.cn = ws.take<WvCn>(nCn); L.rootCn = L.cn + (size_t)(WV_LB + 2) * WV_REP; L.dev = ws.take<WvDev>(1);
+    L.exact = ws.take<WvDNode>(caps.maxList2); L.exactInd = ws.take<int32_t>(caps.maxList2); L.undec = ws.take<WvDNode>(caps.maxList2); L.roots = ws.take<WvRoot>(WV_REP * caps.rootCap);
+    L.counts = ws.take<int32_t>((size_t)N); double* dKeep = ws.take<double>(nchr); WvDNode* dListIn = ws.take<WvDNode>(nnodes);
+    L.listCap = (unsigned)caps.listCap; L.chCap = (unsigned)caps.chCap; L.maxList2 = (unsigned)caps.maxList2; L.rootCap = (unsigned)caps.rootCap; L.P1 = P.P1; L.P2 = P.P2; L.off = P.off; L.keep = dKeep; L.wvLong = wv_long;
+    rc = wv_prefix_enqueue(ctx, nchr, h_chr_offset, d_cov, P.off, P.tile0, P.K32, P.agg, P.P1, P.P2, P.bad); if (rc) return rc;
+    int bad[2] = {1, 1};
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(bad, P.bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dKeep, h_keep_above, (size_t)nchr * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dListIn, nodes.data(), (size_t)nnodes * sizeof(WvDNode), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(L.counts, 0, (size_t)N * sizeof(int32_t), ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(L.dev, 0, sizeof(WvDev), ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(L.cn, 0, nCn * sizeof(WvCn), ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad[0] || bad[1]) WV_PROBE_FAIL(ctx, who, "the coverage is not made of non-negative two-decimal values below 2e7 (no exact sums: canvas_wavelets takes the chains)");
+    wv_list_init_launch(ctx->stream, L, dListIn, nnodes);
+    wv_level_launch(ctx->stream, L, 0);
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    WvDev hdev; std::vector<WvCn> hcn(2 * WV_REP), hroot(WV_REP);
+    CANVAS_HIP_TRY(ctx, hipMemcpy(&hdev, L.dev, sizeof hdev, hipMemcpyDeviceToHost));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(hcn.data(), L.cn, 2 * WV_REP * sizeof(WvCn), hipMemcpyDeviceToHost));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(hroot.data(), L.rootCn, WV_REP * sizeof(WvCn), hipMemcpyDeviceToHost));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(h_counts, L.counts, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *h_overflow = (int32_t)hdev.overflow;
+    // the next level's long nodes and the short roots, gathered over the replicas; every child by its first bin
+    std::map<int32_t, std::pair<int32_t, int32_t>> childAt;      // start -> (len, level)
+    int64_t nNext = 0, nRoots = 0;
+    std::vector<WvSlot> sl; std::vector<WvRoot> rt;
+    for (int r = 0; r < WV_REP; r++) {
+        const size_t k = std::min<size_t>((size_t)(hcn[WV_REP + r].cn & 0xFFFFFFFFull), caps.listCap);
+        sl.resize(k);
+        if (k) CANVAS_HIP_TRY(ctx, hipMemcpy(sl.data(), L.listB + (size_t)r * caps.listCap, k * sizeof(WvSlot), hipMemcpyDeviceToHost));
+        for (const WvSlot& s : sl) { int32_t* o = h_next4 + 4 * nNext++; o[0] = s.nd.start; o[1] = s.nd.len; o[2] = s.nd.chrom; o[3] = s.nd.level; childAt[s.nd.start] = {s.nd.len, s.nd.level}; }
+        const size_t kr = std::min<size_t>((size_t)hroot[r].cn, caps.rootCap);
+        rt.resize(kr);
+        if (kr) CANVAS_HIP_TRY(ctx, hipMemcpy(rt.data(), L.roots + (size_t)r * caps.rootCap, kr * sizeof(WvRoot), hipMemcpyDeviceToHost));
+        for (const WvRoot& q : rt) { int32_t* o = h_roots6 + 6 * nRoots++; o[0] = q.start; o[1] = q.len; o[2] = q.chrom; o[3] = q.level; o[4] = q.s1; o[5] = q.cbase; childAt[q.start] = {q.len, q.level}; }
+    }
+    *h_nnext = nNext; *h_nroots = nRoots;
+    // per input node: 0 undecided (the kernel's list), 1 decided and zeroed (its coefficient's bracket lies at or below keepAbove), 2 decided and listed for the exact chain.
+    // NOTE on h_ind: the kernel writes a decided arg-max (1-based) only for the nodes it lists for the chain (exactInd); for those h_ind is that value, and the children are checked
+    // against it below.  For a zeroed node the kernel leaves NO record of the arg-max but the children themselves, so h_ind is RECONSTRUCTED here: the length of the child of the
+    // next level that starts at the node's first bin, or 1 when there is none (a node split behind its first bin has no left child).  A caller that builds the expected children
+    // from h_ind therefore has to compare h_ind with an independent arg-max first.
+    std::map<int32_t, int> nodeAt;
+    for (int i = 0; i < nnodes; i++) { nodeAt[nodes[(size_t)i].start] = i; h_status[i] = 1; h_ind[i] = 0; }
+    const size_t nU = std::min<size_t>(hdev.nUndec, caps.maxList2), nE = std::min<size_t>(hdev.nExact, caps.maxList2);
+    std::vector<WvDNode> hU(nU), hE(nE); std::vector<int32_t> hEI(nE);
+    if (nU) CANVAS_HIP_TRY(ctx, hipMemcpy(hU.data(), L.undec, nU * sizeof(WvDNode), hipMemcpyDeviceToHost));
+    if (nE) { CANVAS_HIP_TRY(ctx, hipMemcpy(hE.data(), L.exact, nE * sizeof(WvDNode), hipMemcpyDeviceToHost)); CANVAS_HIP_TRY(ctx, hipMemcpy(hEI.data(), L.exactInd, nE * sizeof(int32_t), hipMemcpyDeviceToHost)); }
+    for (const WvDNode& u : hU) { auto it = nodeAt.find(u.start); if (it == nodeAt.end() || nodes[(size_t)it->second].len != u.len) CANVAS_FAIL(ctx, CANVAS_ERR_HIP, "canvas_wavelets_level_probe: an undecided node is none of the list's"); h_status[it->second] = 0; }
+    for (int i = 0; i < nnodes; i++) if (h_status[i]) {
+        auto it = childAt.find(nodes[(size_t)i].start);
+        h_ind[i] = (it != childAt.end() && it->second.second == nodes[(size_t)i].level + 1) ? it->second.first : 1;
+    }
+    for (size_t k = 0; k < nE; k++) {
+        auto it = nodeAt.find(hE[k].start);
+        if (it == nodeAt.end() || nodes[(size_t)it->second].len != hE[k].len || h_status[it->second] != 1) CANVAS_FAIL(ctx, CANVAS_ERR_HIP, "canvas_wavelets_level_probe: a node of the exact list is none of the list's decided ones");
+        h_status[it->second] = 2;
+        if (h_ind[it->second] != hEI[k]) CANVAS_FAIL(ctx, CANVAS_ERR_HIP, "canvas_wavelets_level_probe: a node's children do not lie where its listed arg-max puts them");
+    }
+    return CANVAS_OK;
+}
+
+extern "C" int32_t canvas_wavelets_chain_probe(canvas_ctx* ctx, int64_t n_cov, const double* d_cov, int32_t nnodes, const int32_t* h_nodes2, const int32_t* h_lim, int32_t fast, int32_t own_slices,
+                                               double* h_coef, int32_t* h_ind, int32_t* h_flag) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    const char* who = "canvas_wavelets_chain_probe";
+    if (n_cov < 2 || n_cov > 0x7FFFFFF0ll || !d_cov || nnodes < 1 || nnodes > (1 << 20) || !h_nodes2 || !h_coef || !h_ind || !h_flag) WV_PROBE_FAIL(ctx, who, "bad arguments");
+    std::vector<WvNode> nodes((size_t)nnodes); std::vector<int32_t> list((size_t)nnodes), base((size_t)nnodes + 1, 0); std::vector<long long> opsOff((size_t)nnodes);
+    std::vector<std::pair<int64_t, int64_t>> spans((size_t)nnodes);
+    long long o = 0;
+    for (int i = 0; i < nnodes; i++) {
+        const int64_t s = h_nodes2[2 * (size_t)i], len = h_nodes2[2 * (size_t)i + 1];
+        if (len < 2 || s < 0 || s + len > n_cov) WV_PROBE_FAIL(ctx, who, "a node has fewer than two bins or leaves the coverage");
+        if (h_lim && h_lim[i] < 0) WV_PROBE_FAIL(ctx, who, "a chain cannot stop before step 0");
+        nodes[(size_t)i] = WvNode{(int32_t)s, (int32_t)len}; list[(size_t)i] = i; spans[(size_t)i] = {s, len};
+        base[(size_t)i + 1] = base[(size_t)i] + wv_chunk_count((int32_t)len, h_lim ? h_lim + i : nullptr);
+        opsOff[(size_t)i] = o; o += len + 8;
+    }
+    if (!own_slices && !probe_disjoint(spans)) WV_PROBE_FAIL(ctx, who, "nodes that share bins need operand slices of their own");
+    const int nChunks = base[(size_t)nnodes];
+    const size_t opsCap = own_slices ? (size_t)o : (size_t)n_cov;
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    WsSizer sz; sz.take<WvOps>(opsCap); sz.take<WvNode>(nnodes); sz.take<WvOut>(nnodes); sz.take<int32_t>(nnodes); sz.take<int32_t>(nnodes + 1); sz.take<int32_t>(nnodes); sz.take<WvHead>(nnodes);
+    sz.take<WvCk>(nChunks + 1); sz.take<WvBest>(nChunks + 1); sz.take<long long>(nnodes); sz.take<int32_t>(nnodes);
+    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    WsCarver ws(ctx->ws);
+    WvOps* dOps = ws.take<WvOps>(opsCap);
+    LongBufs B; B.nodes = ws.take<WvNode>(nnodes); B.out = ws.take<WvOut>(nnodes); B.list = ws.take<int32_t>(nnodes); B.base = ws.take<int32_t>(nnodes + 1); B.flag = ws.take<int32_t>(nnodes); B.head = ws.take<WvHead>(nnodes);
+    B.ck = ws.take<WvCk>(nChunks + 1); B.best = ws.take<WvBest>(nChunks + 1);
+    long long* dOpsOff = ws.take<long long>(nnodes); int32_t* dLim = ws.take<int32_t>(nnodes);
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(B.nodes, nodes.data(), (size_t)nnodes * sizeof(WvNode), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(B.list, list.data(), (size_t)nnodes * 4, hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(B.base, base.data(), ((size_t)nnodes + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (own_slices) CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dOpsOff, opsOff.data(), (size_t)nnodes * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    if (h_lim) CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dLim, h_lim, (size_t)nnodes * 4, hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (the sources are the caller's and this function's own pageable arrays)
+    rc = wv_long_pass(ctx, ctx->stream, B, (size_t)nnodes, nChunks, fast != 0, d_cov, dOps, own_slices ? dOpsOff : nullptr, h_lim ? dLim : nullptr); if (rc) return rc;
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<WvOut> out((size_t)nnodes);
+    CANVAS_HIP_TRY(ctx, hipMemcpy(out.data(), B.out, (size_t)nnodes * sizeof(WvOut), hipMemcpyDeviceToHost));
+    for (int i = 0; i < nnodes; i++) { h_coef[i] = out[(size_t)i].coef; h_ind[i] = out[(size_t)i].ind; h_flag[i] = out[(size_t)i].flag; }
+    return CANVAS_OK;
+}
+
+extern "C" int32_t canvas_wavelets_subtree_probe(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int32_t nroots, const int32_t* h_roots6, const double* h_keep_above,
+                                                 int64_t cap_cand, int32_t wv_long, int32_t use_table, int32_t* h_counts, int32_t* h_cand5, double* h_cand_coef, int64_t* h_ncand, int32_t* h_overflow) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    const char* who = "canvas_wavelets_subtree_probe";
+    int64_t N = 0;
+    int32_t rc = probe_offsets(ctx, who, nchr, d_cov, h_chr_offset, N); if (rc) return rc;
+    if (nroots < 1 || nroots > (1 << 22) || !h_roots6 || !h_keep_above || cap_cand < 0 || cap_cand > N + 16 || !h_counts || (cap_cand && (!h_cand5 || !h_cand_coef)) || !h_ncand || !h_overflow) WV_PROBE_FAIL(ctx, who, "missing arrays, or a candidate capacity outside 0..N+16");
+    if (wv_long < 8 || wv_long > WV_LONG_MAX) WV_PROBE_FAIL(ctx, who, "wv_long outside 8..256");
+    std::vector<WvRoot> roots((size_t)nroots); std::vector<std::pair<int64_t, int64_t>> spans((size_t)nroots);
+    for (int i = 0; i < nroots; i++) {
+        const int32_t* q = h_roots6 + 6 * (size_t)i;
+        if (!probe_node_ok(nchr, h_chr_offset, q[0], q[1], q[2])) WV_PROBE_FAIL(ctx, who, "a root has fewer than two bins or leaves its chromosome");
+        if (q[1] > wv_long) WV_PROBE_FAIL(ctx, who, "a root longer than wv_long belongs to the level loop");
+        const int64_t cb = h_chr_offset[q[2]], L = h_chr_offset[q[2] + 1] - cb;
+        if (q[5] != cb || q[4] != q[0] - cb + 1) WV_PROBE_FAIL(ctx, who, "a root's cbase / s1 do not name its chromosome's first bin / its own place in it");
+        if (q[3] < 0 || (int64_t)q[3] + q[1] - 1 > L) WV_PROBE_FAIL(ctx, who, "the levels of a root's subtree must lie inside the chromosome's slice of the counters");
+        roots[(size_t)i] = WvRoot{q[0], q[1], q[2], q[3], q[4], q[5]}; spans[(size_t)i] = {q[0], q[1]};
+    }
+    if (!probe_disjoint(spans)) WV_PROBE_FAIL(ctx, who, "the roots share no bin (a walker keeps its stack in its own bins' slice)");
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = wv_fgh_ensure(ctx, wv_long); if (rc) return rc;
+    const size_t capAlloc = (size_t)std::max<int64_t>(cap_cand, 1);
+    WsSizer sz; sz.take<WvRoot>(nroots); sz.take<uint32_t>((size_t)N); sz.take<int32_t>((size_t)N); sz.take<WvCand>(capAlloc); sz.take<double>(nchr); sz.take<unsigned long long>(2);
+    rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    WsCarver ws(ctx->ws);
+    WvRoot* dRoots = ws.take<WvRoot>(nroots); uint32_t* dStack = ws.take<uint32_t>((size_t)N); int32_t* dCounts = ws.take<int32_t>((size_t)N); WvCand* dCands = ws.take<WvCand>(capAlloc);
+    double* dKeep = ws.take<double>(nchr); unsigned long long* dNcand = ws.take<unsigned long long>(2); int32_t* dOverflow = (int32_t*)(dNcand + 1);
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dRoots, roots.data(), (size_t)nroots * sizeof(WvRoot), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dKeep, h_keep_above, (size_t)nchr * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(dCounts, 0, (size_t)N * sizeof(int32_t), ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(dNcand, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const WvSubBufs S{dRoots, d_cov, dKeep, dStack, dCounts, dCands, dNcand, (unsigned long long)cap_cand, dOverflow, use_table ? (const WvFgh*)ctx->wv_fgh : nullptr, use_table ? wv_long : 0};
+    WvRootSegs sg; memset(&sg, 0, sizeof sg); sg.n = 1; sg.start[0] = 0; sg.count[0] = nroots;
+    wv_subtree_launch(ctx->stream, S, sg, (size_t)nroots);
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned long long hN[2] = {0, 0};
+    CANVAS_HIP_TRY(ctx, hipMemcpy(hN, dNcand, sizeof hN, hipMemcpyDeviceToHost));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(h_counts, dCounts, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *h_ncand = (int64_t)hN[0]; *h_overflow = (int32_t)(hN[1] & 0xFFFFFFFFull);
+    const size_t k = (size_t)std::min<unsigned long long>(hN[0], (unsigned long long)cap_cand);
+    std::vector<WvCand> hc(k);
+    if (k) CANVAS_HIP_TRY(ctx, hipMemcpy(hc.data(), dCands, k * sizeof(WvCand), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < k; i++) { int32_t* o = h_cand5 + 5 * i; o[0] = hc[i].chrom; o[1] = hc[i].level; o[2] = hc[i].s; o[3] = hc[i].b; o[4] = hc[i].e; h_cand_coef[i] = hc[i].coef; }
+    return CANVAS_OK;
+}
+
+extern "C" int32_t canvas_wavelets_median_probe(canvas_ctx* ctx, int64_t n_cov, const double* d_cov, int32_t nstretch, const int64_t* h_start, const int64_t* h_len, double* h_median, double* h_median_wg,
+                                                int32_t* h_bad2) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    const char* who = "canvas_wavelets_median_probe";
+    if (n_cov < 1 || n_cov > 0x7FFFFFF0ll || !d_cov || nstretch < 1 || !h_start || !h_len || !h_median || !h_bad2) WV_PROBE_FAIL(ctx, who, "bad arguments");
+    if (nstretch > WV_MED_MAXR) WV_PROBE_FAIL(ctx, who, "at most 1024 stretches per call");
+    std::vector<long long> st((size_t)nstretch), ln((size_t)nstretch); std::vector<unsigned long long> segs; std::vector<int> segOf;
+    for (int r = 0; r < nstretch; r++) {
+        if (h_start[r] < 0 || h_len[r] < 0 || h_start[r] + h_len[r] > n_cov) WV_PROBE_FAIL(ctx, who, "a stretch leaves the coverage");
+        st[(size_t)r] = h_start[r]; ln[(size_t)r] = h_len[r];
+        if (h_len[r] > 0) { segs.push_back(((unsigned long long)h_start[r] << 32) | (unsigned long long)h_len[r]); segOf.push_back(r); }      // (canvas_wavelets hands no empty stretch to the per-workgroup kernel either)
+    }
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t medR = WV_MED_MAXR;
+    WsSizer sz; prefix_size(sz, n_cov, 1, false); sz.take<long long>(medR); sz.take<long long>(medR); sz.take<int32_t>(medR + 2); sz.take<WvMedState>(medR); sz.take<uint32_t>(medR * 2 * WV_MD); sz.take<uint32_t>(medR);
+    sz.take<double>(medR); sz.take<unsigned long long>(medR); sz.take<double>(medR);
+    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    WsCarver ws(ctx->ws);
+    const PrefixBufs P = prefix_carve(ws, n_cov, 1, false);
+    WvMedBufs M; M.K32 = P.K32; M.start = ws.take<long long>(medR); M.len = ws.take<long long>(medR); M.tile0 = ws.take<int32_t>(medR + 2); M.state = ws.take<WvMedState>(medR); M.hist = ws.take<uint32_t>(medR * 2 * WV_MD); M.tick = ws.take<uint32_t>(medR);
+    double* dOut = ws.take<double>(medR); unsigned long long* dSegs = ws.take<unsigned long long>(medR); double* dOutWg = ws.take<double>(medR);
+    const int64_t off[2] = {0, n_cov};
+    rc = wv_prefix_enqueue(ctx, 1, off, d_cov, P.off, P.tile0, P.K32, P.agg, nullptr, nullptr, P.bad); if (rc) return rc;      // (the integers only: the medians need no sums)
+    CANVAS_HIP_TRY(ctx, hipMemsetAsync(dOut, 0, (size_t)nstretch * sizeof(double), ctx->stream));      // (wv_medians_enqueue launches nothing when every stretch is empty)
+    rc = wv_medians_enqueue(ctx, M, st, ln, dOut); if (rc) return rc;
+    if (h_median_wg && !segs.empty()) {
+        CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dSegs, segs.data(), segs.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        wv_segment_median_launch(ctx->stream, d_cov, dSegs, segs.size(), dOutWg);
+    }
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpy(h_median, dOut, (size_t)nstretch * sizeof(double), hipMemcpyDeviceToHost));
+    if (h_median_wg) {
+        std::vector<double> w(segs.size());
+        if (!segs.empty()) CANVAS_HIP_TRY(ctx, hipMemcpy(w.data(), dOutWg, segs.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int r = 0; r < nstretch; r++) h_median_wg[r] = 0.0;
+        for (size_t k = 0; k < segs.size(); k++) h_median_wg[segOf[k]] = w[k];
+    }
+    int bad[2] = {0, 0};
+    CANVAS_HIP_TRY(ctx, hipMemcpy(bad, P.bad, sizeof bad, hipMemcpyDeviceToHost));
+    h_bad2[0] = bad[0]; h_bad2[1] = bad[1];
+    return CANVAS_OK;
+}
+
+extern "C" int32_t canvas_wavelets_inputs(canvas_ctx* ctx, int32_t nchr, int32_t* h_has_cv, double* h_cv, double* h_f3_9, uint8_t* h_is_root, double* h_median, double* h_sigma, double* h_keep_above,
+                                          int32_t* h_paths) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    const wv::CallInputs* in = (const wv::CallInputs*)ctx->wv_inputs.get();
+    if (!in || !in->valid) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_wavelets_inputs: no completed canvas_wavelets call on this context");
+    if ((size_t)nchr != in->isRoot.size() || !h_has_cv || !h_cv || !h_f3_9 || !h_is_root || !h_median || !h_sigma || !h_keep_above || !h_paths) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_wavelets_inputs: nchr is the last call's, and every array is needed");
+    *h_has_cv = in->hasCV; *h_cv = in->cv; *h_paths = in->paths;
+    for (int i = 0; i < 9; i++) h_f3_9[i] = in->f3[i];
+    for (int c = 0; c < nchr; c++) { h_is_root[c] = in->isRoot[(size_t)c]; h_median[c] = in->median[(size_t)c]; h_sigma[c] = in->sigma[(size_t)c]; h_keep_above[c] = in->keepAbove[(size_t)c]; }
     return CANVAS_OK;
 }

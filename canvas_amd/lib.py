@@ -19,7 +19,7 @@ ABI_SYMBOLS = [
     "canvas_packed_plane_bytes", "canvas_pack_reference_host", "canvas_pack_hits_host", "canvas_pack_genome_device", "canvas_upload_packed_begin", "canvas_bin_sample_packed", "canvas_sample_pipeline_packed", "canvas_pack_hits2_host", "canvas_upload_packed2_begin",
     "canvas_mask_from_fasta", "canvas_mask_exclude_intervals", "canvas_screen_hits",
     "canvas_bin_rates", "canvas_bin_size_from_rates", "canvas_bin_count_upper_bound", "canvas_bin_genome", "canvas_bin_sample", "canvas_bin_sample_gcweighted", "canvas_bin_predefined", "canvas_bin_predefined_gcweighted",
-    "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_normalize_best_normal", "canvas_normalize_pca_reference", "canvas_sample_pipeline",
+    "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_wavelets_inputs", "canvas_wavelets_prefix_probe", "canvas_wavelets_bound_probe", "canvas_wavelets_level_probe", "canvas_wavelets_chain_probe", "canvas_wavelets_subtree_probe", "canvas_wavelets_median_probe", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_normalize_best_normal", "canvas_normalize_pca_reference", "canvas_sample_pipeline",
     "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads", "canvas_select_probe", "canvas_hmm_backbone_probe",
     "canvas_memcpy_h2d_async", "canvas_snv_count", "canvas_flag_unique_kmers", "canvas_fasta_case_from_mask",
     "canvas_smooth", "canvas_smooth_lengths", "canvas_smooth_plan",
@@ -889,6 +889,110 @@ class Canvas:
         out = np.zeros(2, np.int64)
         self._check(self.lib.canvas_wavelets_stats(self.ctx, _np_ptr(out)))
         return out
+
+    def wavelets_inputs(self, nchr):
+        """what the last wavelets() call computed its thresholds and its healing step from (canvas_wavelets_inputs): dict(has_cv, cv, f3 float64[9], and per chromosome
+        is_root, median, sigma, keep_above), and paths: which code computed them (f3_device, var_device, median_device, median_from_integers: the bits of *h_paths)"""
+        has = C.c_int32(0); cvv = C.c_double(0.0); f3 = np.zeros(9, np.float64); paths = C.c_int32(0)
+        root = np.zeros(nchr, np.uint8); med = np.zeros(nchr, np.float64); sig = np.zeros(nchr, np.float64); keep = np.zeros(nchr, np.float64)
+        self._check(self.lib.canvas_wavelets_inputs(self.ctx, C.c_int32(nchr), C.byref(has), C.byref(cvv), _np_ptr(f3), _np_ptr(root), _np_ptr(med), _np_ptr(sig), _np_ptr(keep), C.byref(paths)))
+        return dict(has_cv=bool(has.value), cv=cvv.value, f3=f3, is_root=root.astype(bool), median=med, sigma=sig, keep_above=keep,
+                    paths=dict(f3_device=bool(paths.value & 1), var_device=bool(paths.value & 2), median_device=bool(paths.value & 4), median_from_integers=bool(paths.value & 8)))
+
+    def _wv_probe_cov(self, cov, chr_offset=None):
+        """coverage (numpy float64, sent bit for bit) and offsets of the Wavelets probe entries -> (device tensor, int64 offsets)"""
+        cov = np.ascontiguousarray(cov)
+        if cov.dtype != np.float64 or cov.ndim != 1 or len(cov) < 1:
+            raise CanvasError("wavelets probe: a non-empty one-dimensional float64 coverage")
+        off = np.ascontiguousarray([0, len(cov)] if chr_offset is None else chr_offset, np.int64)
+        if len(off) < 2 or off[0] != 0 or off[-1] != len(cov) or (np.diff(off) < 0).any():
+            raise CanvasError("wavelets probe: the offsets start at 0, do not decrease and end at len(cov)")
+        dev = self.torch.from_numpy(cov.view(np.int64)).to(self.device)      # (the bits travel as integers: NaN payloads and -0.0 stay as they are)
+        self.torch.cuda.synchronize(self.device)      # the library runs on its own stream
+        return dev, off
+
+    @staticmethod
+    def _wv_rows(a, width, what):
+        a = np.ascontiguousarray(a, np.int32)
+        if a.ndim != 2 or a.shape[1] != width or len(a) < 1:
+            raise CanvasError(f"wavelets probe: {what} is an int32 array of shape (n >= 1, {width})")
+        return a
+
+    def wavelets_prefix_probe(self, cov, chr_offset):
+        """k_wv_prefix_tiles + k_wv_prefix_apply (canvas_wavelets_prefix_probe) -> (P1 int64[N], P2 int64[N], bad int32[2])"""
+        dev, off = self._wv_probe_cov(cov, chr_offset)
+        p1 = np.zeros(len(cov), np.int64); p2 = np.zeros(len(cov), np.int64); bad = np.zeros(2, np.int32)
+        self._check(self.lib.canvas_wavelets_prefix_probe(self.ctx, C.c_int32(len(off) - 1), C.c_void_p(dev.data_ptr()), _np_ptr(off), _np_ptr(p1), _np_ptr(p2), _np_ptr(bad)))
+        return p1, p2, bad
+
+    def wavelets_bound_probe(self, cov, chr_offset, nodes):
+        """the closed form T[m] and its error bound B[m] as k_wv_level evaluates them (canvas_wavelets_bound_probe).  nodes: int32 (n, 3) = start, len, chromosome ->
+        (list of T arrays, list of B arrays), len - 1 values per node, in units of 100 x"""
+        dev, off = self._wv_probe_cov(cov, chr_offset)
+        nodes = self._wv_rows(nodes, 3, "nodes")
+        total = int(np.maximum(nodes[:, 1].astype(np.int64) - 1, 0).sum())
+        t = np.zeros(max(total, 1), np.float64); b = np.zeros(max(total, 1), np.float64)
+        self._check(self.lib.canvas_wavelets_bound_probe(self.ctx, C.c_int32(len(off) - 1), C.c_void_p(dev.data_ptr()), _np_ptr(off), C.c_int32(len(nodes)), _np_ptr(nodes), _np_ptr(t), _np_ptr(b)))
+        cut = np.cumsum(nodes[:, 1].astype(np.int64) - 1)[:-1]
+        return np.split(t[:total], cut), np.split(b[:total], cut)
+
+    def wavelets_level_probe(self, cov, chr_offset, nodes, keep_above, wv_long=64):
+        """k_wv_list_init + one k_wv_level (canvas_wavelets_level_probe).  nodes: int32 (n, 4) = start, len, chromosome, level -> dict(status int32[n] (0 undecided, 1 decided and
+        zeroed, 2 decided and listed for the exact chain), ind int32[n] (the kernel's own for status 2; for status 1 reconstructed by the entry from the children: canvas_hip.h), next int32 (k, 4), roots int32 (r, 6), counts int32[N], overflow)"""
+        dev, off = self._wv_probe_cov(cov, chr_offset)
+        nodes = self._wv_rows(nodes, 4, "nodes")
+        keep = np.ascontiguousarray(keep_above, np.float64)
+        if len(keep) != len(off) - 1:
+            raise CanvasError("wavelets_level_probe: one keep_above per chromosome")
+        n = len(nodes)
+        status = np.zeros(n, np.int32); ind = np.zeros(n, np.int32); nxt = np.zeros((2 * n, 4), np.int32); roots = np.zeros((2 * n, 6), np.int32); counts = np.zeros(len(cov), np.int32)
+        nn = C.c_int64(0); nr = C.c_int64(0); ov = C.c_int32(0)
+        self._check(self.lib.canvas_wavelets_level_probe(self.ctx, C.c_int32(len(off) - 1), C.c_void_p(dev.data_ptr()), _np_ptr(off), C.c_int32(n), _np_ptr(nodes), _np_ptr(keep), C.c_int32(wv_long),
+                                                         _np_ptr(status), _np_ptr(ind), _np_ptr(nxt), C.byref(nn), _np_ptr(roots), C.byref(nr), _np_ptr(counts), C.byref(ov)))
+        return dict(status=status, ind=ind, next=nxt[:nn.value].copy(), roots=roots[:nr.value].copy(), counts=counts, overflow=ov.value)
+
+    def wavelets_chain_probe(self, cov, nodes, lim=None, fast=True, own_slices=False):
+        """k_wv_coeff, k_wv_chain_long, k_wv_chunks, k_wv_reduce (canvas_wavelets_chain_probe).  nodes: int32 (n, 2) = start, len; lim: int32[n] or None ->
+        (coef float64[n], ind int32[n], flag int32[n])"""
+        dev, _ = self._wv_probe_cov(cov)
+        nodes = self._wv_rows(nodes, 2, "nodes")
+        n = len(nodes)
+        if lim is not None:
+            lim = np.ascontiguousarray(lim, np.int32)
+            if lim.shape != (n,):
+                raise CanvasError("wavelets_chain_probe: one lim per node")
+        coef = np.zeros(n, np.float64); ind = np.zeros(n, np.int32); flag = np.zeros(n, np.int32)
+        self._check(self.lib.canvas_wavelets_chain_probe(self.ctx, C.c_int64(len(cov)), C.c_void_p(dev.data_ptr()), C.c_int32(n), _np_ptr(nodes), None if lim is None else _np_ptr(lim),
+                                                         C.c_int32(int(bool(fast))), C.c_int32(int(bool(own_slices))), _np_ptr(coef), _np_ptr(ind), _np_ptr(flag)))
+        return coef, ind, flag
+
+    def wavelets_subtree_probe(self, cov, chr_offset, roots, keep_above, cap_cand, wv_long=64, use_table=True):
+        """k_wv_fgh_table + k_wv_subtree (canvas_wavelets_subtree_probe).  roots: int32 (n, 6) = start, len, chromosome, level, s1, cbase -> dict(counts int32[N], cand int32 (k, 5) =
+        chromosome, level, s, b, e, coef float64[k], ncand (found; k = min(ncand, cap_cand) were written), overflow)"""
+        dev, off = self._wv_probe_cov(cov, chr_offset)
+        roots = self._wv_rows(roots, 6, "roots")
+        keep = np.ascontiguousarray(keep_above, np.float64)
+        if len(keep) != len(off) - 1:
+            raise CanvasError("wavelets_subtree_probe: one keep_above per chromosome")
+        cap = int(cap_cand)
+        counts = np.zeros(len(cov), np.int32); cand = np.zeros((max(cap, 1), 5), np.int32); coef = np.zeros(max(cap, 1), np.float64)
+        nc = C.c_int64(0); ov = C.c_int32(0)
+        self._check(self.lib.canvas_wavelets_subtree_probe(self.ctx, C.c_int32(len(off) - 1), C.c_void_p(dev.data_ptr()), _np_ptr(off), C.c_int32(len(roots)), _np_ptr(roots), _np_ptr(keep), C.c_int64(cap),
+                                                           C.c_int32(wv_long), C.c_int32(int(bool(use_table))), _np_ptr(counts), _np_ptr(cand), _np_ptr(coef), C.byref(nc), C.byref(ov)))
+        k = min(nc.value, max(cap, 0))
+        return dict(counts=counts, cand=cand[:k].copy(), coef=coef[:k].copy(), ncand=nc.value, overflow=ov.value)
+
+    def wavelets_median_probe(self, cov, start, length, per_workgroup=False):
+        """medians of up to 1024 stretches through k_wv_prefix_tiles + three k_wv_rmed_pass launches (canvas_wavelets_median_probe) -> (median float64[n], the same through
+        k_wv_segment_median or None, bad int32[2])"""
+        dev, _ = self._wv_probe_cov(cov)
+        st = np.ascontiguousarray(start, np.int64); ln = np.ascontiguousarray(length, np.int64)
+        if st.ndim != 1 or st.shape != ln.shape:
+            raise CanvasError("wavelets_median_probe: one (start, length) per stretch")
+        med = np.zeros(max(len(st), 1), np.float64); wg = np.zeros(max(len(st), 1), np.float64) if per_workgroup else None; bad = np.zeros(2, np.int32)
+        self._check(self.lib.canvas_wavelets_median_probe(self.ctx, C.c_int64(len(cov)), C.c_void_p(dev.data_ptr()), C.c_int32(len(st)), _np_ptr(st), _np_ptr(ln), _np_ptr(med),
+                                                          None if wg is None else _np_ptr(wg), _np_ptr(bad)))
+        return med[:len(st)], (None if wg is None else wg[:len(st)]), bad
 
 
 # ---- synthetic generator (bench/test tooling, separate library)

@@ -359,6 +359,55 @@ int32_t canvas_wavelets_stats(canvas_ctx* ctx, int64_t* h_out2);
    [1] long nodes the bound could not decide (exact chain), [2] long nodes chained for their coefficient (candidates to survive HardThresh, WaveletSegmentation.cs:73-117),
    [3] 1 if the closed form was in use (coverage of non-negative two-decimal values) */
 int32_t canvas_wavelets_decisions(canvas_ctx* ctx, int64_t* h_out4);
+/* last completed canvas_wavelets call (nchr must be that call's): what its thresholds and its healing step were computed from, as the call itself held them — nothing is
+ * computed or waited for here.  *h_has_cv: 1 when the coverage variability was used (at least ten windows of bins), *h_cv: SegmentationInput.GetCoverageVariability
+ * (Segmentation.cs:308-328; NaN when most windows have median 0), h_f3_9: FactorOfThreeCoverageVariabilities (Segmentation.cs:366-429), and per chromosome h_is_root (longer than
+ * min_size, and selected by the mask of the sharded call), h_median (0 for the others), h_sigma = mad_factor x median x cv clamped to [threshold_lower, threshold_upper]
+ * (WaveletSegmentation.cs:394-405) and h_keep_above, the bracket below which the device drops a coefficient (-1 for a NaN threshold).  CANVAS_ERR_INVALID before the first
+ * completed call and for another nchr.  *h_paths: which code computed them, bit 0 the factor-of-three values on the device (clear: the host thread, CANVAS_WV_F3_HOST), bit 1 the
+ * window statistics of cv on the device (clear: host threads, CANVAS_WV_VAR_HOST, or no cv), bit 2 the chromosome medians on the device (clear: host threads), bit 3 those from the
+ * integers by the multi-stretch kernels (clear with bit 2 set: one workgroup per chromosome, CANVAS_WV_MEDIAN_PER_WG or a coverage without two-decimal values).
+ * tests/test_wavelets_kernels_gpu.py compares them with the oracle's. */
+int32_t canvas_wavelets_inputs(canvas_ctx* ctx, int32_t nchr, int32_t* h_has_cv, double* h_cv, double* h_f3_9, uint8_t* h_is_root, double* h_median, double* h_sigma, double* h_keep_above,
+                               int32_t* h_paths);
+/* Diagnostic / test entries: the kernels of canvas_wavelets (csrc/wavelets.hip) on caller-supplied nodes, through the launch sets the call itself uses (same kernels, same grids).
+ * d_cov (device) holds the coverage; h_chr_offset[nchr + 1] (host) starts at 0 and does not decrease, 1 .. 2^31 - 16 bins.  Nodes are (start, len) into the whole coverage with
+ * len >= 2, inside their chromosome.  wv_long (8..256) and the table switch are arguments here (the call reads CANVAS_WV_LONG / CANVAS_WV_NO_TABLE once per process).
+ * CANVAS_ERR_INVALID for anything outside these rules.  No reference counterpart; tests/test_wavelets_kernels_gpu.py compares every result with tests/wavelets_ref.py.
+ *
+ * prefix: k_wv_prefix_tiles + k_wv_prefix_apply.  h_p1[i] = sum of the integers 100 x of the chromosome's bins up to i, h_p2[i] = sum of its h_p1 up to i; h_bad2[0] != 0: some bin
+ * is not a non-negative two-decimal value below 2e7, or a chromosome's sums could pass 2^61 (canvas_wavelets then takes the chains); h_bad2[1] != 0: NaN or infinite. */
+int32_t canvas_wavelets_prefix_probe(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int64_t* h_p1, int64_t* h_p2, int32_t* h_bad2);
+/* bound: for node i = (start, len, chromosome) of h_nodes3 and every m = 0 .. len-2, the closed form T[m] and its rounding-error bound B[m] (in units of 100 x) exactly as
+ * k_wv_level's inner loop evaluates them (the same device function), concatenated node by node: sum of (len - 1) doubles in h_t and in h_b.  Refuses a coverage with a bad word. */
+int32_t canvas_wavelets_bound_probe(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int32_t nnodes, const int32_t* h_nodes3, double* h_t, double* h_b);
+/* level: k_wv_list_init and ONE k_wv_level (iteration 0, the call's grid) over the nodes (start, len, chromosome, level) of h_nodes4, which share no bin.  h_status[i]: 0 the bound
+ * could not decide the node, 1 decided and its coefficient's bracket lies at or below h_keep_above[chromosome] (HardThresh zeroes it), 2 decided and listed for the exact chain;
+ * h_ind[i]: the decided arg-max (1-based; 0 for status 0) — the kernel's own record for status 2; for status 1 the kernel keeps none, and the entry RECONSTRUCTS it from the
+ * children it appended (the length of the child at the node's first bin, 1 without one): compare it with an independent arg-max before deriving children from it.  h_next4 / *h_nnext: the next level's long nodes (len > wv_long) gathered over the replicas, h_roots6 / *h_nroots: the
+ * short children as the subtree walker takes them (start, len, chromosome, level, s1 = 1-based start inside the chromosome, cbase = the chromosome's first bin); both need room for
+ * 2 nnodes entries.  h_counts[bins]: the node counters, entry (chromosome's first bin + level).  *h_overflow: the device's overflow word.  Refuses a coverage with a bad word and a
+ * list that does not fit the capacities canvas_wavelets allocates for this coverage and wv_long (per replica for the list itself; an eighth of the level's worst case per replica for
+ * what it appends, as the call assumes — an assumption, not a guarantee: the kernel checks every append against its capacity and reports a full replica in *h_overflow). */
+int32_t canvas_wavelets_level_probe(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int32_t nnodes, const int32_t* h_nodes4, const double* h_keep_above,
+                                    int32_t wv_long, int32_t* h_status, int32_t* h_ind, int32_t* h_next4, int64_t* h_nnext, int32_t* h_roots6, int64_t* h_nroots, int32_t* h_counts,
+                                    int32_t* h_overflow);
+/* chain: k_wv_coeff, k_wv_chain_long (fast != 0: the shortcut division, else IEEE), k_wv_chunks and k_wv_reduce over the nodes (start, len) of h_nodes2 in a coverage of n_cov bins.
+ * h_lim (optional, >= 0): the chain of node i stops after step h_lim[i].  own_slices != 0: every node gets an operand slice of its own (needed when nodes share bins).  Per node:
+ * h_coef = ipi[ind - 1] / max(0.5, mean / 200), h_ind = GetInnerProdMax (1-based), h_flag != 0: a checkpoint of the shortcut chain was not reproduced (canvas_wavelets redoes such
+ * a node with IEEE divisions). */
+int32_t canvas_wavelets_chain_probe(canvas_ctx* ctx, int64_t n_cov, const double* d_cov, int32_t nnodes, const int32_t* h_nodes2, const int32_t* h_lim, int32_t fast, int32_t own_slices,
+                                    double* h_coef, int32_t* h_ind, int32_t* h_flag);
+/* subtree: k_wv_fgh_table (use_table != 0) and k_wv_subtree over the roots (start, len <= wv_long, chromosome, level, s1, cbase) of h_roots6, which share no bin.  h_counts[bins] as
+ * above; *h_ncand: coefficients above h_keep_above[chromosome] the walkers found, of which the first min(*h_ncand, cap_cand) are in h_cand5 (chromosome, level, s, b, e: 1-based
+ * inside the chromosome) and h_cand_coef, in no particular order; *h_overflow != 0: there were more than cap_cand (0 <= cap_cand <= bins + 16). */
+int32_t canvas_wavelets_subtree_probe(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int32_t nroots, const int32_t* h_roots6, const double* h_keep_above,
+                                      int64_t cap_cand, int32_t wv_long, int32_t use_table, int32_t* h_counts, int32_t* h_cand5, double* h_cand_coef, int64_t* h_ncand, int32_t* h_overflow);
+/* medians: Utilities.Median (Utilities.cs:428-443) of up to 1024 stretches (start, len >= 0; 0 for an empty one) from the integers of k_wv_prefix_tiles through the three
+ * k_wv_rmed_pass launches -> h_median; h_median_wg (optional): the same stretches through k_wv_segment_median, one workgroup per stretch over the doubles.  h_bad2 as for prefix
+ * (with a bad word the integers, and h_median, mean nothing). */
+int32_t canvas_wavelets_median_probe(canvas_ctx* ctx, int64_t n_cov, const double* d_cov, int32_t nstretch, const int64_t* h_start, const int64_t* h_len, double* h_median, double* h_median_wg,
+                                     int32_t* h_bad2);
 
 /* ---- one sample through the whole path in one call -------------------------------------------------------------
  * canvas_bin_sample -> canvas_clean2 -> canvas_quantize_f2 -> canvas_chromosome_offsets -> canvas_hmm_per_sample -> canvas_segment_ids with

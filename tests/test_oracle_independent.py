@@ -825,27 +825,7 @@ def test_predefined_bins_gc_content_weighted_two_restatements():
 # (RefineSegments), :385-425 (HaarWavelets).  The reference's own known-answer test pins the non-germline flavour on one vector
 # (tests/test_oracle_golden.py); this second reading runs both flavours on many.  Germline's Array.Sort with a comparison is restated as
 # .NET Core's introsort (insertion sort up to 16 elements, median-of-three partition above; a case that would reach its heapsort is skipped).
-def _inner_products(x):
-    n = len(x)
-    plus = [0.0] * (n - 1); minus = [0.0] * (n - 1)
-    plus[0] = math.sqrt(1 - 1.0 / n) * x[0]
-    rest = 0.0
-    for v in x[1:]:
-        rest += v
-    mean = (x[0] + rest) / n
-    minus[0] = (1.0 / math.sqrt(n * (n - 1))) * rest
-    for m in range(1, n - 1):
-        factor = math.sqrt(float(n - m - 1) * m / float(m + 1) / float(n - m))
-        plus[m] = plus[m - 1] * factor + x[m] * math.sqrt(1.0 / (m + 1) - 1.0 / n)
-        minus[m] = minus[m - 1] / factor - x[m] / math.sqrt((float(n) * n / float(m + 1)) - float(n))
-    return [p - q for p, q in zip(plus, minus)], mean
-
-
-def _first_largest(ipi):
-    top = max(abs(v) for v in ipi)
-    for k, v in enumerate(ipi):
-        if abs(v) == top:
-            return k + 1
+from wavelets_ref import inner_products as _inner_products, first_argmax as _first_largest      # (shared with the direct kernel tests: tests/wavelets_ref.py)
 
 
 class _NeedsHeapsort(Exception):
@@ -904,8 +884,8 @@ def _dotnet_sort(keys, compare):
     intro(0, n - 1, 2 * depth)
 
 
-def py_haar_wavelets(x, thr_lower, thr_upper, germline, mad_factor, cv, factor_of_three):
-    x = [float(v) for v in x]
+def py_haar_tree(x):
+    """FindBestUnbalancedHaarDecomposition: levels of nodes [index, coefficient, start, split, end], positions 1-based"""
     n = len(x)
     ipi, mean = _inner_products(x)
     k = _first_largest(ipi)
@@ -922,6 +902,13 @@ def py_haar_wavelets(x, thr_lower, thr_upper, germline, mad_factor, cv, factor_o
                 k = _first_largest(ipi)
                 level.append([2 * index, ipi[k - 1] / max(0.5, mean / 200.0), split + 1, k + split, end])
         tree.append(level)
+    return tree
+
+
+def py_haar_wavelets(x, thr_lower, thr_upper, germline, mad_factor, cv, factor_of_three):
+    x = [float(v) for v in x]
+    n = len(x)
+    tree = py_haar_tree(x)
     smooth = 0.0
     for v in x:
         smooth += v

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from gpu_common import get_canvas, to_dev
+from gpu_common import get_canvas, to_dev, wavelets_coverage as _coverage
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -17,16 +17,6 @@ def _run(cv, per_chr, **kw):
     cov = np.ascontiguousarray(np.concatenate(per_chr), np.float64)
     off = np.concatenate([[0], np.cumsum([len(a) for a in per_chr])]).astype(np.int64)
     return cv.wavelets(to_dev(cov, cv.device), off, **kw)
-
-
-def _coverage(rng, n, mean=100.0, events=6, wave=0.0):
-    x = rng.poisson(mean, n).astype(np.float64)
-    for _ in range(events if n > 40 else 0):
-        a = int(rng.randint(0, n - 20)); b = min(n, a + int(rng.choice([12, 40, 300, 2500, n // 4 + 1])))
-        x[a:b] = np.round(x[a:b] * float(rng.choice([0.0, 0.5, 1.5, 2.0])))
-    if wave:
-        x = np.round(x * (1 + wave * np.sin(np.arange(n) / 700.0)))
-    return np.round(x * 100) / 100      # what the cleaned file holds: F2 text
 
 
 def test_reference_known_answer_on_device():
