@@ -168,7 +168,8 @@ __global__ void __launch_bounds__(ARC_THREADS) k_arc_search(const ArcReq* __rest
 #define AP_PAIRCAP 8192
 struct ArcPReq { const double* sx; int n; int al0; double tau; double* bmin; double* bmax; int* pairs; unsigned long long* out /* [0] max key, [1] count, [2] min packed arc, [3] npairs, [4] overflow, [5] best block-extreme arc (bits) */; double* pairMax;
                  int* bpos /* [2 nb]: position of every block's first minimum / first maximum */;
-                 unsigned long long* hOut /* pinned host: out[0..4] of the finished search */; unsigned* hSeq /* pinned host: the mailbox's sequence word */; unsigned seq; };
+                 unsigned long long* hOut /* pinned host: out[0..4] of the finished search */; unsigned* hSeq /* pinned host: the mailbox's sequence word */; unsigned seq;
+                 int pairCap /* pairs the list may hold: AP_PAIRCAP (the arrays are sized for it); canvas_cbs_arc_probe lowers it to reach the overflow branch */; };
 __global__ void __launch_bounds__(256) k_arcp_blocks(const ArcPReq* __restrict__ reqs) {
     const ArcPReq R = reqs[blockIdx.y];
     const int nb = (R.n + AP_BK - 1) / AP_BK;
@@ -239,7 +240,7 @@ __global__ void __launch_bounds__(256) k_arcp_bounds(const ArcPReq* __restrict__
     const double rn = (double)R.n, c1 = arc_c(rn, llo), c2 = arc_c(rn, lhi), c = c1 > c2 ? c1 : c2;
     if (c * (D * D) >= tau) {
         const unsigned long long slot = atomicAdd(&R.out[3], 1ull);
-        if (slot < AP_PAIRCAP) R.pairs[slot] = A * 65536 + B; else R.out[4] = 1ull;
+        if (slot < (unsigned long long)R.pairCap) R.pairs[slot] = A * 65536 + B; else R.out[4] = 1ull;
     }
 }
 // pass 0: maximum over the arcs of a surviving block pair; pass 1: count of the arcs that attain the global maximum + the smallest (L, i)
@@ -252,7 +253,7 @@ __global__ void __launch_bounds__(256) k_arcp_bounds(const ArcPReq* __restrict__
 #define AP_NSUB (AP_BK / AP_SUB)
 __global__ void __launch_bounds__(256) k_arcp_eval(const ArcPReq* __restrict__ reqs, int pass) {
     const ArcPReq R = reqs[blockIdx.y];
-    unsigned long long np = R.out[3]; if (np > AP_PAIRCAP) np = AP_PAIRCAP;
+    unsigned long long np = R.out[3]; if (np > (unsigned long long)R.pairCap) np = (unsigned long long)R.pairCap;
     if (R.out[4]) return;
     __shared__ double sA[AP_BK], sB[AP_BK], sC[2 * AP_BK];
     __shared__ double sMn[2][AP_NSUB], sMx[2][AP_NSUB];
@@ -1869,53 +1870,63 @@ struct ArcGpu {       // one per chromosome thread: own buffers; the launches go
                 if (dMax) { (void)hipFree(dMax); (void)hipFree(dFirst); (void)hipHostFree(pinEx); } }
 };
 
-// TMaxO with the O(n^2) search on the GPU.  Returns false when the caller must fall back to the host replay (ambiguous maximum).
-static int32_t tmaxo_gpu(ArcGpu& G, const double* x, int n, double tss, double* sx, int iseg[2], double& ostat, int al0, Stats& st, bool& ok) {
-    // sequential prefix sums and the initial incumbent exactly as the reference builds them (block structure does not change sx)
-    Blocks B; build_blocks(x, n, sx, B);
+// TMaxO with the O(n^2) search on the GPU, in steps: arc_begin builds the request, a launch runs it (service_submit_arc, or canvas_cbs_arc_probe's own shared launch),
+// arc_end_pruned / arc_end_exhaustive decide.  path: what decided (canvas_hip.h, canvas_cbs_arc_probe): 0 no launch, 1 incumbent kept, 2 unique maximiser accepted,
+// 3 several arcs attain the maximum, 4 unique maximiser that the reference does not scan; 3 and 4 send the caller to the host replay.
+struct ArcJob { Blocks B; ArcHostReq q; double bss0 = 0; int ti = 0, tj = 0; int path = 0; bool overflow = false; };
+enum { ARC_DECIDED = 0, ARC_REPLAY = 1, ARC_OVERFLOW = 2 };
+// sequential prefix sums and the initial incumbent exactly as the reference builds them (block structure does not change sx); launch = false: psdiff <= 0, the answer is there
+static int32_t arc_begin(ArcGpu& G, const double* x, int n, double tss, double* sx, int iseg[2], double& ostat, int al0, bool pruned, int pairCap, ArcJob& J, bool& launch) {
+    Blocks& B = J.B; build_blocks(x, n, sx, B);
     double rn = (double)n, psdiff = B.psmax0 - B.psmin0, rj0 = (double)std::abs(B.ipsmax0 - B.ipsmin0);
-    double bss0 = (rn / (rj0 * (rn - rj0))) * sq(psdiff);
-    int ti = std::min(B.ipsmax0, B.ipsmin0), tj = std::max(B.ipsmax0, B.ipsmin0);
-    ok = true;
-    if (psdiff <= 0) { ostat = normalise(0.0, tss, rn); iseg[0] = ti; iseg[1] = tj; return CANVAS_OK; }
+    J.bss0 = (rn / (rj0 * (rn - rj0))) * sq(psdiff);
+    J.ti = std::min(B.ipsmax0, B.ipsmin0); J.tj = std::max(B.ipsmax0, B.ipsmin0);
+    launch = false; J.path = 0;
+    if (psdiff <= 0) { J.bss0 = 0.0; ostat = normalise(0.0, tss, rn); iseg[0] = J.ti; iseg[1] = J.tj; return CANVAS_OK; }
     canvas_ctx* ctx = G.ctx;
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int32_t rc = G.ensure(n); if (rc) return rc;
-    double* hSx = (double*)G.pin; double* hMax = nullptr; int32_t* hFirst = nullptr; unsigned long long* hOut = (unsigned long long*)(G.pin + (size_t)G.pinCap * 8);
+    double* hSx = (double*)G.pin; unsigned long long* hOut = (unsigned long long*)(G.pin + (size_t)G.pinCap * 8);
     // a host that makes ONE call and exits (canvas_set_one_shot: the CanvasPartition executable) uploads the prefix sums from the caller's pageable array: the pinned staging
     // buffers of fifty engines are ~100 MB that such a process pins at 1.4 ms per MB and unpins again when it leaves; a host that keeps its context (warm calls: 0.046 against
     // 0.056 s for the germline sample) keeps the staging buffers
     if (G.pageable()) { hSx = sx; hOut = (unsigned long long*)G.pinSmall; }
     else memcpy(hSx, sx, (size_t)n * 8);
     const size_t nbk = (size_t)G.cap / AP_BK + 2;
-    ArcHostReq q; q.hSx = hSx; q.hMax = hMax; q.hFirst = hFirst; q.hOut = hOut;
+    ArcHostReq& q = J.q; q.hSx = hSx; q.hMax = nullptr; q.hFirst = nullptr; q.hOut = hOut;
     q.r.sx = G.dSx; q.r.n = n; q.r.dmax = G.dMax; q.r.firstI = G.dFirst;
-    q.p.sx = G.dSx; q.p.n = n; q.p.al0 = al0; q.p.tau = bss0; q.p.bmin = (double*)G.dPr; q.p.bmax = q.p.bmin + nbk; q.p.pairs = (int*)(q.p.bmax + nbk);
+    q.p.sx = G.dSx; q.p.n = n; q.p.al0 = al0; q.p.tau = J.bss0; q.p.bmin = (double*)G.dPr; q.p.bmax = q.p.bmin + nbk; q.p.pairs = (int*)(q.p.bmax + nbk);
     q.p.pairMax = (double*)(q.p.pairs + AP_PAIRCAP); q.p.out = (unsigned long long*)(q.p.pairMax + AP_PAIRCAP); q.p.bpos = (int*)(q.p.out + 8);
-    q.pruned = cvx_hook("CANVAS_CBS_EXHAUSTIVE_ARCS") == nullptr;
-    if (q.pruned) {
-        rc = service_submit_arc(G.svc, q); if (rc) return rc;
-        st.gpu_searches++;
-        if (!hOut[4]) {
-            st.gpu_pairs += (long long)hOut[3] * AP_BK * AP_BK;
-            const double M = hOut[3] ? __builtin_bit_cast(double, hOut[0]) : -1.0;
-            if (!(M > bss0)) { ostat = normalise(bss0, tss, rn); iseg[0] = ti; iseg[1] = tj; return CANVAS_OK; }   // the incumbent survives every strict '>' test
-            if (hOut[1] == 1) {
-                const int L = (int)(hOut[2] >> 32), i0 = (int)(hOut[2] & 0xffffffffull);
-                if (ref_scans_arc(B, n, al0, i0 + 1, L)) { ostat = normalise(M, tss, rn); iseg[0] = i0 + 1; iseg[1] = i0 + 1 + L; return CANVAS_OK; }
-                st.unscanned_max++;      // the best admissible arc is one the reference does not look at: its own (smaller) maximum comes from the host replay
-            }
-            ok = false;       // several arcs attain the maximum: the winner depends on the reference's block visiting order
-            return CANVAS_OK;
-        }
-        q.pruned = false;     // too many candidate block pairs (flat data): exhaustive search
+    q.p.pairCap = pairCap;
+    q.pruned = pruned;
+    launch = true;
+    return CANVAS_OK;
+}
+static int arc_end_pruned(ArcJob& J, int n, double tss, int iseg[2], double& ostat, int al0, Stats& st) {
+    const unsigned long long* hOut = J.q.hOut; const double rn = (double)n, bss0 = J.bss0;
+    st.gpu_searches++;
+    if (hOut[4]) { J.overflow = true; return ARC_OVERFLOW; }      // too many candidate block pairs (flat data): exhaustive search
+    st.gpu_pairs += (long long)hOut[3] * AP_BK * AP_BK;
+    const double M = hOut[3] ? __builtin_bit_cast(double, hOut[0]) : -1.0;
+    if (!(M > bss0)) { J.path = 1; ostat = normalise(bss0, tss, rn); iseg[0] = J.ti; iseg[1] = J.tj; return ARC_DECIDED; }   // the incumbent survives every strict '>' test
+    if (hOut[1] == 1) {
+        const int L = (int)(hOut[2] >> 32), i0 = (int)(hOut[2] & 0xffffffffull);
+        if (ref_scans_arc(J.B, n, al0, i0 + 1, L)) { J.path = 2; ostat = normalise(M, tss, rn); iseg[0] = i0 + 1; iseg[1] = i0 + 1 + L; return ARC_DECIDED; }
+        st.unscanned_max++;      // the best admissible arc is one the reference does not look at: its own (smaller) maximum comes from the host replay
+        J.path = 4; return ARC_REPLAY;
     }
-    rc = G.ensure_exhaustive(); if (rc) return rc;
-    hMax = (double*)G.pinEx; hFirst = (int32_t*)(hMax + G.cap);
-    q.hMax = hMax; q.hFirst = hFirst; q.r.dmax = G.dMax; q.r.firstI = G.dFirst;
-    rc = service_submit_arc(G.svc, q); if (rc) return rc;
-    const double* dmax = hMax; const int32_t* firstI = hFirst;
-    if (!cvx_hook("CANVAS_CBS_EXHAUSTIVE_ARCS")) st.gpu_searches--;
+    J.path = 3;       // several arcs attain the maximum: the winner depends on the reference's block visiting order
+    return ARC_REPLAY;
+}
+static int32_t arc_begin_exhaustive(ArcGpu& G, ArcJob& J) {
+    int32_t rc = G.ensure_exhaustive(); if (rc) return rc;
+    double* hMax = (double*)G.pinEx;
+    J.q.pruned = false; J.q.hMax = hMax; J.q.hFirst = (int32_t*)(hMax + G.cap); J.q.r.dmax = G.dMax; J.q.r.firstI = G.dFirst;
+    return CANVAS_OK;
+}
+static int arc_end_exhaustive(ArcJob& J, int n, double tss, const double* sx, int iseg[2], double& ostat, int al0, Stats& st) {
+    const double* dmax = (const double*)J.q.hMax; const int32_t* firstI = (const int32_t*)J.q.hFirst; const double rn = (double)n, bss0 = J.bss0;
+    if (J.overflow) st.gpu_searches--;      // (counted by the pruned search that overflowed)
     st.gpu_searches++; st.gpu_pairs += (long long)n * (n - 1) / 2;
     // arcs of length L in [al0, n - al0] (CBSTStatistic.cs:139-151: alenlo >= al0, alenhi <= n - al0)
     double M = -1.0; int bestL = -1, nbest = 0;
@@ -1923,15 +1934,30 @@ static int32_t tmaxo_gpu(ArcGpu& G, const double* x, int n, double tss, double* 
         double rj = (double)L; double v = (rn / (rj * (rn - rj))) * sq(dmax[L]);
         if (v > M) { M = v; bestL = L; nbest = 1; } else if (v == M) nbest++;
     }
-    if (!(M > bss0)) { ostat = normalise(bss0, tss, rn); iseg[0] = ti; iseg[1] = tj; return CANVAS_OK; }   // the incumbent survives every strict '>' test
+    if (!(M > bss0)) { J.path = 1; ostat = normalise(bss0, tss, rn); iseg[0] = J.ti; iseg[1] = J.tj; return ARC_DECIDED; }   // the incumbent survives every strict '>' test
     if (nbest == 1) {
         // is the maximising arc unique among all arcs of that length (including rounding plateaus of v)?
         double rj = (double)bestL, c = rn / (rj * (rn - rj)); int cnt = 0;
         for (int i = 0; i + bestL < n && cnt < 2; i++) { double d = std::fabs(sx[i + bestL] - sx[i]); if (c * sq(d) == M) cnt++; }
-        if (cnt == 1 && ref_scans_arc(B, n, al0, firstI[bestL] + 1, bestL)) { ostat = normalise(M, tss, rn); iseg[0] = firstI[bestL] + 1; iseg[1] = firstI[bestL] + 1 + bestL; return CANVAS_OK; }
-        if (cnt == 1) st.unscanned_max++;
+        if (cnt == 1 && ref_scans_arc(J.B, n, al0, firstI[bestL] + 1, bestL)) { J.path = 2; ostat = normalise(M, tss, rn); iseg[0] = firstI[bestL] + 1; iseg[1] = firstI[bestL] + 1 + bestL; return ARC_DECIDED; }
+        if (cnt == 1) { st.unscanned_max++; J.path = 4; return ARC_REPLAY; }
     }
-    ok = false;     // exact tie: the winner depends on the reference's block visiting order
+    J.path = 3;     // exact tie: the winner depends on the reference's block visiting order
+    return ARC_REPLAY;
+}
+// ok = false when the caller must fall back to the host replay (ambiguous maximum)
+static int32_t tmaxo_gpu(ArcGpu& G, const double* x, int n, double tss, double* sx, int iseg[2], double& ostat, int al0, Stats& st, bool& ok) {
+    ArcJob J; bool launch = false;
+    ok = true;
+    int32_t rc = arc_begin(G, x, n, tss, sx, iseg, ostat, al0, cvx_hook("CANVAS_CBS_EXHAUSTIVE_ARCS") == nullptr, AP_PAIRCAP, J, launch); if (rc || !launch) return rc;
+    if (J.q.pruned) {
+        rc = service_submit_arc(G.svc, J.q); if (rc) return rc;
+        const int r = arc_end_pruned(J, n, tss, iseg, ostat, al0, st);
+        if (r != ARC_OVERFLOW) { ok = r == ARC_DECIDED; return CANVAS_OK; }
+    }
+    rc = arc_begin_exhaustive(G, J); if (rc) return rc;
+    rc = service_submit_arc(G.svc, J.q); if (rc) return rc;
+    ok = arc_end_exhaustive(J, n, tss, sx, iseg, ostat, al0, st) == ARC_DECIDED;
     return CANVAS_OK;
 }
 
@@ -2555,11 +2581,22 @@ struct PermService {
     }
     int32_t submit_arc(ArcHostReq& q) {
         std::unique_lock<std::mutex> lk(mu);
+        q.done = false;      // (a request comes a second time when its pair list overflowed: without this the wait below returned before the exhaustive launch had run)
         pendingArc.push_back(&q);
         cvWork.notify_one();
         cvDone.wait(lk, [&]() { return q.done; });
         if (q.rc) ctx->err = err;
         return q.rc;
+    }
+    // several searches at once (canvas_cbs_arc_probe): all of them are queued before the launcher wakes, so which requests share a launch (64 at a time, in order) is fixed
+    int32_t submit_arcs(const std::vector<ArcHostReq*>& qs) {
+        if (qs.empty()) return CANVAS_OK;
+        std::unique_lock<std::mutex> lk(mu);
+        for (auto* q : qs) { q->done = false; pendingArc.push_back(q); }
+        cvWork.notify_one();
+        cvDone.wait(lk, [&]() { for (auto* q : qs) if (!q->done) return false; return true; });
+        for (auto* q : qs) if (q->rc) { ctx->err = err; return q->rc; }
+        return CANVAS_OK;
     }
     int32_t init() {
         CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3488,6 +3525,72 @@ extern "C" int32_t canvas_cbs_perm_probe(canvas_ctx* ctx, const double* h_x, int
         fprintf(stderr, "k_perm_rp workgroup 0 (n %d, %d permutations): cycles range set-up %lld, inbox %lld, own steps: targets + independent steps %lld, ordered replay %lld, last steps (one wave) %lld, statistic: tables %lld, gather %lld, sums + arcs %lld\n",
                 n, (nb + rpWGs - 1) / rpWGs, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]); }
     if (h_ms3) for (int i = 0; i < 3; i++) h_ms3[i] = svc.lastMs[i];
+    return CANVAS_OK;
+}
+// Diagnostic / test entry: TMaxO (CBSTStatistic.cs:19-341) of nseg caller-supplied centred segments exactly as find_change_point runs it on a segment of 4096 bins or more — the
+// steps of tmaxo_gpu, the launcher's launch_arc, tmaxo_host where they say replay — with every segment of the call queued at the launcher before it wakes, so that they share
+// launches (grid.y = request, 64 at a time).  Own launcher and engines on the caller's context; nothing is kept.  See canvas_hip.h for the outputs.
+extern "C" int32_t canvas_cbs_arc_probe(canvas_ctx* ctx, int32_t mode, int32_t nseg, const int64_t* h_off, const double* h_x, int32_t al0, int32_t pair_cap,
+                                        double* h_sx, double* h_tau, double* h_stat, int32_t* h_iseg, int32_t* h_path, uint64_t* h_words, double* h_dmax, int32_t* h_first) {
+    if (!ctx) return CANVAS_ERR_INVALID;
+    if (!h_off || !h_x || !h_sx || !h_tau || !h_stat || !h_iseg || !h_path || !h_words || !h_dmax || !h_first) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: null array");
+    if (nseg < 1) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: nseg < 1");
+    if (mode != 0 && mode != 1) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: mode is 0 (pruned search, exhaustive on overflow) or 1 (exhaustive search)");
+    if (al0 < 1) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: al0 < 1");
+    if (pair_cap < 0 || pair_cap > AP_PAIRCAP) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: pair_cap outside 0 .. 8192");
+    if (h_off[0] != 0) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: the offsets do not start at 0");
+    for (int s = 0; s < nseg; s++) {
+        if (h_off[s + 1] < h_off[s]) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: the offsets decrease");
+        if (h_off[s + 1] - h_off[s] < 4) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: a segment shorter than 4");
+        if (h_off[s + 1] - h_off[s] > (int64_t)1 << 30) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: a segment longer than 2^30");
+    }
+    for (int64_t i = 0; i < h_off[nseg]; i++) if (!std::isfinite(h_x[i])) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_cbs_arc_probe: a value that is not finite");
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int cap = pair_cap ? pair_cap : AP_PAIRCAP;
+    std::vector<std::unique_ptr<cbs::ArcGpu>> engines((size_t)nseg); std::vector<cbs::ArcJob> jobs((size_t)nseg);      // (declared before the launcher: destroyed after its thread has gone)
+    cbs::PermService svc(ctx);
+    cbs::Stats st;
+    std::vector<char> launched((size_t)nseg, 0); std::vector<double> tss((size_t)nseg, 0.0);
+    std::vector<cbs::ArcHostReq*> round;
+    memset(h_words, 0, (size_t)nseg * 6 * sizeof(uint64_t));
+    for (int s = 0; s < nseg; s++) {
+        const int n = (int)(h_off[s + 1] - h_off[s]); const double* x = h_x + h_off[s];
+        for (int i = 0; i < n; i++) tss[(size_t)s] += 1.0 * x[i] * x[i];
+        engines[(size_t)s].reset(new cbs::ArcGpu()); engines[(size_t)s]->ctx = ctx; engines[(size_t)s]->svc = &svc;
+        bool launch = false;
+        int32_t rc = cbs::arc_begin(*engines[(size_t)s], x, n, tss[(size_t)s], h_sx + h_off[s], h_iseg + 2 * s, h_stat[s], al0, mode == 0, cap, jobs[(size_t)s], launch); if (rc) return rc;
+        h_tau[s] = jobs[(size_t)s].bss0; h_path[s] = 0; launched[(size_t)s] = launch ? 1 : 0;
+        if (launch && mode == 0) round.push_back(&jobs[(size_t)s].q);
+    }
+    std::vector<int> result((size_t)nseg, cbs::ARC_DECIDED);
+    auto submit = [&](std::vector<cbs::ArcHostReq*>& r) { return r.size() == 1 ? svc.submit_arc(*r[0]) : svc.submit_arcs(r); };      // (one request: the call tmaxo_gpu makes, a second time after an overflow)
+    { int32_t rc = submit(round); if (rc) return rc; }
+    round.clear();
+    for (int s = 0; s < nseg; s++) {
+        if (!launched[(size_t)s]) continue;
+        cbs::ArcJob& J = jobs[(size_t)s]; const int n = J.q.r.n;
+        if (mode == 0) {
+            // (the mailbox carries words 0..4; the sixth is read from the device, behind everything the launcher put on its stream)
+            CANVAS_HIP_TRY(ctx, hipMemcpyAsync(h_words + 6 * (size_t)s, J.q.p.out, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, svc.stream));
+            CANVAS_HIP_TRY(ctx, hipStreamSynchronize(svc.stream));
+            for (int w = 0; w < 5; w++) if (h_words[6 * (size_t)s + w] != J.q.hOut[w]) CANVAS_FAIL(ctx, CANVAS_ERR_HIP, "canvas_cbs_arc_probe: the mailbox and the device disagree on a result word");
+            result[(size_t)s] = cbs::arc_end_pruned(J, n, tss[(size_t)s], h_iseg + 2 * s, h_stat[s], al0, st);
+            if (result[(size_t)s] != cbs::ARC_OVERFLOW) continue;
+        }
+        int32_t rc = cbs::arc_begin_exhaustive(*engines[(size_t)s], J); if (rc) return rc;
+        round.push_back(&J.q);
+    }
+    { int32_t rc = submit(round); if (rc) return rc; }
+    for (int s = 0; s < nseg; s++) {
+        if (!launched[(size_t)s]) continue;
+        cbs::ArcJob& J = jobs[(size_t)s]; const int n = J.q.r.n;
+        if (!J.q.pruned) {
+            result[(size_t)s] = cbs::arc_end_exhaustive(J, n, tss[(size_t)s], h_sx + h_off[s], h_iseg + 2 * s, h_stat[s], al0, st);
+            for (int L = 1; L < n; L++) { h_dmax[h_off[s] + L] = ((const double*)J.q.hMax)[L]; h_first[h_off[s] + L] = ((const int32_t*)J.q.hFirst)[L]; }
+        }
+        h_path[s] = J.path + (J.overflow ? 8 : 0);
+        if (result[(size_t)s] == cbs::ARC_REPLAY) cbs::tmaxo_host(h_x + h_off[s], n, tss[(size_t)s], h_sx + h_off[s], h_iseg + 2 * s, h_stat[s], al0);
+    }
     return CANVAS_OK;
 }
 // the chromosomes' draw streams ahead of the first call: returns at once, the generator runs on its own thread and stream (cbs::MtStreamCache)

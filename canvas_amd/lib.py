@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     "canvas_mask_from_fasta", "canvas_mask_exclude_intervals", "canvas_screen_hits",
     "canvas_bin_rates", "canvas_bin_size_from_rates", "canvas_bin_count_upper_bound", "canvas_bin_genome", "canvas_bin_sample", "canvas_bin_sample_gcweighted", "canvas_bin_predefined", "canvas_bin_predefined_gcweighted",
     "canvas_clean", "canvas_clean2", "canvas_clean_batch", "canvas_merge_cleaned", "canvas_chromosome_offsets", "canvas_quantize_f2", "canvas_hmm_per_sample", "canvas_hmm_joint", "canvas_segment_ids", "canvas_segment_ids_filtered", "canvas_segment_ids_ploidy", "canvas_evenness_score", "canvas_split_overlapping", "canvas_cbs", "canvas_cbs_undo", "canvas_cbs_device_stats", "canvas_cbs_tailp_stats", "canvas_cbs_tail_probe", "canvas_cbs_boundary", "canvas_cbs_seeds", "canvas_cbs_prefetch", "canvas_cbs_stream_read", "canvas_cbs_cache_stats", "canvas_wavelets", "canvas_wavelets_stats", "canvas_wavelets_decisions", "canvas_wavelets_inputs", "canvas_wavelets_prefix_probe", "canvas_wavelets_bound_probe", "canvas_wavelets_level_probe", "canvas_wavelets_chain_probe", "canvas_wavelets_subtree_probe", "canvas_wavelets_median_probe", "canvas_normalize_reference", "canvas_normalize_ratio", "canvas_normalize_best_normal", "canvas_normalize_pca_reference", "canvas_sample_pipeline",
-    "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_stale_reads", "canvas_select_probe", "canvas_hmm_backbone_probe",
+    "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_cbs_arc_probe", "canvas_stale_reads", "canvas_select_probe", "canvas_hmm_backbone_probe",
     "canvas_memcpy_h2d_async", "canvas_snv_count", "canvas_flag_unique_kmers", "canvas_fasta_case_from_mask",
     "canvas_smooth", "canvas_smooth_lengths", "canvas_smooth_plan",
 ]
@@ -476,6 +476,19 @@ class Canvas:
         lohi = np.zeros((nb, 2), np.float64); ms = np.zeros(3, np.float64)
         self._check(self.lib.canvas_cbs_perm_probe(self.ctx, _np_ptr(x), C.c_int32(len(x)), C.c_uint32(seed & 0xFFFFFFFF), C.c_int32(nb), C.c_int32(kernel), C.c_double(tss), _np_ptr(lohi), _np_ptr(ms)))
         return lohi, ms
+
+    def cbs_arc_probe(self, segments, al0=2, mode=0, pair_cap=0):
+        """TMaxO of centred segments through the device arc search (canvas_cbs_arc_probe), all in shared launches.  mode 0: pruned search, 1: exhaustive kernel; pair_cap 0: the
+        library's.  Returns a dict: off[nseg + 1], sx, tau[nseg], stat[nseg], iseg[nseg, 2], path[nseg], words[nseg, 6] (uint64), dmax, first (sx, dmax, first: concatenated like the input)"""
+        segs = [np.ascontiguousarray(s, np.float64).ravel() for s in segments]
+        off = np.zeros(len(segs) + 1, np.int64); off[1:] = np.cumsum([len(s) for s in segs])
+        x = np.ascontiguousarray(np.concatenate(segs)) if segs else np.zeros(0, np.float64)
+        ns, tot = len(segs), max(1, len(x))
+        out = dict(off=off, sx=np.zeros(tot, np.float64), tau=np.zeros(ns, np.float64), stat=np.zeros(ns, np.float64), iseg=np.zeros((ns, 2), np.int32), path=np.zeros(ns, np.int32),
+                   words=np.zeros((ns, 6), np.uint64), dmax=np.zeros(tot, np.float64), first=np.zeros(tot, np.int32))
+        self._check(self.lib.canvas_cbs_arc_probe(self.ctx, C.c_int32(mode), C.c_int32(ns), _np_ptr(off), _np_ptr(x), C.c_int32(al0), C.c_int32(pair_cap), _np_ptr(out["sx"]), _np_ptr(out["tau"]),
+                                                  _np_ptr(out["stat"]), _np_ptr(out["iseg"]), _np_ptr(out["path"]), _np_ptr(out["words"]), _np_ptr(out["dmax"]), _np_ptr(out["first"])))
+        return out
 
     def select_probe(self, variant, dtype, values, seg_off, seg_lo, seg_hi, k):
         """the order-statistics engine of select.hpp on its own (canvas_select_probe).  values: numpy array of float32 / float64 / uint32 / uint64 for dtype 0 / 1 / 2 / 3;

@@ -302,6 +302,23 @@ int32_t canvas_cbs_tail_probe(canvas_ctx* ctx, const double* h_x, int32_t n, dou
  * the intervals of all three kernels with the oracle's XPerm + HTMaxP.
  * h_ms3 (optional): milliseconds of the generator's sequential part, its strided part, and the permutation + statistic kernel.  No reference counterpart: the engine's test bench. */
 int32_t canvas_cbs_perm_probe(canvas_ctx* ctx, const double* h_x, int32_t n, uint32_t seed, int32_t nb, int32_t kernel, double tss, double* h_lohi, double* h_ms3);
+/* Diagnostic / test entry: the observed statistic TMaxO (CBSTStatistic.cs:19-341) of nseg centred segments, h_x[h_off[s] .. h_off[s + 1]), exactly as canvas_cbs searches it on the
+ * device for a segment of 4096 bins or more (here: n >= 4).  mode 0: the pruned search (k_arcp_blocks, k_arcp_bounds, k_arcp_eval, k_arcp_mail), the exhaustive kernel
+ * (k_arc_search) when the pair list overflows; mode 1: the exhaustive kernel only (as under CANVAS_CBS_EXHAUSTIVE_ARCS).  al0 >= 1: the minimum arc length.  pair_cap: the pair
+ * list's capacity, 0 = the library's 8192, else 1 .. 8192 (a small one reaches the overflow branch on a short segment).  All segments of a call are queued at one launcher
+ * before it wakes: they share its launches, 64 requests at a time, in order.  Finite values only.  Per segment s:
+ *   h_sx[h_off[s] ..]   the prefix sums;
+ *   h_tau[s]            the incumbent the search starts from (the arc between the prefix sums' extremes, both taken as 0 at position n until something beats that; 0 when they coincide);
+ *   h_stat[s], h_iseg[2 s ..]  the statistic (before FindChangePoint's 0.99999) and the 1-based arc, as the reference's TMaxO returns them;
+ *   h_path[s]           0 no launch (the extremes coincide), 1 the incumbent was kept, 2 the device's unique maximiser was accepted, 3 several arcs attain the maximum (host replay
+ *                       of the reference's block order), 4 a unique maximiser that the reference's scan leaves out (host replay); + 8: the pair list overflowed and the exhaustive
+ *                       kernel supplied the answer;
+ *   h_words[6 s ..]     the pruned search's result words after it finished: the maximum's bits, the number of arcs attaining it, the smallest (L << 32) | i among them (i: 0-based
+ *                       start), the number of surviving block pairs, the overflow flag, the best block-extreme arc's bits (zeros when no pruned search ran);
+ *   h_dmax, h_first [h_off[s] + L], L = 1 .. n - 1: where the exhaustive kernel ran, max_i |sx[i + L] - sx[i]| and the smallest such i (untouched otherwise).
+ * h_sx, h_dmax, h_first are as long as h_x.  tests/test_cbs_arc_kernels_gpu.py compares all of it with an every-arc search in numpy and with the oracle's TMaxO. */
+int32_t canvas_cbs_arc_probe(canvas_ctx* ctx, int32_t mode, int32_t nseg, const int64_t* h_off, const double* h_x, int32_t al0, int32_t pair_cap,
+                             double* h_sx, double* h_tau, double* h_stat, int32_t* h_iseg, int32_t* h_path, uint64_t* h_words, double* h_dmax, int32_t* h_first);
 /* Diagnostic / test entry: the exact order-statistics engine behind every median and quartile of the library (csrc/select.hpp) on caller-supplied data.  d_values (device) holds
  * h_seg_off[nseg] elements partitioned in nseg segments by h_seg_off[nseg + 1] (host, non-decreasing).  dtype: 0 float32 values keyed on the device (the CanvasClean / PerSampleHMM
  * path, 32-bit keys), 1 float64 values keyed on the device (CanvasNormalize / LOESS, 64-bit keys), 2 / 3 raw uint32 / uint64 keys.  The key of a value is its order-preserving
