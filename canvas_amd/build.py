@@ -10,7 +10,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-result"]
-PRODUCT_SRC = ["ctx.hip", "prep.hip", "bin.hip", "clean.hip", "hmm.hip", "cbs.hip", "wavelets.hip", "evenness.hip", "normalize.hip", "pipeline.hip", "sharded.hip", "comm.hip", "snv.hip", "kmer.hip", "smooth.hip"]
+PRODUCT_SRC = ["ctx.hip", "prep.hip", "bin.hip", "clean.hip", "hmm.hip", "cbs.hip", "wavelets.hip", "evenness.hip", "normalize.hip", "pipeline.hip", "sharded.hip", "comm.hip", "snv.hip", "kmer.hip", "smooth.hip", "call.hip"]
 
 
 def _hipcc():
@@ -234,8 +234,8 @@ def build_tools(force=False, verbose=False):
 
 
 def build_more_tools(force=False, verbose=False):
-    """the drivers added after those six, by the same staleness rule (the hash covers every *.hpp of tools/ and the headers of include/): canvas_amd/bin/CanvasSmooth"""
-    return _build_tool_set((("CanvasSmooth", "canvas_smooth_main.cpp"),), force, verbose)
+    """the drivers added after those six, by the same staleness rule (the hash covers every *.hpp of tools/ and the headers of include/): canvas_amd/bin/CanvasSmooth, CanvasDiploidCaller"""
+    return _build_tool_set((("CanvasSmooth", "canvas_smooth_main.cpp"), ("CanvasDiploidCaller", "canvas_diploid_caller_main.cpp")), force, verbose)
 
 
 if __name__ == "__main__":

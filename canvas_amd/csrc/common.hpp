@@ -32,6 +32,8 @@ struct canvas_ctx {
     void* sel_ws = nullptr; size_t sel_ws_bytes = 0;
     void* sel_hist = nullptr; size_t sel_hist_bytes = 0;   // replicated histograms: all zero between calls (k_select_pick clears what it reads)
     void* sel_pin = nullptr; size_t sel_pin_bytes = 0;
+    void* call_pin = nullptr; size_t call_pin_bytes = 0; hipEvent_t call_pin_ev = nullptr;      // call.hip: pinned image of a select's flag and lists (one copy per select) and the event behind that copy
+    void* call_ws = nullptr; size_t call_ws_bytes = 0;     // call.hip: what canvas_call_diploid keeps across the selects it enqueues (they carve ctx->ws); grow-only
     // small pinned staging area for host->device parameter tables (async copies from pinned memory need no synchronisation
     // to protect the source); bump-allocated, wrapped with a synchronisation when full
     char* misc_pin = nullptr; size_t misc_off = 0;

@@ -66,6 +66,9 @@ void canvas_destroy(canvas_ctx* ctx) {
     if (ctx->misc_pin) (void)hipHostFree(ctx->misc_pin);
     if (ctx->sel_ws) (void)hipFree(ctx->sel_ws);
     if (ctx->sel_hist) (void)hipFree(ctx->sel_hist);
+    if (ctx->call_ws) (void)hipFree(ctx->call_ws);
+    if (ctx->call_pin) (void)hipHostFree(ctx->call_pin);
+    if (ctx->call_pin_ev) (void)hipEventDestroy(ctx->call_pin_ev);
     if (ctx->sel_pin) (void)hipHostFree(ctx->sel_pin);
     if (ctx->pin) (void)hipHostFree(ctx->pin);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -45,10 +45,12 @@ static inline double host_double_of_key(unsigned long long k) {
 // a median until the last digits) share ONE LDS histogram row that is replicated at flush time; (ii) digits are concentrated
 // (exponent bytes of similar counts, zero low bytes of integer-valued floats), so a wave first aggregates up to four distinct
 // digits with ballots — one LDS atomic per distinct digit — and only the lanes left over issue their own atomics.
-template <typename K>
-__device__ __forceinline__ void select_hist_body(const K* __restrict__ keys, const SelTile* __restrict__ tiles, const SelSegQ* __restrict__ segq,
+// (Src / Map: the array may hold the VALUES instead of their key images — map(value, index) turns one into its key as it is loaded, call.hip; the default is the array of keys)
+template <typename K> struct SelKeysAsStored { __device__ __forceinline__ K operator()(K k, int64_t) const { return k; } };
+template <typename K, typename Src = K, typename Map = SelKeysAsStored<K>>
+__device__ __forceinline__ void select_hist_body(const Src* __restrict__ keys, const SelTile* __restrict__ tiles, const SelSegQ* __restrict__ segq,
                                                  const unsigned long long* __restrict__ qprefix, int shift, int firstPass,
-                                                 uint32_t* __restrict__ hist /* [SEL_REP][nq][256] */, int nq, const uint32_t* __restrict__ hdr) {
+                                                 uint32_t* __restrict__ hist /* [SEL_REP][nq][256] */, int nq, const uint32_t* __restrict__ hdr, Map map = Map()) {
     __shared__ uint32_t lh[SEL_MAXQ * 256];
     __shared__ unsigned long long lpre[SEL_MAXQ];
     __shared__ int srep[SEL_MAXQ], suniq[SEL_MAXQ], snu;
@@ -78,7 +80,7 @@ __device__ __forceinline__ void select_hist_body(const K* __restrict__ keys, con
     // all 16 keys of this thread are loaded up front (independent loads in flight), then binned
     K kreg[SEL_CHUNK / 256];
 #pragma unroll
-    for (int r = 0; r < SEL_CHUNK / 256; r++) { const int64_t i = cbeg + threadIdx.x + (int64_t)r * 256; kreg[r] = i < T.end ? keys[i] : (K)0; }
+    for (int r = 0; r < SEL_CHUNK / 256; r++) { const int64_t i = cbeg + threadIdx.x + (int64_t)r * 256; kreg[r] = i < T.end ? map(keys[i], i) : (K)0; }
     if (nu == 1) {
         // one histogram row for the whole tile (every first pass, every single-query select): prefix and row index in registers, no LDS
         // reads and no loop over rows inside the key loop

@@ -10,6 +10,9 @@ _SO = os.path.join(HERE, "libcanvas_hip.so")
 _SYNTH_SO = os.path.join(HERE, "libcanvas_synth.so")
 
 MODE_BINARY, MODE_TDR, MODE_GCW = 0, 3, 5
+SELECT_MEDIAN_F32, SELECT_MEDIAN_F64, SELECT_UPPER = 0, 1, 2
+LOGISTIC_GERMLINE = (-5.0123, 4.9801, -5.5472, -1.7914)      # QualityScoreParameters.cs: LogisticGermline{Intercept, LogBinCount, ModelDistance, DistanceRatio}
+FILTER_Q10, FILTER_L10KB = 1, 2
 CLEAN_GCNORM, CLEAN_FILTSIZE, CLEAN_OUTLIERS, CLEAN_LOCALSD, CLEAN_LOESS = 1, 2, 4, 8, 16
 
 # every symbol include/canvas_hip.h declares (checked by tests/test_abi.py)
@@ -23,6 +26,7 @@ ABI_SYMBOLS = [
     "canvas_comm_unique_id", "canvas_comm_init", "canvas_comm_init_host", "canvas_allgather_boundaries", "canvas_sample_pipeline_sharded", "canvas_sample_pipeline_sharded_packed", "canvas_sharded_stats", "canvas_cbs_sharded", "canvas_wavelets_sharded", "canvas_allgather_host", "canvas_merge_cleaned_sharded", "canvas_profile_enable", "canvas_profile_get", "canvas_bin_gcw_stats", "canvas_cbs_tpermp_stats", "canvas_comm_split", "canvas_comm_restore", "canvas_comm_rank", "canvas_bin_sample_sharded", "canvas_hmm_per_sample_sharded", "canvas_cbs_perm_probe", "canvas_cbs_arc_probe", "canvas_stale_reads", "canvas_select_probe", "canvas_hmm_backbone_probe",
     "canvas_memcpy_h2d_async", "canvas_snv_count", "canvas_flag_unique_kmers", "canvas_fasta_case_from_mask",
     "canvas_smooth", "canvas_smooth_lengths", "canvas_smooth_plan",
+    "canvas_segment_select", "canvas_segment_select_plan", "canvas_call_diploid",
 ]
 
 
@@ -158,6 +162,17 @@ def smooth_plan(max_half_window):
     if rc:
         raise CanvasError(f"canvas_smooth_plan: error {rc}")
     return dict(fused=bool(out[0]), tile=int(out[1]), halo=int(out[2]), launches=int(out[3]))
+
+
+def segment_select_plan():
+    """canvas_segment_select_plan (plain host code, no GPU): dict(wave_max, lds_max, tile, launches, forced) — the size classes of Canvas.segment_select and the class the
+    CANVAS_CALL_CLASS test hook forces (None, "wave", "lds" or "tiled")"""
+    lib = load_library()
+    out = np.zeros(6, np.int64)
+    rc = lib.canvas_segment_select_plan(_np_ptr(out))
+    if rc:
+        raise CanvasError(f"canvas_segment_select_plan: error {rc}")
+    return dict(wave_max=int(out[0]), lds_max=int(out[1]), tile=int(out[2]), launches=int(out[3]), forced=(None, "wave", "lds", "tiled")[int(out[4])])
 
 
 class Canvas:
@@ -633,6 +648,66 @@ class Canvas:
         torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
         self._check(self.lib.canvas_smooth(self.ctx, C.c_int32(len(off) - 1), _np_ptr(off), C.c_void_p(counts.data_ptr()), C.c_int32(int(max_half_window)), C.c_void_p(out.data_ptr()), _np_ptr(out_n)))
         return out, out_n[:len(off) - 1]
+
+    def segment_select(self, values, seg_offset, mode, out=None):
+        """exact order statistics of many segments at once (canvas_segment_select): values = float32 device tensor, segment s = values[seg_offset[s]:seg_offset[s + 1]],
+        mode = SELECT_MEDIAN_F32 / SELECT_MEDIAN_F64 (Median() with the even-length average in float / in double) / SELECT_UPPER (a[n/2]).  Returns (out, n_empty): out =
+        float64 device tensor with one value per segment (0 for an empty one, created unless given)"""
+        torch = self.torch
+        off = np.ascontiguousarray(seg_offset, np.int64)
+        assert off.ndim == 1 and len(off) >= 1
+        assert values.dtype == torch.float32 and values.is_contiguous() and values.dim() == 1 and (values.numel() == 0 or values.device == self.device), "segment_select: values must be a dense float32 tensor on the context's device"
+        assert int(off.max()) <= values.numel(), "segment_select: the offsets reach past the values"
+        nseg = len(off) - 1
+        if out is None:
+            out = torch.empty(max(nseg, 1), dtype=torch.float64, device=self.device)
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.dim() == 1 and out.numel() >= nseg and out.device == self.device
+        nempty = C.c_int64(0)
+        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        self._check(self.lib.canvas_segment_select(self.ctx, C.c_void_p(values.data_ptr()), C.c_int64(nseg), _np_ptr(off), C.c_int32(int(mode)), C.c_void_p(out.data_ptr()), C.byref(nempty)))
+        return out[:nseg], nempty.value
+
+    def call_diploid(self, counts, chr_seg_offset, seg_begin, seg_end, seg_bin_offset, chr_site_offset, site_pos, site_ref, site_alt, logistic=LOGISTIC_GERMLINE,
+                     seg_start_ci=None, seg_end_ci=None):
+        """CanvasDiploidCaller.CallVariants between the parsed files and the written ones (canvas_call_diploid).  counts: float32 device tensor of every bin; segments
+        grouped by chromosome (chr_seg_offset[nchr + 1]) with zero-based seg_begin / seg_end and the bins seg_bin_offset[s] .. seg_bin_offset[s + 1]; sites grouped the same
+        way (chr_site_offset) as int32 device tensors site_pos (one-based) / site_ref / site_alt.  Returns a dict of numpy arrays: per segment bin_count, median_count,
+        site_count, informative, median_maf, cn, mcc (-1 = null), dist, dist2, qscore; per merged run run_first, run_last, run_begin, run_end, run_cn, run_mcc, run_qscore,
+        run_filter (FILTER_Q10 | FILTER_L10KB), run_bin_count, run_median_count (and run_start_ci / run_end_ci when the segments' confidence intervals are given: the first
+        segment's start interval, the last segment's end interval); diploid_coverage, mean_coverage, kept_sites, integer_sum (whether the mean came from the device)"""
+        torch = self.torch
+        cso = np.ascontiguousarray(chr_seg_offset, np.int64); csi = np.ascontiguousarray(chr_site_offset, np.int64)
+        beg = np.ascontiguousarray(seg_begin, np.int32); end = np.ascontiguousarray(seg_end, np.int32); sbo = np.ascontiguousarray(seg_bin_offset, np.int64)
+        nchr, nseg = len(cso) - 1, len(beg)
+        if nchr < 0 or len(csi) != nchr + 1 or len(end) != nseg or len(sbo) != nseg + 1 or (nchr >= 0 and len(cso) and int(cso[-1]) != nseg):
+            raise CanvasError("call_diploid: one begin / end per segment, nseg + 1 bin offsets, nchr + 1 chromosome offsets that end at the number of segments / sites")
+        assert counts.dtype == torch.float32 and counts.is_contiguous() and counts.dim() == 1 and (counts.numel() == 0 or counts.device == self.device)
+        for t in (site_pos, site_ref, site_alt):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.numel() == site_pos.numel() and (t.numel() == 0 or t.device == self.device)
+        if int(csi[-1]) != site_pos.numel():
+            raise CanvasError("call_diploid: the chromosomes' site offsets must end at the number of sites")
+        b4 = np.ascontiguousarray(logistic, np.float64)
+        assert b4.shape == (4,)
+        n1 = max(nseg, 1)
+        o = dict(median_count=np.zeros(n1, np.float64), site_offset=np.zeros(n1 + 1, np.int64), informative=np.zeros(n1, np.int32), median_maf=np.zeros(n1, np.float64),
+                 cn=np.zeros(n1, np.int32), mcc=np.zeros(n1, np.int32), dist=np.zeros(n1, np.float64), dist2=np.zeros(n1, np.float64), qscore=np.zeros(n1, np.int32),
+                 run_first=np.zeros(n1, np.int64), run_last=np.zeros(n1, np.int64), run_qscore=np.zeros(n1, np.int32), run_filter=np.zeros(n1, np.int32), run_median_count=np.zeros(n1, np.float64))
+        nruns = C.c_int64(0); scal = np.zeros(2, np.float64); info = np.zeros(4, np.int64)
+        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        self._check(self.lib.canvas_call_diploid(self.ctx, C.c_int64(counts.numel()), C.c_void_p(counts.data_ptr()), C.c_int32(nchr), _np_ptr(cso), _np_ptr(beg), _np_ptr(end), _np_ptr(sbo),
+                                                 _np_ptr(csi), C.c_void_p(site_pos.data_ptr()), C.c_void_p(site_ref.data_ptr()), C.c_void_p(site_alt.data_ptr()), _np_ptr(b4),
+                                                 _np_ptr(o["median_count"]), _np_ptr(o["site_offset"]), _np_ptr(o["informative"]), _np_ptr(o["median_maf"]), _np_ptr(o["cn"]), _np_ptr(o["mcc"]),
+                                                 _np_ptr(o["dist"]), _np_ptr(o["dist2"]), _np_ptr(o["qscore"]), C.byref(nruns), _np_ptr(o["run_first"]), _np_ptr(o["run_last"]),
+                                                 _np_ptr(o["run_qscore"]), _np_ptr(o["run_filter"]), _np_ptr(o["run_median_count"]), _np_ptr(scal), _np_ptr(info)))
+        r = nruns.value
+        out = {k: (v[:r] if k.startswith("run_") else v[:nseg]) for k, v in o.items() if k != "site_offset"}
+        out["site_count"] = np.diff(o["site_offset"][:nseg + 1]); out["bin_count"] = np.diff(sbo)
+        f, l = out["run_first"], out["run_last"]
+        out.update(run_begin=beg[f], run_end=end[l], run_cn=out["cn"][f], run_mcc=out["mcc"][f], run_bin_count=sbo[l + 1] - sbo[f],
+                   diploid_coverage=float(scal[0]), mean_coverage=float(scal[1]), kept_sites=int(info[0]), integer_sum=bool(info[1]))
+        if seg_start_ci is not None and seg_end_ci is not None:
+            out.update(run_start_ci=np.asarray(seg_start_ci)[f], run_end_ci=np.asarray(seg_end_ci)[l])
+        return out
 
     def segment_ids(self, chr_offset, state, start, stop, max_inter_bin_dist=1000000, excluded=None, out=None, ploidy=None):
         """DeriveSegments + PostProcessSegments; excluded = per-chromosome list of (starts, stops) of the -b BED file; ploidy = per-chromosome list

@@ -135,6 +135,17 @@ namespace CanvasHipInterop
         [DllImport(Lib)] public static extern int canvas_smooth(IntPtr ctx, int nchr, long[] chrOffset, IntPtr dCount, int maxHalfWindow, IntPtr dOut, long[] outN);
         [DllImport(Lib)] public static extern int canvas_smooth_lengths(int nchr, long[] n, int maxHalfWindow, long[] outN);
         [DllImport(Lib)] public static extern int canvas_smooth_plan(int maxHalfWindow, long[] out4);
+        // CanvasDiploidCaller's per-segment order statistics: dOut[s] (double) = median (mode 0: even-length average in float, 1: in double) or upper median a[n/2] (mode 2) of
+        // dValues[segOffset[s] .. segOffset[s + 1]) (float), 0 for an empty segment (counted in nEmpty).  canvas_segment_select_plan is plain host code: {wave max, LDS max, tile, launches, forced class, 0}
+        [DllImport(Lib)] public static extern int canvas_segment_select(IntPtr ctx, IntPtr dValues, long nseg, long[] segOffset, int mode, IntPtr dOut, out long nEmpty);
+        [DllImport(Lib)] public static extern int canvas_segment_select_plan(long[] out6);
+        // CanvasDiploidCaller.CallVariants between the parsed files and the written ones: sites to segments, MeanCoverage / diploidCoverage, the 36 model points, per-segment
+        // medians and nearest model point, q-scores, MergeSegments, filters, run medians.  Per-segment arrays hold nseg entries (segSiteOffset nseg + 1), per-run arrays nseg
+        // entries of which nRuns are filled; scalars2 = {diploidCoverage, MeanCoverage}; info4 = {kept sites, integer sum used, coverage sum, 0} or null
+        [DllImport(Lib)] public static extern int canvas_call_diploid(IntPtr ctx, long nbins, IntPtr dCount, int nchr, long[] chrSegOffset, int[] segBegin, int[] segEnd, long[] segBinOffset,
+            long[] chrSiteOffset, IntPtr dSitePos, IntPtr dSiteRef, IntPtr dSiteAlt, double[] logistic4,
+            double[] segMedianCount, long[] segSiteOffset, int[] segInformative, double[] segMedianMaf, int[] segCn, int[] segMcc, double[] segDist, double[] segDist2, int[] segQScore,
+            out long nRuns, long[] runFirst, long[] runLast, int[] runQScore, int[] runFilter, double[] runMedianCount, double[] scalars2, long[] info4);
 
         /// <summary>Turns a non-zero status into the module's own failure convention (message on stderr, exit code 1).</summary>
         public static void Check(IntPtr ctx, int status, string what)

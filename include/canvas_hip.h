@@ -612,6 +612,47 @@ int32_t canvas_smooth_lengths(int32_t nchr, const int64_t* h_n, int32_t max_half
  * (per-pass path: launches = max_half_window, an upper bound: the passes end once every chromosome is empty; 0 = a copy) */
 int32_t canvas_smooth_plan(int32_t max_half_window, int64_t* h_out4);
 
+/* ---- CanvasDiploidCaller: per-segment order statistics (CanvasDiploidCaller.cs AssignPloidyCallsDistance, CanvasSegment.cs MedianCount / WriteCoveragePlotData) ---- */
+#define CANVAS_SELECT_MEDIAN_F32 0 /* a[n/2] for odd n, (a[n/2-1] + a[n/2]) / 2 averaged in float for even n: Utilities.Median(IEnumerable<float>) */
+#define CANVAS_SELECT_MEDIAN_F64 1 /* the same with the average taken in double: the median of floats widened into a List<double> */
+#define CANVAS_SELECT_UPPER 2      /* a[n/2] of the sorted values (CanvasSegment.cs:696-697) */
+/* Exact order statistics of nseg segments of a float32 device array in a fixed sequence of launches (at most 11, whatever nseg is): segment s is
+ * d_values[h_seg_offset[s] .. h_seg_offset[s+1]); d_out[s] (double, device) = its statistic — an order statistic is a value of the array bit for bit, widened; the
+ * averages are ((double)(float)((a + b) / 2f)) and ((double)a + (double)b) / 2.  An empty segment gives 0 and is counted in *h_nempty (may be NULL).  -0.0 sorts in front of 0.0.
+ * Values must be finite (CANVAS_ERR_INVALID names the first index that is not); CANVAS_ERR_INVALID as well for a mode outside 0..2, a negative first offset, offsets that
+ * decrease, or 2^31 segments and more — all of that is decided first, before the context is looked at (a NULL ctx returns CANVAS_ERR_INVALID too, but only after
+ * *h_nempty has been written for offsets that passed).  The call waits for its result. */
+int32_t canvas_segment_select(canvas_ctx* ctx, const float* d_values, int64_t nseg, const int64_t* h_seg_offset /* nseg+1 */, int32_t mode, double* d_out /* nseg */,
+                              int64_t* h_nempty);
+/* host only, no context: h_out6 = { largest segment of the wave class (rank counting inside a wave), largest segment of the LDS class (staged once, radix-selected in LDS),
+ * keys per tile of the tiled multi-pass class above that, launches at most, class forced by the CANVAS_CALL_CLASS test hook (0 none, 1 wave, 2 lds, 3 tiled), 0 } */
+int32_t canvas_segment_select_plan(int64_t* h_out6);
+
+/* CanvasDiploidCaller.CallVariants between "files parsed" and "files written" (CanvasDiploidCaller.cs:295-343) on device-resident bins and sites.
+ * Bins: d_count[nbins] (float).  Segments (host tables, grouped by chromosome: those of chromosome c are h_chr_seg_offset[c] .. h_chr_seg_offset[c+1]): zero-based
+ * h_seg_begin / h_seg_end and the bins h_seg_bin_offset[s] .. h_seg_bin_offset[s+1] (offsets from 0 to nbins, at least one bin each).  Sites of chromosome c:
+ * h_chr_site_offset[c] .. [c+1] of d_site_pos (one-based) / d_site_ref / d_site_alt.  h_logistic4 = LogisticGermline{Intercept, LogBinCount, ModelDistance, DistanceRatio}.
+ * A site with ref + alt >= 10 belongs to the first segment of its chromosome with End > position if that segment's Begin <= position (IO.cs:156-176, the one-based /
+ * zero-based comparison kept); Frequency = alt / (float)(ref + alt), folded as f > 0.5 ? 1 - f : f in float.
+ * Per segment (arrays of nseg): median count (Utilities.Median(float)), h_seg_site_offset[nseg+1] (kept sites in front of each segment), informative (nMaf >=
+ * max(10, (End-Begin)/463/2)), median folded frequency (double average; -1 when not informative), copy number and major chromosome count of the nearest of the 36 model
+ * points (MCC -1 when fewer than 10 sites), its distance and the runner-up's, the LogisticGermline q-score.
+ * Per merged run (MergeSegments with its defaults: same chromosome, same CN, Begin - run.End < 10000; arrays of nseg, *h_nruns filled): first and last segment (the run
+ * spans Begin of the first to End of the last and takes their confidence intervals), q-score recomputed with the run's bin count, filter bits (1 = q10, 2 = L10kb), median
+ * count (double average).  h_scalars2 = { diploidCoverage (bit-equal to the serial Utilities.Mean(float[])), MeanCoverage }; h_info4 (may be NULL) = { kept sites, 1 when
+ * diploidCoverage came from the exact integer sum on the device and 0 when the counts were summed on the host in bin order, coverage sum of the kept sites, 0 }.
+ * CANVAS_ERR_INVALID (checked on the host tables before the context is looked at unless marked *; *h_nruns is set to 0 once they have passed, also with a NULL ctx): offsets that do not start at 0 / decrease / do not end at nbins, no segment, a segment without
+ * bins or with End < Begin, begins that decrease or ends that do not increase within a chromosome (MergeIn would drop the bins of a segment that ends where its
+ * predecessor ends), * positions that decrease within a chromosome or negative counts (the message names the site), * no kept site, * a non-finite count.
+ * The call waits three times (site table and scalars; per-segment results; run medians). */
+int32_t canvas_call_diploid(canvas_ctx* ctx, int64_t nbins, const float* d_count, int32_t nchr, const int64_t* h_chr_seg_offset /* nchr+1 */, const int32_t* h_seg_begin,
+                            const int32_t* h_seg_end, const int64_t* h_seg_bin_offset /* nseg+1 */, const int64_t* h_chr_site_offset /* nchr+1 */, const int32_t* d_site_pos,
+                            const int32_t* d_site_ref, const int32_t* d_site_alt, const double* h_logistic4,
+                            double* h_seg_median_count, int64_t* h_seg_site_offset /* nseg+1 */, int32_t* h_seg_informative, double* h_seg_median_maf, int32_t* h_seg_cn,
+                            int32_t* h_seg_mcc, double* h_seg_dist, double* h_seg_dist2, int32_t* h_seg_qscore,
+                            int64_t* h_nruns, int64_t* h_run_first, int64_t* h_run_last, int32_t* h_run_qscore, int32_t* h_run_filter, double* h_run_median_count,
+                            double* h_scalars2, int64_t* h_info4);
+
 /* ---- profiling hooks (hipEvent pairs recorded on the context's stream around the named kernels) --------------------- */
 /* on: 0 off; 1 every named scope; 2 only the scopes around the dominant (HBM-bound) kernel of CanvasBin — "bin_summary", "bin_summary_packed", "bin_pass",
    "bin_tile_stats" — so that a timed pass carries two event records instead of a dozen (each scope costs two barrier packets on the stream) */
