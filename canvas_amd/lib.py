@@ -27,10 +27,60 @@ ABI_SYMBOLS = [
     "canvas_memcpy_h2d_async", "canvas_snv_count", "canvas_flag_unique_kmers", "canvas_fasta_case_from_mask",
     "canvas_smooth", "canvas_smooth_lengths", "canvas_smooth_plan",
     "canvas_segment_select", "canvas_segment_select_plan", "canvas_call_diploid",
+    "canvas_somatic_model_fit",
 ]
 
 
-BACKBONE_PROBE_UNTOUCHED = 0x7FF8C0DEC0DEC0DE      # bits of the carries canvas_hmm_backbone_probe leaves alone (a quiet NaN no sum produces)
+SOMATIC_TILE, SOMATIC_MAX_CN = 256, 10                        # CANVAS_SOMATIC_TILE (segments per tile of the model-fit kernel), CANVAS_SOMATIC_MAX_CN
+ERR_SOMATIC_NO_MODEL, ERR_SOMATIC_NO_SCORE = -6, -7
+SOMATIC_INFO_CLUSTER_TERM, SOMATIC_INFO_INDEX_CUTOFF = 1, 2
+SOMATIC_MODEL_VALID, SOMATIC_MODEL_SCORED = 1, 2
+# SomaticCallerParameters.json, as far as Canvas.somatic_model_fit reads it
+SOMATIC_DEFAULTS = dict(maximum_copy_number=8, deviation_index_cutoff=11, maximum_related_models=5, min_allowed_ploidy=0.5, max_allowed_ploidy=8.0, deviation_factor=1.75,
+                        cn2_weighting_factor=0.175, deviation_score_weighting_factor=0.375, diploid_distance_score_weighting_factor=0.125,
+                        heterogeneity_score_weighting_factor=0.202)
+
+
+class SomaticParams(C.Structure):
+    _fields_ = [("maximum_copy_number", C.c_int32), ("deviation_index_cutoff", C.c_int32), ("maximum_related_models", C.c_int32),
+                ("min_allowed_ploidy", C.c_float), ("max_allowed_ploidy", C.c_float), ("deviation_factor", C.c_float),
+                ("cn2_weighting_factor", C.c_double), ("deviation_score_weighting_factor", C.c_double), ("diploid_distance_score_weighting_factor", C.c_double),
+                ("heterogeneity_score_weighting_factor", C.c_double)]
+
+
+class SomaticGrid(C.Structure):
+    _fields_ = [("min_coverage", C.c_int32), ("max_coverage", C.c_int32), ("minimum_purity_hard_limit", C.c_int32), ("fixed_percent_purity", C.c_int32),
+                ("fixed_coverage", C.c_int32), ("is_enrichment", C.c_int32), ("min_minor_allele_coverage", C.c_double), ("coverage_weighting_factor", C.c_double),
+                ("genome_length", C.c_int64)]
+
+
+class SomaticResult(C.Structure):
+    _fields_ = [("best_model", C.c_int32), ("best_coverage", C.c_int32), ("best_percent_purity", C.c_int32), ("info", C.c_uint32),
+                ("nmodels", C.c_int32), ("nvalid", C.c_int32), ("nscored", C.c_int32), ("reserved", C.c_int32),
+                ("diploid_coverage", C.c_double), ("purity", C.c_double), ("deviation", C.c_double), ("precision_deviation", C.c_double), ("accuracy_deviation", C.c_double),
+                ("ploidy", C.c_double), ("percent_normal", C.c_double), ("diploid_distance", C.c_double), ("percent_cn", C.c_double * (SOMATIC_MAX_CN + 1)),
+                ("score", C.c_double), ("inter_model_distance", C.c_double), ("best_deviation", C.c_double), ("worst_allowed_deviation", C.c_double),
+                ("host_table_ms", C.c_double), ("upload_ms", C.c_double), ("device_ms", C.c_double), ("selection_ms", C.c_double)]
+
+
+class SomaticModels(C.Structure):
+    _fields_ = [("capacity", C.c_int64), ("coverage", C.c_void_p), ("percent_purity", C.c_void_p), ("deviation", C.c_void_p), ("precision_deviation", C.c_void_p),
+                ("accuracy_deviation", C.c_void_p), ("ploidy", C.c_void_p), ("percent_normal", C.c_void_p), ("percent_cn", C.c_void_p), ("diploid_distance", C.c_void_p),
+                ("flags", C.c_void_p), ("score", C.c_void_p)]
+
+
+def somatic_grid(min_coverage, max_coverage, minimum_purity_hard_limit, min_minor_allele_coverage, fixed_percent_purity=-1, fixed_coverage=-1):
+    """the (diploid coverage, percent purity) models of the search in its order (SomaticCaller.cs:1899-1914), as canvas_somatic_model_fit lays them out"""
+    lo, hi = (fixed_coverage, fixed_coverage) if fixed_coverage >= 0 else (min_coverage, max_coverage)
+    models = []
+    for cov in range(lo, hi + 1):
+        p0 = int(max(float(minimum_purity_hard_limit), 100 * (1 - 2 * min_minor_allele_coverage / cov) - 10))
+        p0, p1 = (fixed_percent_purity, fixed_percent_purity) if fixed_percent_purity >= 0 else (p0, 100)
+        models += [(cov, p) for p in range(p0, p1 + 1)]
+    return models
+
+
+BACKBONE_PROBE_UNTOUCHED = 0x7FF8C0DEC0DEC0DE     # bits of the carries canvas_hmm_backbone_probe leaves alone (a quiet NaN no sum produces)
 
 
 class CanvasError(RuntimeError):
@@ -707,6 +757,69 @@ class Canvas:
                    diploid_coverage=float(scal[0]), mean_coverage=float(scal[1]), kept_sites=int(info[0]), integer_sum=bool(info[1]))
         if seg_start_ci is not None and seg_end_ci is not None:
             out.update(run_start_ci=np.asarray(seg_start_ci)[f], run_end_ci=np.asarray(seg_end_ci)[l])
+        return out
+
+    def somatic_model_fit(self, coverage, maf, weight, length, coverage_weighting_factor, genome_length, min_coverage, max_coverage, minimum_purity_hard_limit=20,
+                          min_minor_allele_coverage=0.0, is_enrichment=False, fixed_percent_purity=-1, fixed_coverage=-1, all_models=True, **params):
+        """CanvasSomaticCaller's purity / ploidy grid search (canvas_somatic_model_fit; ModelOverallCoverageAndPurity, SomaticCaller.cs:1870-2117) over the usable segments:
+        coverage / maf (< 0: none) / weight as float64 and length (End - Begin) as int32, all four numpy arrays or all four tensors on the context's device (per-segment median
+        count and upper median of the folded frequencies are what Canvas.segment_select gives).  coverage_weighting_factor is CoverageWeightingFactor (already divided by the
+        median level); **params override SOMATIC_DEFAULTS.  Returns a dict: the best model (model, coverage, percent_purity, purity, diploid_coverage, deviation,
+        precision_deviation, accuracy_deviation, ploidy, percent_normal, diploid_distance, percent_cn, score, inter_model_distance), info, nmodels / nvalid / nscored,
+        best_deviation, worst_allowed_deviation, seg_point / seg_distance (the best model's assignment), times_ms (host_table, upload, device, selection) and, with
+        all_models, `models`: one array per column of PurityModel.txt in grid order.  CanvasError carries .code (ERR_SOMATIC_NO_MODEL, ERR_SOMATIC_NO_SCORE, -1) and,
+        for the two somatic codes, .partial with what was filled."""
+        torch = self.torch
+        on_device = hasattr(coverage, "data_ptr")
+        arrs = (coverage, maf, weight, length)
+        if on_device:
+            for t, dt in zip(arrs, (torch.float64, torch.float64, torch.float64, torch.int32)):
+                assert hasattr(t, "data_ptr") and t.dtype == dt and t.is_contiguous() and t.dim() == 1 and t.numel() == coverage.numel() and t.device == self.device, \
+                    "somatic_model_fit: float64 coverage / maf / weight and int32 length, dense and on the context's device"
+            nseg = coverage.numel()
+            ptrs = [C.c_void_p(t.data_ptr()) for t in arrs]
+            torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        else:
+            arrs = tuple(np.ascontiguousarray(a, dt) for a, dt in zip(arrs, (np.float64, np.float64, np.float64, np.int32)))
+            nseg = len(arrs[0])
+            assert all(a.ndim == 1 and len(a) == nseg for a in arrs), "somatic_model_fit: one coverage, maf, weight and length per segment"
+            ptrs = [_np_ptr(a) for a in arrs]
+        unknown = set(params) - set(SOMATIC_DEFAULTS)
+        if unknown:
+            raise TypeError("somatic_model_fit: unknown parameters %s" % sorted(unknown))
+        sp = SomaticParams(**dict(SOMATIC_DEFAULTS, **params))
+        grid = SomaticGrid(int(min_coverage), int(max_coverage), int(minimum_purity_hard_limit), int(fixed_percent_purity), int(fixed_coverage), int(bool(is_enrichment)),
+                           float(min_minor_allele_coverage), float(coverage_weighting_factor), int(genome_length))
+        res = SomaticResult()
+        n1 = max(nseg, 1)
+        seg_point = np.zeros(n1, np.int32); seg_distance = np.zeros(n1, np.float64)
+        cols, sm = {}, None
+        if all_models:
+            cap = 0
+            lo, hi = (grid.fixed_coverage, grid.fixed_coverage) if grid.fixed_coverage >= 0 else (grid.min_coverage, grid.max_coverage)
+            if 1 <= lo and hi <= 100000 and np.isfinite(grid.min_minor_allele_coverage):      # otherwise the call refuses the grid
+                cap = len(somatic_grid(grid.min_coverage, grid.max_coverage, grid.minimum_purity_hard_limit, grid.min_minor_allele_coverage, grid.fixed_percent_purity, grid.fixed_coverage))
+            c1 = max(cap, 1)
+            cols = dict(coverage=np.zeros(c1, np.int32), percent_purity=np.zeros(c1, np.int32), deviation=np.zeros(c1), precision_deviation=np.zeros(c1), accuracy_deviation=np.zeros(c1),
+                        ploidy=np.zeros(c1), percent_normal=np.zeros(c1), percent_cn=np.zeros((c1, SOMATIC_MAX_CN + 1)), diploid_distance=np.zeros(c1), flags=np.zeros(c1, np.int32), score=np.zeros(c1))
+            sm = SomaticModels(cap, *[c.ctypes.data for c in cols.values()])
+        fn = self.lib.canvas_somatic_model_fit
+        fn.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = fn(self.ctx, nseg, *ptrs, int(on_device), C.byref(grid), C.byref(sp), C.byref(res), _np_ptr(seg_point), _np_ptr(seg_distance), C.byref(sm) if sm is not None else None)
+        M = res.nmodels
+        out = dict(model=res.best_model, coverage=res.best_coverage, percent_purity=res.best_percent_purity, info=res.info, nmodels=M, nvalid=res.nvalid, nscored=res.nscored,
+                   diploid_coverage=res.diploid_coverage, purity=res.purity, deviation=res.deviation, precision_deviation=res.precision_deviation,
+                   accuracy_deviation=res.accuracy_deviation, ploidy=res.ploidy, percent_normal=res.percent_normal, diploid_distance=res.diploid_distance,
+                   percent_cn=np.array(res.percent_cn[:sp.maximum_copy_number + 1]), score=res.score, inter_model_distance=res.inter_model_distance,
+                   best_deviation=res.best_deviation, worst_allowed_deviation=res.worst_allowed_deviation, seg_point=seg_point[:nseg], seg_distance=seg_distance[:nseg],
+                   times_ms=dict(host_table=res.host_table_ms, upload=res.upload_ms, device=res.device_ms, selection=res.selection_ms))
+        if all_models:
+            out["models"] = {k: (v[:M, :sp.maximum_copy_number + 1] if k == "percent_cn" else v[:M]) for k, v in cols.items()}
+        if rc != 0:
+            e = CanvasError(f"libcanvas_hip error {rc}: {self.lib.canvas_last_error(self.ctx).decode()}")
+            e.code = rc
+            e.partial = out if rc in (ERR_SOMATIC_NO_MODEL, ERR_SOMATIC_NO_SCORE) else None
+            raise e
         return out
 
     def segment_ids(self, chr_offset, state, start, stop, max_inter_bin_dist=1000000, excluded=None, out=None, ploidy=None):

@@ -147,6 +147,40 @@ namespace CanvasHipInterop
             double[] segMedianCount, long[] segSiteOffset, int[] segInformative, double[] segMedianMaf, int[] segCn, int[] segMcc, double[] segDist, double[] segDist2, int[] segQScore,
             out long nRuns, long[] runFirst, long[] runLast, int[] runQScore, int[] runFilter, double[] runMedianCount, double[] scalars2, long[] info4);
 
+        // CanvasSomaticCaller.ModelOverallCoverageAndPurity's grid search (SomaticCaller.cs:1870-2117) over the usable segments (coverage / maf / weight double, length int:
+        // device arrays when inputsOnDevice != 0, host arrays otherwise); the structs mirror include/canvas_hip.h field by field.  The cluster term of ModelDeviation is not
+        // built: SomaticInfoClusterTerm in result.info says when the reference would have added it.  segPoint / segDistance (nseg, or IntPtr.Zero) and models (or IntPtr.Zero)
+        public const int ErrSomaticNoModel = -6, ErrSomaticNoScore = -7, SomaticTile = 256, SomaticMaxCn = 10;
+        public const uint SomaticInfoClusterTerm = 1, SomaticInfoIndexCutoff = 2;
+        [StructLayout(LayoutKind.Sequential)] public struct canvas_somatic_params
+        {
+            public int maximum_copy_number, deviation_index_cutoff, maximum_related_models;
+            public float min_allowed_ploidy, max_allowed_ploidy, deviation_factor;
+            public double cn2_weighting_factor, deviation_score_weighting_factor, diploid_distance_score_weighting_factor, heterogeneity_score_weighting_factor;
+        }
+        [StructLayout(LayoutKind.Sequential)] public struct canvas_somatic_grid
+        {
+            public int min_coverage, max_coverage, minimum_purity_hard_limit, fixed_percent_purity, fixed_coverage, is_enrichment;
+            public double min_minor_allele_coverage, coverage_weighting_factor;
+            public long genome_length;
+        }
+        [StructLayout(LayoutKind.Sequential)] public unsafe struct canvas_somatic_result
+        {
+            public int best_model, best_coverage, best_percent_purity;
+            public uint info;
+            public int nmodels, nvalid, nscored, reserved;
+            public double diploid_coverage, purity, deviation, precision_deviation, accuracy_deviation, ploidy, percent_normal, diploid_distance;
+            public fixed double percent_cn[11];
+            public double score, inter_model_distance, best_deviation, worst_allowed_deviation, host_table_ms, upload_ms, device_ms, selection_ms;
+        }
+        [StructLayout(LayoutKind.Sequential)] public struct canvas_somatic_models
+        {
+            public long capacity;
+            public IntPtr coverage, percent_purity, deviation, precision_deviation, accuracy_deviation, ploidy, percent_normal, percent_cn, diploid_distance, flags, score;
+        }
+        [DllImport(Lib)] public static extern int canvas_somatic_model_fit(IntPtr ctx, long nseg, IntPtr coverage, IntPtr maf, IntPtr weight, IntPtr length, int inputsOnDevice,
+            ref canvas_somatic_grid grid, ref canvas_somatic_params parameters, out canvas_somatic_result result, IntPtr segPoint, IntPtr segDistance, IntPtr models);
+
         /// <summary>Turns a non-zero status into the module's own failure convention (message on stderr, exit code 1).</summary>
         public static void Check(IntPtr ctx, int status, string what)
         {

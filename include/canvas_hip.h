@@ -653,6 +653,82 @@ int32_t canvas_call_diploid(canvas_ctx* ctx, int64_t nbins, const float* d_count
                             int64_t* h_nruns, int64_t* h_run_first, int64_t* h_run_last, int32_t* h_run_qscore, int32_t* h_run_filter, double* h_run_median_count,
                             double* h_scalars2, int64_t* h_info4);
 
+/* ---- CanvasSomaticCaller: the purity / ploidy model fit (CanvasSomaticCaller/SomaticCaller.cs:1870-2117, ModelOverallCoverageAndPurity's grid search) ---- */
+#define CANVAS_SOMATIC_TILE 256                /* segments per tile of the device kernel: more segments than this take its tile loop */
+#define CANVAS_SOMATIC_MAX_CN 10               /* largest MaximumCopyNumber: PercentCN rows always hold CANVAS_SOMATIC_MAX_CN + 1 entries (0 beyond MaximumCopyNumber) */
+#define CANVAS_ERR_SOMATIC_NO_MODEL (-6)       /* no model passes the ploidy filter (the reference throws UncallableDataException, :1934-1937) */
+#define CANVAS_ERR_SOMATIC_NO_SCORE (-7)       /* no model scores above 0 (the reference dereferences a null bestModel, :2061) */
+#define CANVAS_SOMATIC_INFO_CLUSTER_TERM 1u    /* result.info: not enrichment, more than 100 segments and more than 100 with a MAF: the reference would have added ClusterDeviation */
+#define CANVAS_SOMATIC_INFO_INDEX_CUTOFF 2u    /* result.info: fewer than DeviationIndexCutoff models within DeviationFactor, worstAllowedDeviation came from the sorted deviations */
+#define CANVAS_SOMATIC_MODEL_VALID 1           /* models.flags: passed the ploidy filter (allModels) */
+#define CANVAS_SOMATIC_MODEL_SCORED 2          /* models.flags: Deviation <= worstAllowedDeviation, has a score (bestModels; a row of PurityModel.txt) */
+/* SomaticCallerParameters as this entry reads them; the comments give SomaticCallerParameters.json */
+typedef struct canvas_somatic_params {
+    int32_t maximum_copy_number;               /* 8; 2 .. 10 */
+    int32_t deviation_index_cutoff;            /* 11 */
+    int32_t maximum_related_models;            /* 5; 1 .. 64 */
+    float min_allowed_ploidy;                  /* 0.5 */
+    float max_allowed_ploidy;                  /* 8 */
+    float deviation_factor;                    /* 1.75 */
+    double cn2_weighting_factor;               /* 0.175 */
+    double deviation_score_weighting_factor;   /* 0.375 */
+    double diploid_distance_score_weighting_factor; /* 0.125 */
+    double heterogeneity_score_weighting_factor;    /* 0.202 (multiplies a heterogeneity index that is 0 here) */
+} canvas_somatic_params;
+/* the scalars of the search and its grid: diploid coverage min_coverage .. max_coverage, and per coverage the purities
+ * (int)max(minimum_purity_hard_limit, 100 * (1 - 2 * min_minor_allele_coverage / coverage) - 10) .. 100 percent (:1907) */
+typedef struct canvas_somatic_grid {
+    int32_t min_coverage, max_coverage;        /* 1 .. 100000 */
+    int32_t minimum_purity_hard_limit;         /* 5 or 20 in the reference; 0 .. 99 */
+    int32_t fixed_percent_purity;              /* < 0: none; else the one purity of every coverage, (int)(userPurity * 100) */
+    int32_t fixed_coverage;                    /* < 0: none; else the one coverage, (int)GetDiploidCoverage(median, userPloidy) */
+    int32_t is_enrichment;
+    double min_minor_allele_coverage;
+    double coverage_weighting_factor;          /* CoverageWeightingFactor: already divided by the median coverage level */
+    int64_t genome_length;
+} canvas_somatic_grid;
+typedef struct canvas_somatic_result {
+    int32_t best_model;                        /* index in grid order (coverage outer, purity inner); -1 when there is none */
+    int32_t best_coverage, best_percent_purity;
+    uint32_t info;                             /* CANVAS_SOMATIC_INFO_* */
+    int32_t nmodels, nvalid, nscored, reserved;
+    /* the best model's CoveragePurityModel */
+    double diploid_coverage, purity /* percent / 100f, widened */, deviation, precision_deviation, accuracy_deviation, ploidy, percent_normal, diploid_distance;
+    double percent_cn[CANVAS_SOMATIC_MAX_CN + 1];
+    double score, inter_model_distance;
+    double best_deviation, worst_allowed_deviation;
+    double host_table_ms, upload_ms, device_ms, selection_ms;   /* wall time of the call's four parts */
+} canvas_somatic_result;
+/* every model's columns of PurityModel.txt, in grid order; any pointer may be NULL */
+typedef struct canvas_somatic_models {
+    int64_t capacity;                          /* models each array holds; CANVAS_ERR_CAPACITY when the grid has more */
+    int32_t* coverage; int32_t* percent_purity;
+    double* deviation; double* precision_deviation; double* accuracy_deviation; double* ploidy; double* percent_normal;
+    double* percent_cn;                        /* capacity * (CANVAS_SOMATIC_MAX_CN + 1) */
+    double* diploid_distance;
+    int32_t* flags;                            /* CANVAS_SOMATIC_MODEL_* */
+    double* score;                             /* 0 where the model has none */
+} canvas_somatic_models;
+/* Fits every (diploid coverage, purity) model of the grid to nseg usable segments and selects the best one.  coverage / maf (< 0: none) / weight (double) and length
+ * (int32, End - Begin) are device arrays when inputs_on_device is not 0 and host arrays otherwise.
+ * Per model, bit for bit as the reference: the model points in InitializePloidies' order with InitializeModelPoints(model) and AdjustedMAF (host libm, host threads, one
+ * upload); on the device RefineDiploidMAF, the clustering loop of ModelDeviation, the accuracy deviation, PercentCN, Ploidy, PercentNormal, Deviation = 0.5f * precision +
+ * 0.5f * accuracy and DiploidModelDistance, every sum over segments in segment order, without fused multiply-adds.  On the host the selection of :1921-2116: ploidy filter,
+ * worstAllowedDeviation with the DeviationIndexCutoff fallback, the four sub-scores, the first model with the strictly highest score, and InterModelDistance over the
+ * first MaximumRelatedModels models of the stable order by -score.  h_seg_point / h_seg_distance (nseg each, may be NULL): the best model's info.Ploidy.Index and
+ * info.Distance after the final ModelDeviation call.
+ * NOT built: the cluster term of ModelDeviation (ClusterDeviation, :1309-1313, needs the centroids of the mean-shift / density clustering).  The result equals the
+ * reference's where the reference skips that term: enrichment data, at most 100 segments, or at most 100 segments with a MAF.  Otherwise the two-term deviation is still
+ * computed and CANVAS_SOMATIC_INFO_CLUSTER_TERM is set.  The ploidies' pure-tumour MinorAlleleFrequency (EstimateDiploidMAF of MeanCoverage) is not an input: the
+ * search never reads it (InitializeModelPoints(model) takes every point's MAF from AdjustedMAF).  The de-duplicated-model probe (:2058-2080) only logs and is left out.
+ * CANVAS_ERR_INVALID: nseg < 3, a total weight of 0, a negative length or one whose product with MaximumCopyNumber leaves int32, a coverage or weight that is not finite
+ * or a MAF that is NaN, an empty grid, a parameter outside the ranges above.  All of that except the segment checks of device inputs is decided before the context
+ * is looked at; *h_result is then cleared and nmodels set, also with a NULL ctx (which returns CANVAS_ERR_INVALID).  CANVAS_ERR_SOMATIC_NO_MODEL / _NO_SCORE: the
+ * per-model arrays and nmodels / nvalid / nscored are filled, best_model is -1.  The call waits for its result. */
+int32_t canvas_somatic_model_fit(canvas_ctx* ctx, int64_t nseg, const double* coverage, const double* maf, const double* weight, const int32_t* length,
+                                 int32_t inputs_on_device, const canvas_somatic_grid* grid, const canvas_somatic_params* params, canvas_somatic_result* h_result,
+                                 int32_t* h_seg_point, double* h_seg_distance, const canvas_somatic_models* h_models);
+
 /* ---- profiling hooks (hipEvent pairs recorded on the context's stream around the named kernels) --------------------- */
 /* on: 0 off; 1 every named scope; 2 only the scopes around the dominant (HBM-bound) kernel of CanvasBin — "bin_summary", "bin_summary_packed", "bin_pass",
    "bin_tile_stats" — so that a timed pass carries two event records instead of a dozen (each scope costs two barrier packets on the stream) */
