@@ -1,3 +1,4 @@
+// (canvas_call_somatic, CanvasSomaticCaller's calls around the model fit, is the last section of this file: it shares the site kernels and the selects below.)
 // CanvasDiploidCaller, first layer: exact order statistics of MANY segments of a float32 array in one fixed sequence of launches (canvas_segment_select).
 // The caller's per-segment numbers are all of this kind: medianCoverage = Utilities.Median(float[]) of a segment's counts (CanvasDiploidCaller.cs, AssignPloidyCallsDistance),
 // medianMaf = the median of its folded allele frequencies widened to double, MedianCount of a merged run (CanvasSegment.cs, doubles converted from floats), and the
@@ -540,5 +541,507 @@ extern "C" int32_t canvas_call_diploid(canvas_ctx* ctx, int64_t nbins, const flo
     CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                                                        // ---- the third wait
     *h_nruns = nruns; h_scalars2[0] = diploidCoverage; h_scalars2[1] = meanCoverage;
     if (h_info4) { h_info4[0] = (int64_t)hSt->kept; h_info4[1] = integerPath; h_info4[2] = (int64_t)hSt->covSum; h_info4[3] = 0; }
+    return CANVAS_OK;
+}
+
+// ================================================================ canvas_call_somatic: CanvasSomaticCaller.CallVariants around canvas_somatic_model_fit ======================
+// Stage 1 is canvas_call_diploid's (the same reader): k_call_sites / k_call_scan / k_call_scatter / k_call_segoff and the selects.  New here:
+//   k_scall_to_float   the per-segment medians as floats (enrichment: the list of Convert.ToSingle(Median(Counts)) that Quartiles sorts)
+//   k_scall_usable     info.Coverage / Maf / Weight of every segment, gathered to the usable segments' dense arrays the fit reads
+//   k_scall_compact    the bins of the usable segments at reference copy number 2, packed for the select of medianCoverageLevel (one thread per bin, its segment by bisection)
+//   k_scall_assign     AssignPloidyCalls' scan over the ploidy table of the best model, one thread per segment, strict < / else-if <, double without contraction
+//   k_scall_mean       MeanCount of the segments whose best ploidy is MaximumCopyNumber, one workgroup per segment.  The reference's LINQ Sum adds the floats into a double in
+//                      bin order and rounds the total to float.  Counts that are non-negative multiples of 2^e with n * max < 2^(53 + e) make every partial sum of that loop a
+//                      multiple of 2^e below 2^(53 + e), hence exact, so any order gives its bits: the workgroup finds e and max, and when the bound holds adds the counts as
+//                      integers of 2^e (EXACT).  Otherwise lane 0 adds them in bin order out of LDS tiles (WALK).  CANVAS_SOMATIC_MEAN=walk (test hook) sends every segment there.
+#include "somatic_points.hpp"
+#define SC_MAXP 36
+#define SC_WALK_TILE 1024
+struct ScModel { double cov[SC_MAXP], maf[SC_MAXP], hcov[SC_MAXP]; int cn[SC_MAXP], major[SC_MAXP]; double cwf; int P, maxCN; };
+
+__global__ void __launch_bounds__(CL_BLOCK) k_scall_to_float(const double* __restrict__ in, long long n, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (i < n) out[i] = (float)in[i];
+}
+__global__ void __launch_bounds__(CL_BLOCK) k_scall_usable(long long nseg, const int* __restrict__ segBegin, const int* __restrict__ segEnd, const long long* __restrict__ segOff,
+                                                           const double* __restrict__ medCount, const double* __restrict__ mafUpper, const int* __restrict__ dense, int threshold,
+                                                           double* __restrict__ cov, double* __restrict__ maf, double* __restrict__ weight,
+                                                           double* __restrict__ uCov, double* __restrict__ uMaf, double* __restrict__ uW, int* __restrict__ uLen) {
+    const long long s = (long long)blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (s >= nseg) return;
+    const long long nf = segOff[s + 1] - segOff[s];
+    const int len = segEnd[s] - segBegin[s];
+    const double c = medCount[s], m = nf < threshold ? -1.0 : mafUpper[s];
+    double w = (double)len;
+    if (nf < 10) w *= (double)nf / 10;
+    cov[s] = c; maf[s] = m; weight[s] = w;
+    const int d = dense[s];                                    // position among the usable segments, -1: not usable
+    if (d >= 0) { uCov[d] = c; uMaf[d] = m; uW[d] = w; uLen[d] = len; }
+}
+__global__ void __launch_bounds__(CL_BLOCK) k_scall_compact(const float* __restrict__ count, long long nbins, long long nseg, const long long* __restrict__ binOff,
+                                                            const long long* __restrict__ dst, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (i >= nbins) return;
+    long long lo = 0, hi = nseg;                               // the segment with binOff[s] <= i < binOff[s + 1] (binOff runs from 0 to nbins, no empty segment)
+    while (hi - lo > 1) { const long long mid = (lo + hi) >> 1; if (binOff[mid] <= i) lo = mid; else hi = mid; }
+    const long long d = dst[lo];
+    if (d >= 0) out[d + (i - binOff[lo])] = count[i];
+}
+__global__ void __launch_bounds__(CL_BLOCK) k_scall_assign(long long nseg, const long long* __restrict__ segOff, const double* __restrict__ medCount, const double* __restrict__ mafUpper,
+                                                           const int* __restrict__ refCn, const ScModel* __restrict__ model, int* __restrict__ cn, int* __restrict__ cn2,
+                                                           int* __restrict__ mcc, double* __restrict__ dist, double* __restrict__ dist2) {
+    const long long s = (long long)blockIdx.x * CL_BLOCK + threadIdx.x;
+    if (s >= nseg) return;
+    const bool hasMaf = segOff[s + 1] - segOff[s] >= 10;
+    const double coverage = medCount[s], maf = hasMaf ? mafUpper[s] : -1.0, cwf = model->cwf;
+    const bool haploid = refCn && refCn[s] == 1;
+    double best = 1.7976931348623157e308, second = 1.7976931348623157e308; int bi = -1, si = -1;
+    for (int p = 0; p < model->P; p++) {
+        const double targetCoverage = haploid ? model->hcov[p] : model->cov[p], targetMaf = haploid ? 0.0 : model->maf[p];
+        double diff = (coverage - targetCoverage) * cwf;
+        double distance = diff * diff;
+        if (!hasMaf || maf < 0) distance = 2 * distance;
+        else { diff = maf - targetMaf; distance += diff * diff; }
+        if (distance < best) { second = best; si = bi; best = distance; bi = p; }
+        else if (distance < second) { second = distance; si = p; }
+    }
+    cn[s] = bi < 0 ? -1 : model->cn[bi];
+    cn2[s] = si < 0 ? -1 : model->cn[si];
+    mcc[s] = (bi < 0 || !hasMaf) ? -1 : model->major[bi];
+    dist[s] = best; dist2[s] = second;
+}
+__global__ void __launch_bounds__(CL_BLOCK) k_scall_mean(const float* __restrict__ count, const long long* __restrict__ binOff, const int* __restrict__ cn, int maxCN, int forceWalk,
+                                                         double* __restrict__ mean, int* __restrict__ route) {
+    __shared__ int sE[CL_BLOCK / 64]; __shared__ float sM[CL_BLOCK / 64]; __shared__ int sBad[CL_BLOCK / 64]; __shared__ unsigned long long sU[CL_BLOCK / 64];
+    __shared__ float tile[SC_WALK_TILE]; __shared__ double sSum;
+    const long long s = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (cn[s] != maxCN) { if (tid == 0) { mean[s] = 0.0; route[s] = CANVAS_SOMATIC_MEAN_NONE; } return; }      // (block-uniform)
+    const long long o = binOff[s], n = binOff[s + 1] - o;
+    int emin = 0x7FFFFFFF; float vmax = 0.0f; bool bad = false;
+    for (long long i = tid; i < n; i += CL_BLOCK) {
+        const float v = count[o + i];
+        const uint32_t u = __float_as_uint(v), e = (u >> 23) & 255u, m = u & 0x7FFFFFu;
+        if ((u >> 31) || e == 255u) bad = true;                 // negative (-0.0 included) or not finite: no proof
+        else if (u) { const int low = e ? (int)e - 150 + __builtin_ctz(m | 0x800000u) : -149 + __builtin_ctz(m); emin = min(emin, low); vmax = fmaxf(vmax, v); }
+    }
+    for (int d = 32; d; d >>= 1) { emin = min(emin, __shfl_xor(emin, d)); vmax = fmaxf(vmax, __shfl_xor(vmax, d)); }
+    const bool anyBad = __ballot(bad) != 0;
+    if (lane == 0) { sE[w] = emin; sM[w] = vmax; sBad[w] = anyBad ? 1 : 0; }
+    __syncthreads();
+    bad = false;
+    for (int k = 0; k < CL_BLOCK / 64; k++) { emin = min(emin, sE[k]); vmax = fmaxf(vmax, sM[k]); bad = bad || sBad[k]; }      // (block-uniform from here)
+    const bool zero = emin == 0x7FFFFFFF;                       // every count is +0
+    const bool proven = !bad && !forceWalk && (zero || (double)n * (double)vmax < ldexp(1.0, 53 + emin));
+    double sum = 0.0;
+    if (proven) {
+        unsigned long long u = 0;
+        if (!zero) {
+            const double scale = ldexp(1.0, -emin);            // emin >= -149: finite; count * scale is an integer below 2^53
+            for (long long i = tid; i < n; i += CL_BLOCK) u += (unsigned long long)((double)count[o + i] * scale);
+        }
+        u = wave_reduce_add_u64(u);
+        if (lane == 0) sU[w] = u;
+        __syncthreads();
+        if (tid == 0) { unsigned long long t = 0; for (int k = 0; k < CL_BLOCK / 64; k++) t += sU[k]; sum = zero ? 0.0 : (double)t * ldexp(1.0, emin); }
+    } else {
+        if (tid == 0) sSum = 0.0;
+        for (long long t0 = 0; t0 < n; t0 += SC_WALK_TILE) {
+            const int m = (int)min((long long)SC_WALK_TILE, n - t0);
+            __syncthreads();
+            for (int i = tid; i < m; i += CL_BLOCK) tile[i] = count[o + t0 + i];
+            __syncthreads();
+            if (tid == 0) { double a = sSum; for (int i = 0; i < m; i++) a += (double)tile[i]; sSum = a; }
+        }
+        if (tid == 0) sum = sSum;
+    }
+    if (tid == 0) { mean[s] = (double)(float)sum / (double)n; route[s] = proven ? CANVAS_SOMATIC_MEAN_EXACT : CANVAS_SOMATIC_MEAN_WALK; }
+}
+
+// ComputeQScore(Logistic), SegmentScoringModel.cs:42-62 with the predictors of :121-125 and :151-160
+static int sc_qscore(const canvas_somatic_call_params& p, long long binCount, int cn, double dist, double dist2) {
+    const double logBins = log10((double)(1 + binCount));
+    double score = p.logistic_intercept;
+    score += logBins * p.logistic_log_bin_count;
+    score += (dist / std::max(1.0, cn - 4.0)) * p.logistic_model_distance;
+    score += (dist2 == 0 ? 0.0 : dist / dist2) * p.logistic_distance_ratio;
+    score += cn >= 15 ? logBins : 0.0;
+    score = exp(score);
+    score = score / (score + 1);
+    int q = cl_round_to_int(-10 * log10(1 - score));
+    q = std::min(60, q);
+    return std::max(2, q);
+}
+// Convert.ToInt32(float): round half to even; false when the result leaves int32 (OverflowException) or the value is NaN
+static bool sc_to_int32(float v, int& out) { const double r = nearbyint((double)v); if (!(r >= -2147483648.0 && r <= 2147483647.0)) return false; out = (int)r; return true; }
+
+extern "C" int32_t canvas_call_somatic(canvas_ctx* ctx, int64_t nbins, const float* d_count, int32_t nchr, const int64_t* h_chr_seg_offset, const int32_t* h_seg_begin,
+                                       const int32_t* h_seg_end, const int64_t* h_seg_bin_offset, const int64_t* h_chr_site_offset, const int32_t* d_site_pos,
+                                       const int32_t* d_site_ref, const int32_t* d_site_alt, const int32_t* h_seg_ref_cn, const int64_t* h_chr_excl_offset,
+                                       const int32_t* h_excl_start, const int32_t* h_excl_stop, const canvas_somatic_call_params* params, const canvas_somatic_call_out* out,
+                                       canvas_somatic_call_scalars* h_scalars, canvas_somatic_result* h_fit) {
+#define SC_REFUSE(msg) do { if (ctx) ctx->err = std::string("canvas_call_somatic: ") + (msg); return CANVAS_ERR_INVALID; } while (0)
+    if (nchr < 0 || nbins < 0 || !h_chr_seg_offset || !h_chr_site_offset || !params || !out || !h_scalars || !h_fit) SC_REFUSE("bad arguments");
+    if (h_chr_seg_offset[0] != 0 || h_chr_site_offset[0] != 0) SC_REFUSE("the chromosome offsets start at 0");
+    for (int c = 0; c < nchr; c++)
+        if (h_chr_seg_offset[c + 1] < h_chr_seg_offset[c] || h_chr_site_offset[c + 1] < h_chr_site_offset[c]) SC_REFUSE("the chromosome offsets must be non-decreasing");
+    const long long nseg = h_chr_seg_offset[nchr], nsites = h_chr_site_offset[nchr];
+    if (nseg > 0x7FFFFFFFll || nsites > (1ll << 36)) SC_REFUSE("too many segments or sites");
+    if (nseg == 0) SC_REFUSE("no segments");
+    const canvas_somatic_call_out& O = *out;
+    if (!h_seg_begin || !h_seg_end || !h_seg_bin_offset || !d_count || (nsites > 0 && (!d_site_pos || !d_site_ref || !d_site_alt)) || !O.seg_median_count || !O.seg_site_offset ||
+        !O.seg_maf_upper || !O.seg_usable || !O.seg_coverage || !O.seg_maf || !O.seg_weight || !O.seg_cn || !O.seg_cn2 || !O.seg_mcc || !O.seg_dist || !O.seg_dist2 || !O.seg_mean_count ||
+        !O.seg_mean_route || !O.seg_qscore || !O.seg_run || !O.run_owner || !O.run_begin || !O.run_end || !O.run_bin_count || !O.run_qscore || !O.run_filter)
+        SC_REFUSE("bad arguments (null array)");
+    if (h_seg_bin_offset[0] != 0 || h_seg_bin_offset[nseg] != nbins) SC_REFUSE("the segments' bin offsets run from 0 to nbins");
+    for (long long s = 0; s < nseg; s++) {
+        if (h_seg_bin_offset[s + 1] <= h_seg_bin_offset[s]) SC_REFUSE("segment " + std::to_string(s) + " has no bins (the reference's median of an empty list throws)");
+        if (h_seg_end[s] < h_seg_begin[s]) SC_REFUSE("segment " + std::to_string(s) + " ends before it begins");
+    }
+    for (int c = 0; c < nchr; c++)
+        for (long long s = h_chr_seg_offset[c] + 1; s < h_chr_seg_offset[c + 1]; s++)
+            if (h_seg_begin[s] < h_seg_begin[s - 1] || h_seg_end[s] <= h_seg_end[s - 1])
+                SC_REFUSE("within a chromosome the segments' begins must not decrease and their ends must increase (segment " + std::to_string(s) + ")");
+    if (h_chr_excl_offset) {
+        if (h_chr_excl_offset[0] != 0) SC_REFUSE("the excluded intervals' offsets start at 0");
+        for (int c = 0; c < nchr; c++) {
+            if (h_chr_excl_offset[c + 1] < h_chr_excl_offset[c]) SC_REFUSE("the excluded intervals' offsets must be non-decreasing");
+            if (h_chr_excl_offset[c + 1] > h_chr_excl_offset[c] && (!h_excl_start || !h_excl_stop)) SC_REFUSE("bad arguments (null excluded intervals)");
+            for (long long k = h_chr_excl_offset[c] + 1; k < h_chr_excl_offset[c + 1]; k++)
+                if (h_excl_start[k] < h_excl_start[k - 1]) SC_REFUSE("the excluded intervals of a chromosome must be sorted by start");
+        }
+    }
+    const canvas_somatic_call_params& P = *params;
+    const int maxCN = P.fit.maximum_copy_number;
+    if (maxCN < 2 || maxCN > CANVAS_SOMATIC_MAX_CN) SC_REFUSE("MaximumCopyNumber must be 2 .. 10");
+    if (!(P.lower_coverage_level_weighting_factor > 0) || !(P.upper_coverage_level_weighting_factor > 0) || !std::isfinite(P.lower_coverage_level_weighting_factor) ||
+        !std::isfinite(P.upper_coverage_level_weighting_factor)) SC_REFUSE("the coverage level weighting factors must be positive and finite");
+    if (!std::isfinite(P.coverage_weighting) || !std::isfinite(P.coverage_weighting_with_maf_segmentation) || !std::isfinite(P.evenness_score_threshold) || !std::isfinite(P.min_evenness_score) ||
+        !std::isfinite(P.logistic_intercept) || !std::isfinite(P.logistic_log_bin_count) || !std::isfinite(P.logistic_model_distance) || !std::isfinite(P.logistic_distance_ratio))
+        SC_REFUSE("the coverage weightings, evenness numbers and Logistic parameters must be finite");
+    if (P.user_ploidy == 0 || std::isnan(P.user_ploidy) || std::isnan(P.user_purity) || P.user_purity > 1) SC_REFUSE("a user ploidy must not be 0 and a user purity at most 1");
+    if (P.genome_length <= 0) SC_REFUSE("genome_length must be positive");
+#undef SC_REFUSE
+    *h_scalars = canvas_somatic_call_scalars{};
+    *h_fit = canvas_somatic_result{}; h_fit->best_model = -1;
+    if (!ctx) return CANVAS_ERR_INVALID;
+    auto fail = [&](int32_t code, const std::string& msg) { ctx->err = "canvas_call_somatic: " + msg; return code; };
+    CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    canvas_somatic_call_scalars& R = *h_scalars;
+    auto clock0 = std::chrono::steady_clock::now();
+    auto lap = [&]() { const auto now = std::chrono::steady_clock::now(); const double ms = std::chrono::duration<double, std::milli>(now - clock0).count(); clock0 = now; return ms; };
+
+    // ---- buffers that live across the selects and the fit (which carve ctx->ws)
+    const long long nb = (nsites + CL_BLOCK - 1) / CL_BLOCK;
+    const size_t S = (size_t)nseg;
+    WsSizer sz; sz.take<ClSiteStat>(1); sz.take<ScModel>(1); sz.take<long long>((size_t)nchr + 1); sz.take<long long>((size_t)nchr + 1); sz.take<int>(S); sz.take<int>(S);
+    sz.take<int>((size_t)nsites); sz.take<unsigned>((size_t)nb); sz.take<unsigned long long>((size_t)nb + 1); sz.take<float>((size_t)nsites); sz.take<int>((size_t)nsites);
+    sz.take<long long>(S + 1); sz.take<long long>(S + 1); sz.take<long long>(S); for (int k = 0; k < 11; k++) sz.take<double>(S); for (int k = 0; k < 7; k++) sz.take<int>(S);
+    sz.take<float>(S); sz.take<float>((size_t)nbins); sz.take<double>(4);
+    if (sz.off + 256 > ctx->call_ws_bytes) {
+        if (ctx->call_ws) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->call_ws)); ctx->call_ws = nullptr; ctx->call_ws_bytes = 0; }
+        const size_t want = sz.off + sz.off / 4 + (1u << 20);
+        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->call_ws, want)); ctx->call_ws_bytes = want;
+    }
+    WsCarver cv(ctx->call_ws);
+    ClSiteStat* dSt = cv.take<ClSiteStat>(1); ScModel* dModel = cv.take<ScModel>(1); long long* dChrSite = cv.take<long long>((size_t)nchr + 1); long long* dChrSeg = cv.take<long long>((size_t)nchr + 1);
+    int* dBegin = cv.take<int>(S); int* dEnd = cv.take<int>(S); int* dSiteSeg = cv.take<int>((size_t)nsites); unsigned* dBlockCnt = cv.take<unsigned>((size_t)nb);
+    unsigned long long* dBlockOff = cv.take<unsigned long long>((size_t)nb + 1); float* dMaf = cv.take<float>((size_t)nsites); int* dCseg = cv.take<int>((size_t)nsites);
+    long long* dSegOff = cv.take<long long>(S + 1); long long* dBinOff = cv.take<long long>(S + 1); long long* dDst = cv.take<long long>(S);
+    double* dMedCount = cv.take<double>(S); double* dMafUp = cv.take<double>(S); double* dCov = cv.take<double>(S); double* dMafU = cv.take<double>(S); double* dW = cv.take<double>(S);
+    double* dUCov = cv.take<double>(S); double* dUMaf = cv.take<double>(S); double* dUW = cv.take<double>(S); double* dDist = cv.take<double>(S); double* dDist2 = cv.take<double>(S);
+    double* dMean = cv.take<double>(S);                         // (11 arrays of doubles, then 7 of ints: the sizer's two loops)
+    int* dULen = cv.take<int>(S); int* dDense = cv.take<int>(S); int* dRefCn = cv.take<int>(S); int* dCn = cv.take<int>(S); int* dCn2 = cv.take<int>(S); int* dMcc = cv.take<int>(S);
+    int* dRoute = cv.take<int>(S);
+    float* dMedF = cv.take<float>(S); float* dCompact = cv.take<float>((size_t)nbins); double* dQ = cv.take<double>(4);
+    int32_t rc = canvas_pin_reserve(ctx, 256); if (rc) return rc;
+    unsigned long long* hBad = (unsigned long long*)ctx->pin;     // [0..3] the selects' flags, [4..8] ClSiteStat, [10..11] the two quartile medians
+    // (hBad[1] and hBad[3], the flags of the two selects over whole arrays, are not looked at: the per-segment select behind hBad[0] has read every one of those counts)
+    ClSiteStat* hSt = (ClSiteStat*)(hBad + 4);
+    double* hQ = (double*)(hBad + 10);
+    const unsigned long long none = ~0ull;
+    const bool enrichment = P.is_enrichment != 0;
+
+    // ---- stage 1 (and the select of stage 2's overallMedianCoverage): the first wait
+    { ClSiteStat z{0, 0, 0, 0, none}; rc = canvas_h2d_small(ctx, dSt, &z, sizeof(z)); if (rc) return rc; }
+    { std::vector<long long> t(h_chr_site_offset, h_chr_site_offset + nchr + 1); rc = canvas_h2d_small(ctx, dChrSite, t.data(), t.size() * sizeof(long long)); if (rc) return rc; }
+    { std::vector<long long> t(h_chr_seg_offset, h_chr_seg_offset + nchr + 1); rc = canvas_h2d_small(ctx, dChrSeg, t.data(), t.size() * sizeof(long long)); if (rc) return rc; }
+    { std::vector<long long> t(h_seg_bin_offset, h_seg_bin_offset + nseg + 1); rc = canvas_h2d_small(ctx, dBinOff, t.data(), t.size() * sizeof(long long)); if (rc) return rc; }
+    rc = canvas_h2d_small(ctx, dBegin, h_seg_begin, S * sizeof(int)); if (rc) return rc;
+    rc = canvas_h2d_small(ctx, dEnd, h_seg_end, S * sizeof(int)); if (rc) return rc;
+    if (h_seg_ref_cn) { rc = canvas_h2d_small(ctx, dRefCn, h_seg_ref_cn, S * sizeof(int)); if (rc) return rc; }
+    const unsigned segGrid = (unsigned)((nseg + 1 + CL_BLOCK - 1) / CL_BLOCK);
+    if (nsites > 0) {
+        ProfScope ps(ctx, "scall_sites");
+        hipLaunchKernelGGL(k_call_sites, dim3((unsigned)nb), dim3(CL_BLOCK), 0, ctx->stream, d_site_pos, d_site_ref, d_site_alt, nsites, dChrSite, dChrSeg, (int)nchr, dBegin, dEnd, dSiteSeg, dBlockCnt, dSt);
+        hipLaunchKernelGGL(k_call_scan, dim3(1), dim3(1024), 0, ctx->stream, dBlockCnt, nb, dBlockOff, dSt);
+        hipLaunchKernelGGL(k_call_scatter, dim3((unsigned)nb), dim3(CL_BLOCK), 0, ctx->stream, d_site_ref, d_site_alt, nsites, dSiteSeg, dBlockOff, dMaf, dCseg);
+    }
+    hipLaunchKernelGGL(k_call_segoff, dim3(segGrid), dim3(CL_BLOCK), 0, ctx->stream, dCseg, dSt, nseg, dSegOff);
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    rc = cl_segment_select_enqueue(ctx, d_count, nseg, h_seg_bin_offset, CL_MODE_MEDIAN_F32, dMedCount, hBad + 0); if (rc) return rc;
+    {
+        const int64_t all[2] = {0, enrichment ? (int64_t)nseg : nbins};
+        if (enrichment) hipLaunchKernelGGL(k_scall_to_float, dim3(segGrid), dim3(CL_BLOCK), 0, ctx->stream, dMedCount, nseg, dMedF);
+        rc = cl_segment_select_enqueue(ctx, enrichment ? dMedF : d_count, 1, all, CL_MODE_MEDIAN_F32, dQ, hBad + 1); if (rc) return rc;
+    }
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(hSt, dSt, sizeof(ClSiteStat), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(hQ, dQ, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_site_offset, dSegOff, (S + 1) * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_median_count, dMedCount, S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (hBad[0] != none) return fail(CANVAS_ERR_INVALID, "counts must be finite (first non-finite count at index " + std::to_string(hBad[0]) + ")");
+    if (hSt->unsorted != none) return fail(CANVAS_ERR_INVALID, "within a chromosome the sites' positions must not decrease and their counts must not be negative (site " + std::to_string(hSt->unsorted) + ")");
+    if (hSt->kept == 0) return fail(CANVAS_ERR_INVALID, "no site with ref + alt >= 10 inside a segment (the reference's Average() of an empty sequence throws)");
+    R.kept_sites = (int64_t)hSt->kept;
+    R.mean_coverage = (double)(long long)hSt->covSum / (double)(long long)hSt->kept;
+    const float q2 = (float)hQ[0];
+    R.overall_median_coverage = q2;
+    // ---- the upper medians of the folded frequencies: the second wait
+    rc = cl_segment_select_enqueue(ctx, dMaf, nseg, O.seg_site_offset, CL_MODE_UPPER, dMafUp, hBad + 2); if (rc) return rc;
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_maf_upper, dMafUp, S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (hBad[2] != none) return fail(CANVAS_ERR_INVALID, "a folded frequency is not finite");      // (cannot happen: ref + alt >= 10)
+    R.stage1_ms = lap();
+
+    // ---- stage 2: the threshold loop is arithmetic on the counts that are back
+    int threshold = P.minimum_variant_frequencies;
+    std::vector<int> dense(S, -1);
+    long long nusable = 0;
+    for (long long s = 0; s < nseg; s++) {
+        const int len = h_seg_end[s] - h_seg_begin[s];
+        const bool ok = !(len < 5000) && !(O.seg_median_count[s] > (double)q2 * 2);
+        O.seg_usable[s] = ok ? 1 : 0;
+        if (ok) dense[(size_t)s] = (int)nusable++;
+    }
+    while (true) {
+        long long validMafCount = 0;
+        for (long long s = 0; s < nseg; s++) if (O.seg_usable[s] && O.seg_site_offset[s + 1] - O.seg_site_offset[s] >= threshold) validMafCount++;
+        if (validMafCount > std::min<long long>(20, nseg)) break;
+        if (threshold <= 5) break;
+        threshold -= 15;
+        threshold = std::max(5, threshold);
+    }
+    R.threshold_used = threshold; R.nusable = nusable;
+    // ---- stage 3's compaction plan: the bins of the usable segments at reference copy number 2
+    std::vector<long long> dst(S, -1);
+    long long total = 0;
+    for (long long s = 0; s < nseg; s++)
+        if (O.seg_usable[s] && (!h_seg_ref_cn || h_seg_ref_cn[s] == 2)) { dst[(size_t)s] = total; total += h_seg_bin_offset[s + 1] - h_seg_bin_offset[s]; }
+    rc = canvas_h2d_small(ctx, dDense, dense.data(), S * sizeof(int)); if (rc) return rc;
+    rc = canvas_h2d_small(ctx, dDst, dst.data(), S * sizeof(long long)); if (rc) return rc;
+    hipLaunchKernelGGL(k_scall_usable, dim3(segGrid), dim3(CL_BLOCK), 0, ctx->stream, nseg, dBegin, dEnd, dSegOff, dMedCount, dMafUp, dDense, threshold, dCov, dMafU, dW, dUCov, dUMaf, dUW, dULen);
+    const bool level = nusable >= 3 && total > 0;
+    if (level) {
+        ProfScope ps(ctx, "scall_compact");
+        hipLaunchKernelGGL(k_scall_compact, dim3((unsigned)((nbins + CL_BLOCK - 1) / CL_BLOCK)), dim3(CL_BLOCK), 0, ctx->stream, d_count, (long long)nbins, nseg, dBinOff, dDst, dCompact);
+    }
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    if (level) {
+        const int64_t all[2] = {0, total};
+        rc = cl_segment_select_enqueue(ctx, dCompact, 1, all, CL_MODE_MEDIAN_F32, dQ + 1, hBad + 3); if (rc) return rc;
+        CANVAS_HIP_TRY(ctx, hipMemcpyAsync(hQ + 1, dQ + 1, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_coverage, dCov, S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_maf, dMafU, S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_weight, dW, S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                                                        // ---- the third wait
+    R.stages = 2; R.stage23_ms = lap();
+    if (nusable < 3) return fail(CANVAS_ERR_SOMATIC_FEW_SEGMENTS, "cannot model coverage/purity with less than 3 usable segments (" + std::to_string(nusable) + ")");
+
+    // ---- stage 3: the scalars
+    if (total == 0) return fail(CANVAS_ERR_INVALID, "no usable segment at reference copy number 2: the reference's Quartiles of an empty list indexes out of range");
+    int medianCoverageLevel = 0;
+    if (!sc_to_int32((float)hQ[1], medianCoverageLevel)) return fail(CANVAS_ERR_INVALID, "the median coverage level leaves int32");
+    R.median_coverage_level = medianCoverageLevel;
+    if (medianCoverageLevel < 1) return fail(CANVAS_ERR_INVALID, "the median coverage level is " + std::to_string(medianCoverageLevel) + ": the reference divides the coverage weighting by it");
+    double cwf;
+    if (!std::isnan(P.evenness_score) && P.evenness_score < P.evenness_score_threshold) {
+        if (P.coverage_weighting <= P.coverage_weighting_with_maf_segmentation) return fail(CANVAS_ERR_INVALID, "CoverageWeighting should be larger than CoverageWeightingWithMafSegmentation");
+        const double scaler = std::max(P.evenness_score - P.min_evenness_score, 0.0) / (P.evenness_score_threshold - P.min_evenness_score);
+        cwf = P.coverage_weighting_with_maf_segmentation + (P.coverage_weighting - P.coverage_weighting_with_maf_segmentation) * scaler;
+        cwf /= medianCoverageLevel;
+    } else cwf = P.coverage_weighting / medianCoverageLevel;
+    int minCoverage = (int)std::max(10.0f, (float)medianCoverageLevel / P.lower_coverage_level_weighting_factor);
+    int maxCoverage = (int)std::max(10.0f, (float)medianCoverageLevel * P.upper_coverage_level_weighting_factor);
+    if (P.user_ploidy >= 0) {
+        const double fixed = (double)((float)medianCoverageLevel / P.user_ploidy) * 2.0;       // GetDiploidCoverage (:2371)
+        if (!(fixed >= 1 && fixed < 100001)) return fail(CANVAS_ERR_INVALID, "the diploid coverage of the user ploidy must be 1 .. 100000");
+        minCoverage = maxCoverage = (int)fixed;
+    }
+    canvas_somatic_params fitParams = P.fit;
+    if (nseg < 500) fitParams.deviation_factor = 2.0f;
+    R.coverage_weighting_factor = cwf; R.min_coverage = minCoverage; R.max_coverage = maxCoverage; R.deviation_factor = fitParams.deviation_factor;
+    R.fixed_percent_purity = P.user_purity >= 0 ? (int)(P.user_purity * 100) : -1;
+    R.stages = 3;
+
+    // ---- stage 4: the fit, on the device arrays of stage 2
+    canvas_somatic_grid grid{};
+    grid.min_coverage = minCoverage; grid.max_coverage = maxCoverage; grid.minimum_purity_hard_limit = P.minimum_purity_hard_limit; grid.fixed_percent_purity = R.fixed_percent_purity;
+    grid.fixed_coverage = P.user_ploidy >= 0 ? minCoverage : -1; grid.is_enrichment = enrichment ? 1 : 0; grid.min_minor_allele_coverage = P.min_minor_allele_coverage;
+    grid.coverage_weighting_factor = cwf; grid.genome_length = P.genome_length;
+    R.stage23_ms += lap();
+    rc = canvas_somatic_model_fit(ctx, nusable, dUCov, dUMaf, dUW, dULen, 1, &grid, &fitParams, h_fit, nullptr, nullptr, nullptr);
+    R.stage4_ms = lap();
+    if (rc) return rc;
+
+    // ---- stage 5: the unrefined ploidy table of the best model (InitializeModelPoints(model), :754-777), the scan and MeanCount: the fourth wait
+    ScModel M{};
+    {
+        unsigned char ptCn[SC_MAXP], ptMajor[SC_MAXP];
+        M.P = som_points(maxCN, ptCn, ptMajor); M.maxCN = maxCN; M.cwf = cwf;
+        const double diploidCoverage = h_fit->diploid_coverage, purity = h_fit->purity;
+        const double tumorHaploid = diploidCoverage * purity / 2.0, normalHaploid = diploidCoverage * (1.0 - purity) / 2.0;
+        const long long nmax = (long long)h_fit->best_coverage * maxCN / 2 + 2;
+        std::vector<double> logFactorial((size_t)nmax + 1, 0.0);
+        for (long long i = 2; i <= nmax; i++) logFactorial[(size_t)i] = log((double)i) + logFactorial[(size_t)i - 1];
+        for (int p = 0; p < M.P; p++) {
+            const double coverage = ptCn[p] * tumorHaploid + 2 * normalHaploid;
+            M.cov[p] = coverage; M.maf[p] = som_adjusted_maf((ptCn[p] - ptMajor[p]) * tumorHaploid + normalHaploid, coverage, logFactorial.data());
+            M.hcov[p] = ptCn[p] * tumorHaploid + normalHaploid; M.cn[p] = ptCn[p]; M.major[p] = ptMajor[p];
+        }
+    }
+    rc = canvas_h2d_small(ctx, dModel, &M, sizeof(M)); if (rc) return rc;
+    const char* meanHook = cvx_hook("CANVAS_SOMATIC_MEAN");
+    const int forceWalk = meanHook && !strcmp(meanHook, "walk") ? 1 : 0;
+    {
+        ProfScope ps(ctx, "scall_assign");
+        hipLaunchKernelGGL(k_scall_assign, dim3(segGrid), dim3(CL_BLOCK), 0, ctx->stream, nseg, dSegOff, dMedCount, dMafUp, h_seg_ref_cn ? dRefCn : (const int*)nullptr, dModel, dCn, dCn2, dMcc, dDist, dDist2);
+        hipLaunchKernelGGL(k_scall_mean, dim3((unsigned)nseg), dim3(CL_BLOCK), 0, ctx->stream, d_count, dBinOff, dCn, maxCN, forceWalk, dMean, dRoute);
+    }
+    CANVAS_HIP_TRY(ctx, hipGetLastError());
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_cn, dCn, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_cn2, dCn2, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_mcc, dMcc, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_dist, dDist, S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_dist2, dDist2, S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_mean_count, dMean, S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipMemcpyAsync(O.seg_mean_route, dRoute, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    {
+        const double diploidCoverage = h_fit->diploid_coverage, purity = h_fit->purity;
+        for (long long s = 0; s < nseg; s++) {                   // :2438-2454
+            if (O.seg_cn[s] != maxCN) continue;
+            const double coverageRatio = O.seg_mean_count[s] / diploidCoverage;
+            const int referenceCN = h_seg_ref_cn ? h_seg_ref_cn[s] : 2;
+            const double estimateCopyNumber = (2 * coverageRatio - referenceCN * (1 - purity)) / purity;
+            const int estimateCN = cl_round_to_int(estimateCopyNumber);
+            if (estimateCN > maxCN) {
+                O.seg_cn[s] = estimateCN; O.seg_mcc[s] = -1;
+                const double coverage = diploidCoverage * ((1 - purity) + purity * estimateCN / 2.0f);
+                O.seg_dist[s] = fabs(O.seg_mean_count[s] - coverage) * cwf;
+            }
+        }
+    }
+
+    R.stage5_ms = lap();
+
+    // ---- stage 6: the host tail
+    std::vector<int> chrOf(S);
+    for (int c = 0; c < nchr; c++) for (long long s = h_chr_seg_offset[c]; s < h_chr_seg_offset[c + 1]; s++) chrOf[(size_t)s] = c;
+    for (long long s = 0; s < nseg; s++) O.seg_qscore[s] = sc_qscore(P, h_seg_bin_offset[s + 1] - h_seg_bin_offset[s], O.seg_cn[s], O.seg_dist[s], O.seg_dist2[s]);
+    double reportedPurity = h_fit->purity;
+    if (!std::isnan(P.snv_purity_estimate)) {                    // SelectPurityEstimate (:2653-2673), on the segments before the merge
+        double fractionAbnormal = 0, totalWeight = 0;
+        for (long long s = 0; s < nseg; s++) {
+            const int len = h_seg_end[s] - h_seg_begin[s];
+            totalWeight += len;
+            if (O.seg_cn[s] != 2 || O.seg_mcc[s] != 1) fractionAbnormal += len;
+        }
+        fractionAbnormal /= totalWeight;
+        if (fractionAbnormal < 0.07 && reportedPurity < 0.5) reportedPurity = P.snv_purity_estimate;
+    }
+    struct Seg { int begin, end; long long bins; };
+    std::vector<Seg> G(S); std::vector<long long> into(S, -1);
+    for (long long s = 0; s < nseg; s++) G[(size_t)s] = Seg{h_seg_begin[s], h_seg_end[s], h_seg_bin_offset[s + 1] - h_seg_bin_offset[s]};
+    auto mergeIn = [&](long long a, long long b) {               // G[a].MergeIn(G[b]), CanvasSegment.cs:318-334
+        Seg& A = G[(size_t)a]; const Seg B = G[(size_t)b];
+        if (B.begin < A.begin) { A.begin = B.begin; A.bins += B.bins; }
+        if (B.end > A.end) { A.end = B.end; A.bins += B.bins; }
+        into[(size_t)b] = a;
+    };
+    auto forbidden = [&](int c, int start, int end) {            // IsForbiddenInterval, :752-764
+        if (!h_chr_excl_offset) return false;
+        for (long long k = h_chr_excl_offset[c]; k < h_chr_excl_offset[c + 1]; k++) {
+            if (h_excl_start[k] >= start && h_excl_start[k] <= end) return true;
+            if (h_excl_stop[k] >= start && h_excl_stop[k] <= end) return true;
+            if (h_excl_start[k] > end) break;
+        }
+        return false;
+    };
+    auto size_of = [&](long long i) { return G[(size_t)i].end - G[(size_t)i].begin; };
+    const int mcs = P.minimum_call_size, span = P.merge_span;
+    std::vector<long long> first, runs;
+    for (long long i = 0; i < nseg;) {
+        if (size_of(i) >= mcs) { first.push_back(i); i++; continue; }
+        long long prev = -1, next = -1; double prevQ = enrichment ? -1 : 0, nextQ = enrichment ? -1 : 0;
+        for (long long c = i - 1; enrichment ? c >= 0 : c > 0; c--) {
+            if (chrOf[(size_t)c] != chrOf[(size_t)i]) break;
+            if (size_of(c) < mcs) continue;
+            if (enrichment ? G[(size_t)i].begin - G[(size_t)c].end > span : forbidden(chrOf[(size_t)c], G[(size_t)c].end, G[(size_t)i].begin)) break;
+            prev = c; prevQ = O.seg_qscore[c];
+            break;
+        }
+        for (long long c = i + 1; c < nseg; c++) {
+            if (chrOf[(size_t)c] != chrOf[(size_t)i]) break;
+            if (size_of(c) < mcs) continue;
+            if (enrichment ? G[(size_t)c].begin - G[(size_t)i].end > span : forbidden(chrOf[(size_t)c], G[(size_t)i].end, G[(size_t)c].begin)) break;
+            next = c; nextQ = O.seg_qscore[c];
+            break;
+        }
+        if ((enrichment ? prevQ >= 0 : prevQ > 0) && prevQ >= nextQ) { mergeIn(prev, i); i++; continue; }
+        if (enrichment ? nextQ >= 0 : nextQ > 0) {
+            if (enrichment) for (long long t = next - 1; i <= t; t--) mergeIn(next, t);
+            else for (long long t = i; t < next; t++) mergeIn(next, t);
+            i = next;
+            continue;
+        }
+        first.push_back(i); i++;
+    }
+    {
+        long long last = first[0];
+        runs.push_back(last);
+        for (size_t k = 1; k < first.size(); k++) {
+            const long long s = first[k];
+            const bool near = enrichment ? G[(size_t)s].begin - G[(size_t)last].end < span : !forbidden(chrOf[(size_t)last], G[(size_t)last].end, G[(size_t)s].begin);
+            if (O.seg_cn[last] == O.seg_cn[s] && chrOf[(size_t)last] == chrOf[(size_t)s] && near) { mergeIn(last, s); continue; }
+            last = s; runs.push_back(s);
+        }
+    }
+    const long long nruns = (long long)runs.size();
+    std::vector<long long> runOf(S, -1); std::vector<int> passes(S, 1);
+    for (long long r = 0; r < nruns; r++) {
+        const long long o = runs[(size_t)r]; const Seg& g = G[(size_t)o];
+        runOf[(size_t)o] = r;
+        O.run_owner[r] = o; O.run_begin[r] = g.begin; O.run_end[r] = g.end; O.run_bin_count[r] = g.bins;
+        O.run_qscore[r] = sc_qscore(P, g.bins, O.seg_cn[o], O.seg_dist[o], O.seg_dist2[o]);
+        O.run_filter[r] = (O.run_qscore[r] < P.quality_filter_threshold ? 1 : 0) | (g.end - g.begin < 10000 ? 2 : 0);
+        passes[(size_t)o] = O.run_filter[r] == 0;
+    }
+    for (long long s = 0; s < nseg; s++) { long long t = s; while (runOf[(size_t)t] < 0) t = into[(size_t)t]; O.seg_run[s] = runOf[(size_t)t]; }
+    // EstimateChromosomeCount (:2613-2646) over the original list: absorbed segments keep their PASS default, absorbers have grown, int32 arithmetic
+    double overallCount = 0;
+    {
+        std::vector<uint32_t> base((size_t)maxCN + 1, 0u);
+        auto weighted = [&]() {
+            double weightedMean = 0, weight = 0;
+            for (int c = 0; c <= maxCN; c++) { weight += (double)(int32_t)base[(size_t)c]; weightedMean += (double)(int32_t)(base[(size_t)c] * (uint32_t)c); }
+            return weight == 0 ? 0.0 : weightedMean / weight;
+        };
+        int current = -1;
+        for (long long s = 0; s < nseg; s++) {
+            if (chrOf[(size_t)s] != current) {
+                if (current >= 0) overallCount += weighted();
+                std::fill(base.begin(), base.end(), 0u);
+                current = chrOf[(size_t)s];
+            }
+            if (!passes[(size_t)s]) continue;
+            if (O.seg_cn[s] == -1) continue;
+            base[(size_t)std::min(O.seg_cn[s], maxCN)] += (uint32_t)(G[(size_t)s].end - G[(size_t)s].begin);
+        }
+        overallCount += weighted();
+    }
+    R.nruns = nruns; R.reported_purity = reportedPurity; R.purity_model_fit = h_fit->deviation; R.inter_model_distance = h_fit->inter_model_distance;
+    R.estimated_chromosome_count = overallCount; R.heterogeneity_proportion = 0; R.stages = 6; R.stage6_ms = lap();
     return CANVAS_OK;
 }

@@ -8,6 +8,7 @@
 //           model's per-segment assignment (the reference's final ModelDeviation call, :2100).
 // Not built: the cluster term of ModelDeviation (ClusterDeviation, :1309-1313); CANVAS_SOMATIC_INFO_CLUSTER_TERM says when the reference would have added it.
 #include "common.hpp"
+#include "somatic_points.hpp"
 #include <algorithm>
 #include <cmath>
 
@@ -17,13 +18,6 @@
 #define SOM_MAXCN 10
 #define SOM_OUT (6 + SOM_MAXCN + 1)  // doubles per model: Deviation, PrecisionDeviation, AccuracyDeviation, Ploidy, PercentNormal, DiploidDistance, PercentCN[0..10]
 static_assert(SOM_T == CANVAS_SOMATIC_TILE, "the tile the header documents");
-
-static int som_points(int maxCN, unsigned char* cn, unsigned char* major) {       // InitializePloidies (:87-116): copyNumber up, majorCount down while 2 * majorCount >= copyNumber
-    int p = 0;
-    for (int c = 0; c <= maxCN; c++)
-        for (int m = c; m * 2 >= c; m--, p++) { if (cn) { cn[p] = (unsigned char)c; major[p] = (unsigned char)m; } }
-    return p;
-}
 
 // GetModelDistance (:884-892)
 __device__ __forceinline__ double som_distance(double coverage, double coverage2, double maf, double maf2, double cwf) {
@@ -172,23 +166,6 @@ __global__ __launch_bounds__(SOM_T) void k_somatic_fit(SomArgs a) {
     o[1] = precisionDeviation; o[2] = accuracyDeviation; o[3] = ploidy;
     o[4] = g[2] / totalWeight;
     o[5] = 1.0 / (totalCNevents > 0.001 ? totalCNevents : 0.001);
-}
-
-// AdjustedMAF (:686-702) with binomP and logCombinations (:704-716); logFactorial[i] = log(i) + logFactorial[i - 1] is what the reference's growing table holds
-static double som_adjusted_maf(double theoreticalMAcvg, double coverage, const double* logFactorial) {
-    if (coverage < 1.0) return 0;
-    if (theoreticalMAcvg == 0) return 0;
-    const double mean = theoreticalMAcvg / coverage;
-    const int n = (int)coverage;
-    const double logP = log(mean), logQ = log(1 - mean);
-    double meanObs = 0.0;
-    for (int i = 0; i <= n; i++) {
-        const double logCombinations = logFactorial[n] - logFactorial[i] - logFactorial[n - i];
-        const double binomP = exp(logCombinations + i * logP + (n - i) * logQ);
-        const double k = i, other = coverage - i;
-        meanObs += (k <= other ? k : other) * binomP;
-    }
-    return meanObs / coverage;
 }
 
 // InitializeModelPoints(model) (:754-777) for models m0, m0 + step, ...

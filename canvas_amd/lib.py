@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "canvas_memcpy_h2d_async", "canvas_snv_count", "canvas_flag_unique_kmers", "canvas_fasta_case_from_mask",
     "canvas_smooth", "canvas_smooth_lengths", "canvas_smooth_plan",
     "canvas_segment_select", "canvas_segment_select_plan", "canvas_call_diploid",
-    "canvas_somatic_model_fit",
+    "canvas_somatic_model_fit", "canvas_call_somatic",
 ]
 
 
@@ -67,6 +67,47 @@ class SomaticModels(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("coverage", C.c_void_p), ("percent_purity", C.c_void_p), ("deviation", C.c_void_p), ("precision_deviation", C.c_void_p),
                 ("accuracy_deviation", C.c_void_p), ("ploidy", C.c_void_p), ("percent_normal", C.c_void_p), ("percent_cn", C.c_void_p), ("diploid_distance", C.c_void_p),
                 ("flags", C.c_void_p), ("score", C.c_void_p)]
+
+
+ERR_SOMATIC_FEW_SEGMENTS = -8                                  # CANVAS_ERR_SOMATIC_FEW_SEGMENTS
+SOMATIC_MEAN_NONE, SOMATIC_MEAN_WALK, SOMATIC_MEAN_EXACT = -1, 0, 1
+# what Canvas.call_somatic reads beside SOMATIC_DEFAULTS: SomaticCallerParameters.json, QualityScoreParameters.cs:9-12, SomaticCaller.cs:70
+SOMATIC_CALL_DEFAULTS = dict(minimum_variant_frequencies=50, minimum_call_size=50000, quality_filter_threshold=10, merge_span=1, is_enrichment=0, minimum_purity_hard_limit=20,
+                             lower_coverage_level_weighting_factor=4.0, upper_coverage_level_weighting_factor=2.355, user_purity=-1.0, user_ploidy=-1.0,
+                             coverage_weighting=0.333, coverage_weighting_with_maf_segmentation=0.20, evenness_score_threshold=94.5, min_evenness_score=88.0,
+                             logistic_intercept=-0.5143, logistic_log_bin_count=0.8596, logistic_model_distance=-50.4366, logistic_distance_ratio=-0.6511,
+                             evenness_score=float("nan"), snv_purity_estimate=float("nan"), min_minor_allele_coverage=0.0, genome_length=0)
+
+
+class SomaticCallParams(C.Structure):
+    _fields_ = [("fit", SomaticParams), ("minimum_variant_frequencies", C.c_int32), ("minimum_call_size", C.c_int32), ("quality_filter_threshold", C.c_int32),
+                ("merge_span", C.c_int32), ("is_enrichment", C.c_int32), ("minimum_purity_hard_limit", C.c_int32),
+                ("lower_coverage_level_weighting_factor", C.c_float), ("upper_coverage_level_weighting_factor", C.c_float), ("user_purity", C.c_float), ("user_ploidy", C.c_float),
+                ("coverage_weighting", C.c_double), ("coverage_weighting_with_maf_segmentation", C.c_double), ("evenness_score_threshold", C.c_double),
+                ("min_evenness_score", C.c_double), ("logistic_intercept", C.c_double), ("logistic_log_bin_count", C.c_double), ("logistic_model_distance", C.c_double),
+                ("logistic_distance_ratio", C.c_double), ("evenness_score", C.c_double), ("snv_purity_estimate", C.c_double), ("min_minor_allele_coverage", C.c_double),
+                ("genome_length", C.c_int64)]
+
+
+# (field, numpy dtype, "seg" | "seg1" (nseg + 1) | "run") in the order of canvas_somatic_call_out
+SOMATIC_CALL_OUT = [("seg_median_count", np.float64, "seg"), ("seg_site_offset", np.int64, "seg1"), ("seg_maf_upper", np.float64, "seg"), ("seg_usable", np.int32, "seg"),
+                    ("seg_coverage", np.float64, "seg"), ("seg_maf", np.float64, "seg"), ("seg_weight", np.float64, "seg"), ("seg_cn", np.int32, "seg"), ("seg_cn2", np.int32, "seg"),
+                    ("seg_mcc", np.int32, "seg"), ("seg_dist", np.float64, "seg"), ("seg_dist2", np.float64, "seg"), ("seg_mean_count", np.float64, "seg"),
+                    ("seg_mean_route", np.int32, "seg"), ("seg_qscore", np.int32, "seg"), ("seg_run", np.int64, "seg"), ("run_owner", np.int64, "run"), ("run_begin", np.int32, "run"),
+                    ("run_end", np.int32, "run"), ("run_bin_count", np.int64, "run"), ("run_qscore", np.int32, "run"), ("run_filter", np.int32, "run")]
+
+
+class SomaticCallOut(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _, _ in SOMATIC_CALL_OUT]
+
+
+class SomaticCallScalars(C.Structure):
+    _fields_ = [("nruns", C.c_int64), ("nusable", C.c_int64), ("kept_sites", C.c_int64), ("stages", C.c_int32), ("threshold_used", C.c_int32),
+                ("median_coverage_level", C.c_int32), ("min_coverage", C.c_int32), ("max_coverage", C.c_int32), ("fixed_percent_purity", C.c_int32),
+                ("overall_median_coverage", C.c_float), ("deviation_factor", C.c_float), ("mean_coverage", C.c_double), ("coverage_weighting_factor", C.c_double),
+                ("reported_purity", C.c_double), ("purity_model_fit", C.c_double), ("inter_model_distance", C.c_double), ("estimated_chromosome_count", C.c_double),
+                ("heterogeneity_proportion", C.c_double), ("stage1_ms", C.c_double), ("stage23_ms", C.c_double), ("stage4_ms", C.c_double), ("stage5_ms", C.c_double),
+                ("stage6_ms", C.c_double)]
 
 
 def somatic_grid(min_coverage, max_coverage, minimum_purity_hard_limit, min_minor_allele_coverage, fixed_percent_purity=-1, fixed_coverage=-1):
@@ -819,6 +860,64 @@ class Canvas:
             e = CanvasError(f"libcanvas_hip error {rc}: {self.lib.canvas_last_error(self.ctx).decode()}")
             e.code = rc
             e.partial = out if rc in (ERR_SOMATIC_NO_MODEL, ERR_SOMATIC_NO_SCORE) else None
+            raise e
+        return out
+
+    def call_somatic(self, counts, chr_seg_offset, seg_begin, seg_end, seg_bin_offset, chr_site_offset, site_pos, site_ref, site_alt, genome_length, seg_ref_cn=None,
+                     excluded=None, **params):
+        """CanvasSomaticCaller.CallVariants between the parsed files and the written ones, with the model fit in the middle (canvas_call_somatic).  Bins, segments and
+        sites as Canvas.call_diploid takes them; seg_ref_cn: the reference copy number per segment (None: 2 everywhere); excluded: per chromosome (starts, stops) of the
+        excluded intervals, sorted by start (None: none); **params override SOMATIC_CALL_DEFAULTS and SOMATIC_DEFAULTS.  Returns a dict: every array of
+        canvas_somatic_call_out (per segment, and per run cut to nruns), every field of canvas_somatic_call_scalars, site_count, and `fit`: the fields of
+        canvas_somatic_result.  CanvasError carries .code (ERR_SOMATIC_FEW_SEGMENTS, ERR_SOMATIC_NO_MODEL, ERR_SOMATIC_NO_SCORE, -1) and .partial, the same dict with the
+        stages that were filled (`stages`: 0, 2 or 3)."""
+        torch = self.torch
+        cso = np.ascontiguousarray(chr_seg_offset, np.int64); csi = np.ascontiguousarray(chr_site_offset, np.int64)
+        beg = np.ascontiguousarray(seg_begin, np.int32); end = np.ascontiguousarray(seg_end, np.int32); sbo = np.ascontiguousarray(seg_bin_offset, np.int64)
+        nchr, nseg = len(cso) - 1, len(beg)
+        if nchr < 0 or len(csi) != nchr + 1 or len(end) != nseg or len(sbo) != nseg + 1 or int(cso[-1]) != nseg:
+            raise CanvasError("call_somatic: one begin / end per segment, nseg + 1 bin offsets, nchr + 1 chromosome offsets that end at the number of segments / sites")
+        assert counts.dtype == torch.float32 and counts.is_contiguous() and counts.dim() == 1 and (counts.numel() == 0 or counts.device == self.device)
+        for t in (site_pos, site_ref, site_alt):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.numel() == site_pos.numel() and (t.numel() == 0 or t.device == self.device)
+        if int(csi[-1]) != site_pos.numel():
+            raise CanvasError("call_somatic: the chromosomes' site offsets must end at the number of sites")
+        ref = None
+        if seg_ref_cn is not None:
+            ref = np.ascontiguousarray(seg_ref_cn, np.int32)
+            assert ref.shape == (nseg,)
+        eo = es = ee = None
+        if excluded is not None:
+            assert len(excluded) == nchr
+            eo = np.concatenate([[0], np.cumsum([len(e[0]) for e in excluded])]).astype(np.int64)
+            es = np.ascontiguousarray(np.concatenate([np.asarray(e[0], np.int32) for e in excluded] + [np.zeros(1, np.int32)]), np.int32)
+            ee = np.ascontiguousarray(np.concatenate([np.asarray(e[1], np.int32) for e in excluded] + [np.zeros(1, np.int32)]), np.int32)
+        unknown = set(params) - set(SOMATIC_DEFAULTS) - set(SOMATIC_CALL_DEFAULTS)
+        if unknown:
+            raise TypeError("call_somatic: unknown parameters %s" % sorted(unknown))
+        fitp = SomaticParams(**dict(SOMATIC_DEFAULTS, **{k: v for k, v in params.items() if k in SOMATIC_DEFAULTS}))
+        own = dict(SOMATIC_CALL_DEFAULTS, genome_length=int(genome_length), **{k: v for k, v in params.items() if k in SOMATIC_CALL_DEFAULTS})
+        own["is_enrichment"] = int(bool(own["is_enrichment"]))
+        cp = SomaticCallParams(fit=fitp, **own)
+        n1 = max(nseg, 1)
+        arrays = {name: np.zeros(n1 + 1 if kind == "seg1" else n1, dt) for name, dt, kind in SOMATIC_CALL_OUT}
+        co = SomaticCallOut(*[arrays[name].ctypes.data for name, _, _ in SOMATIC_CALL_OUT])
+        sc = SomaticCallScalars(); res = SomaticResult()
+        fn = self.lib.canvas_call_somatic
+        fn.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 16
+        opt = lambda a: _np_ptr(a) if a is not None else None
+        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        rc = fn(self.ctx, counts.numel(), C.c_void_p(counts.data_ptr()), nchr, _np_ptr(cso), _np_ptr(beg), _np_ptr(end), _np_ptr(sbo), _np_ptr(csi), C.c_void_p(site_pos.data_ptr()),
+                C.c_void_p(site_ref.data_ptr()), C.c_void_p(site_alt.data_ptr()), opt(ref), opt(eo), opt(es), opt(ee), C.byref(cp), C.byref(co), C.byref(sc), C.byref(res))
+        r = sc.nruns
+        out = {name: (arrays[name][:r] if kind == "run" else arrays[name][:nseg + 1] if kind == "seg1" else arrays[name][:nseg]) for name, _, kind in SOMATIC_CALL_OUT}
+        out["site_count"] = np.diff(out["seg_site_offset"])
+        out.update({name: getattr(sc, name) for name, _ in SomaticCallScalars._fields_})
+        out["fit"] = {name: (np.array(res.percent_cn[:fitp.maximum_copy_number + 1]) if name == "percent_cn" else getattr(res, name)) for name, _ in SomaticResult._fields_}
+        if rc != 0:
+            e = CanvasError(f"libcanvas_hip error {rc}: {self.lib.canvas_last_error(self.ctx).decode()}")
+            e.code = rc
+            e.partial = out
             raise e
         return out
 

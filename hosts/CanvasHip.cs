@@ -181,6 +181,38 @@ namespace CanvasHipInterop
         [DllImport(Lib)] public static extern int canvas_somatic_model_fit(IntPtr ctx, long nseg, IntPtr coverage, IntPtr maf, IntPtr weight, IntPtr length, int inputsOnDevice,
             ref canvas_somatic_grid grid, ref canvas_somatic_params parameters, out canvas_somatic_result result, IntPtr segPoint, IntPtr segDistance, IntPtr models);
 
+        // CanvasSomaticCaller.CallVariants between the parsed files and the written ones, with canvas_somatic_model_fit in the middle: usable segments, the median level and
+        // the grid bounds, the fit, AssignPloidyCalls, Logistic q-scores, the merges, filters and header numbers.  Inputs as canvas_call_diploid plus segRefCn (or null: 2),
+        // the excluded intervals per chromosome (chrExclOffset null: none) and the parameter struct; `output` holds host pointers to arrays of nseg entries (seg_site_offset
+        // nseg + 1), of which scalars.nruns are filled in the per-run arrays.  The clustering is not built: minimum_purity_hard_limit and min_minor_allele_coverage are inputs
+        public const int ErrSomaticFewSegments = -8, SomaticMeanNone = -1, SomaticMeanWalk = 0, SomaticMeanExact = 1;
+        [StructLayout(LayoutKind.Sequential)] public struct canvas_somatic_call_params
+        {
+            public canvas_somatic_params fit;
+            public int minimum_variant_frequencies, minimum_call_size, quality_filter_threshold, merge_span, is_enrichment, minimum_purity_hard_limit;
+            public float lower_coverage_level_weighting_factor, upper_coverage_level_weighting_factor, user_purity, user_ploidy;
+            public double coverage_weighting, coverage_weighting_with_maf_segmentation, evenness_score_threshold, min_evenness_score;
+            public double logistic_intercept, logistic_log_bin_count, logistic_model_distance, logistic_distance_ratio;
+            public double evenness_score, snv_purity_estimate, min_minor_allele_coverage;
+            public long genome_length;
+        }
+        [StructLayout(LayoutKind.Sequential)] public struct canvas_somatic_call_out
+        {
+            public IntPtr seg_median_count, seg_site_offset, seg_maf_upper, seg_usable, seg_coverage, seg_maf, seg_weight, seg_cn, seg_cn2, seg_mcc, seg_dist, seg_dist2;
+            public IntPtr seg_mean_count, seg_mean_route, seg_qscore, seg_run, run_owner, run_begin, run_end, run_bin_count, run_qscore, run_filter;
+        }
+        [StructLayout(LayoutKind.Sequential)] public struct canvas_somatic_call_scalars
+        {
+            public long nruns, nusable, kept_sites;
+            public int stages, threshold_used, median_coverage_level, min_coverage, max_coverage, fixed_percent_purity;
+            public float overall_median_coverage, deviation_factor;
+            public double mean_coverage, coverage_weighting_factor, reported_purity, purity_model_fit, inter_model_distance, estimated_chromosome_count, heterogeneity_proportion;
+            public double stage1_ms, stage23_ms, stage4_ms, stage5_ms, stage6_ms;
+        }
+        [DllImport(Lib)] public static extern int canvas_call_somatic(IntPtr ctx, long nbins, IntPtr dCount, int nchr, long[] chrSegOffset, int[] segBegin, int[] segEnd, long[] segBinOffset,
+            long[] chrSiteOffset, IntPtr dSitePos, IntPtr dSiteRef, IntPtr dSiteAlt, int[] segRefCn, long[] chrExclOffset, int[] exclStart, int[] exclStop,
+            ref canvas_somatic_call_params parameters, ref canvas_somatic_call_out output, out canvas_somatic_call_scalars scalars, out canvas_somatic_result result);
+
         /// <summary>Turns a non-zero status into the module's own failure convention (message on stderr, exit code 1).</summary>
         public static void Check(IntPtr ctx, int status, string what)
         {

@@ -729,6 +729,105 @@ int32_t canvas_somatic_model_fit(canvas_ctx* ctx, int64_t nseg, const double* co
                                  int32_t inputs_on_device, const canvas_somatic_grid* grid, const canvas_somatic_params* params, canvas_somatic_result* h_result,
                                  int32_t* h_seg_point, double* h_seg_distance, const canvas_somatic_models* h_models);
 
+/* ---- CanvasSomaticCaller: the calls around the fit (SomaticCaller.cs CallVariants :366-476 between "files parsed" and "files written") ---- */
+#define CANVAS_ERR_SOMATIC_FEW_SEGMENTS (-8)   /* fewer than 3 usable segments (NotEnoughUsableSegementsException, :1636): stages 1 and 2 are filled */
+#define CANVAS_SOMATIC_MEAN_NONE (-1)          /* seg_mean_route: the best ploidy is not MaximumCopyNumber, MeanCount was not needed (seg_mean_count is 0) */
+#define CANVAS_SOMATIC_MEAN_WALK 0             /* ... summed by one lane in bin order */
+#define CANVAS_SOMATIC_MEAN_EXACT 1            /* ... summed as integers of 2^e by the whole workgroup, after the proof that every partial sum of the serial loop is exact */
+typedef struct canvas_somatic_call_params {
+    canvas_somatic_params fit;                 /* deviation_factor is replaced by 2 when there are fewer than 500 segments (:375) */
+    int32_t minimum_variant_frequencies;       /* MinimumVariantFrequenciesForInformativeSegment, 50 */
+    int32_t minimum_call_size;                 /* 50000 */
+    int32_t quality_filter_threshold;          /* 10 */
+    int32_t merge_span;                        /* maximumMergeSpan of the enrichment merge: 1 in the reference */
+    int32_t is_enrichment;
+    int32_t minimum_purity_hard_limit;         /* from the clustering, caller-supplied: 5 or 20 in the reference */
+    float lower_coverage_level_weighting_factor; /* 4 */
+    float upper_coverage_level_weighting_factor; /* 2.355 */
+    float user_purity;                         /* negative: none */
+    float user_ploidy;                         /* negative: none */
+    double coverage_weighting;                 /* 0.333 */
+    double coverage_weighting_with_maf_segmentation; /* 0.20 */
+    double evenness_score_threshold;           /* 94.5 */
+    double min_evenness_score;                 /* 88 */
+    double logistic_intercept;                 /* -0.5143 */
+    double logistic_log_bin_count;             /* 0.8596 */
+    double logistic_model_distance;            /* -50.4366 */
+    double logistic_distance_ratio;            /* -0.6511 */
+    double evenness_score;                     /* NaN: none */
+    double snv_purity_estimate;                /* NaN: none */
+    double min_minor_allele_coverage;          /* from the clustering, caller-supplied */
+    int64_t genome_length;
+} canvas_somatic_call_params;
+/* host arrays the call fills; every pointer is required.  Per-segment arrays hold nseg entries (seg_site_offset nseg + 1), per-run arrays nseg entries of which nruns are filled */
+typedef struct canvas_somatic_call_out {
+    double* seg_median_count;                  /* stage 1: Utilities.Median(float) of the counts */
+    int64_t* seg_site_offset;                  /* stage 1: kept sites in front of each segment */
+    double* seg_maf_upper;                     /* stage 1: a[n/2] of the folded frequencies (0 without a site) */
+    int32_t* seg_usable;                       /* stage 2 */
+    double* seg_coverage;                      /* stage 2: info.Coverage (every segment) */
+    double* seg_maf;                           /* stage 2: info.Maf under the threshold finally used (every segment) */
+    double* seg_weight;                        /* stage 2: info.Weight (every segment) */
+    int32_t* seg_cn;                           /* stage 5: CopyNumber (after the MaximumCopyNumber rule) */
+    int32_t* seg_cn2;                          /* stage 5: SecondBestCopyNumber (-1: none) */
+    int32_t* seg_mcc;                          /* stage 5: MajorChromosomeCount (-1: null) */
+    double* seg_dist;                          /* stage 5: ModelDistance */
+    double* seg_dist2;                         /* stage 5: RunnerUpModelDistance */
+    double* seg_mean_count;                    /* stage 5: MeanCount where it was needed */
+    int32_t* seg_mean_route;                   /* stage 5: CANVAS_SOMATIC_MEAN_* */
+    int32_t* seg_qscore;                       /* stage 6: Logistic q-score of the segment */
+    int64_t* seg_run;                          /* stage 6: the run the segment went to */
+    int64_t* run_owner;                        /* stage 6: the segment whose call (CN, MCC, distances) the run carries */
+    int32_t* run_begin;
+    int32_t* run_end;
+    int64_t* run_bin_count;                    /* what MergeIn left in GenomicBins: a segment merged in without moving Begin or End adds no bins */
+    int32_t* run_qscore;
+    int32_t* run_filter;                       /* 1 = q<threshold>, 2 = L10kb */
+} canvas_somatic_call_out;
+typedef struct canvas_somatic_call_scalars {
+    int64_t nruns, nusable, kept_sites;
+    int32_t stages;                            /* stages filled: 0, 2, 3 or 6 */
+    int32_t threshold_used;                    /* stage 2: MinimumVariantFrequenciesForInformativeSegment after the loop of :1626-1634 */
+    int32_t median_coverage_level;             /* stage 3 */
+    int32_t min_coverage, max_coverage;        /* stage 3: the grid's coverages (equal with a user ploidy) */
+    int32_t fixed_percent_purity;              /* stage 3: (int)(userPurity * 100), or -1 */
+    float overall_median_coverage;             /* stage 2: Quartiles(...).Item2 */
+    float deviation_factor;                    /* stage 3 */
+    double mean_coverage;                      /* stage 1: MeanCoverage */
+    double coverage_weighting_factor;          /* stage 3 */
+    double reported_purity;                    /* stage 6: ##EstimatedTumorPurity (after SelectPurityEstimate) */
+    double purity_model_fit;                   /* stage 6: ##PurityModelFit */
+    double inter_model_distance;               /* stage 6: ##InterModelDistance */
+    double estimated_chromosome_count;         /* stage 6: ##EstimatedChromosomeCount */
+    double heterogeneity_proportion;           /* stage 6: 0 (see below) */
+    double stage1_ms, stage23_ms, stage4_ms, stage5_ms, stage6_ms;   /* wall time of the call's parts (host clock; each but the last ends in a stream synchronisation) */
+} canvas_somatic_call_scalars;
+/* CanvasSomaticCaller.CallVariants on device-resident bins and sites, with canvas_somatic_model_fit in the middle.  Bins, segments, sites, their ordering rules and the
+ * CANVAS_ERR_INVALID cases are those of canvas_call_diploid.  h_seg_ref_cn (nseg, or NULL = 2 everywhere) is ReferencePloidy.GetReferenceCopyNumber per segment.  Excluded
+ * intervals (_excludedIntervals) of chromosome c are h_chr_excl_offset[c] .. [c+1] of h_excl_start / h_excl_stop, sorted by start (h_chr_excl_offset NULL: none).
+ *   1  sites to segments, MeanCoverage, per-segment median count, number of folded frequencies and their upper median (device, the select classes of canvas_segment_select)
+ *   2  GetUsableSegmentsAndSourcesForModeling (:1432-1493) inside the threshold loop of :1626-1634; overallMedianCoverage is one more select (over every bin, or over the
+ *      per-segment medians as floats for enrichment); the usable segments' coverage / maf / weight / length are gathered on the device for the fit
+ *   3  medianCoverageLevel = Convert.ToInt32(Quartiles(bins of the usable segments at reference copy number 2).Item2): a device compaction in front of the select;
+ *      CoverageWeightingFactor with its evenness branch, the grid's coverages, DeviationFactor
+ *   4  canvas_somatic_model_fit on the device arrays of stage 2; *h_fit is its result
+ *   5  AssignPloidyCalls (:2379-2457) over all segments against the unrefined ploidy table of the best model (host table, device scan), MeanCount for the segments at
+ *      MaximumCopyNumber (bit-equal to the serial double sum in bin order rounded to float: seg_mean_route says how), the rule of :2438-2454
+ *   6  host: Logistic q-scores, MergeSegmentsUsingExcludedIntervals or (enrichment) MergeSegments(minimum_call_size, merge_span) with MergeIn as it is, q-scores of the runs
+ *      with the bins MergeIn kept, SetFilterForSegments, EstimateChromosomeCount over the original list (int32 arithmetic), SelectPurityEstimate
+ * NOT built: the clustering (Program.cs fixes MeanShift, whose KD tree is not in the reference tree), the segment windows, IsSampleClearlyNotAllReferencePloidy and the cluster
+ * term: minimum_purity_hard_limit and min_minor_allele_coverage stay caller-supplied as for the fit.  MeanShift never writes ClusterId, so _heterogeneousSegmentsSignature is
+ * empty in the reference as shipped: IsHeterogeneous is false everywhere, AdjustPloidyCalls changes nothing and HeterogeneityProportion is 0; none of it is computed.  Nor
+ * AssignPloidyCallsGaussianMixture, PruneFrequencies, the truth-set reports, the executable with its VCF and coverage plot file, medians of the merged runs.
+ * Errors: CANVAS_ERR_SOMATIC_FEW_SEGMENTS (stages 1-2 filled); CANVAS_ERR_SOMATIC_NO_MODEL / _NO_SCORE from the fit (stages 1-3 and *h_fit filled); CANVAS_ERR_INVALID for a
+ * median level below 1 or outside int32, no usable segment at reference copy number 2, CoverageWeighting <= CoverageWeightingWithMafSegmentation on the evenness branch, no
+ * kept site, and what the fit refuses.  The host tables and parameters are checked before the context is looked at; *h_scalars is cleared once they have passed. */
+int32_t canvas_call_somatic(canvas_ctx* ctx, int64_t nbins, const float* d_count, int32_t nchr, const int64_t* h_chr_seg_offset /* nchr+1 */, const int32_t* h_seg_begin,
+                            const int32_t* h_seg_end, const int64_t* h_seg_bin_offset /* nseg+1 */, const int64_t* h_chr_site_offset /* nchr+1 */, const int32_t* d_site_pos,
+                            const int32_t* d_site_ref, const int32_t* d_site_alt, const int32_t* h_seg_ref_cn, const int64_t* h_chr_excl_offset /* nchr+1 */,
+                            const int32_t* h_excl_start, const int32_t* h_excl_stop, const canvas_somatic_call_params* params, const canvas_somatic_call_out* out,
+                            canvas_somatic_call_scalars* h_scalars, canvas_somatic_result* h_fit);
+
 /* ---- profiling hooks (hipEvent pairs recorded on the context's stream around the named kernels) --------------------- */
 /* on: 0 off; 1 every named scope; 2 only the scopes around the dominant (HBM-bound) kernel of CanvasBin — "bin_summary", "bin_summary_packed", "bin_pass",
    "bin_tile_stats" — so that a timed pass carries two event records instead of a dozen (each scope costs two barrier packets on the stream) */
