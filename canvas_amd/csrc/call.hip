@@ -412,13 +412,14 @@ static void cl_model(double diploidCoverage, double meanCoverage, ClModel& M) {
     M.factor = 0.6 / diploidCoverage;
 }
 
-extern "C" int32_t canvas_call_diploid(canvas_ctx* ctx, int64_t nbins, const float* d_count, int32_t nchr, const int64_t* h_chr_seg_offset, const int32_t* h_seg_begin,
-                                       const int32_t* h_seg_end, const int64_t* h_seg_bin_offset, const int64_t* h_chr_site_offset, const int32_t* d_site_pos,
-                                       const int32_t* d_site_ref, const int32_t* d_site_alt, const double* h_logistic4,
-                                       double* h_seg_median_count, int64_t* h_seg_site_offset, int32_t* h_seg_informative, double* h_seg_median_maf, int32_t* h_seg_cn, int32_t* h_seg_mcc,
-                                       double* h_seg_dist, double* h_seg_dist2, int32_t* h_seg_qscore,
-                                       int64_t* h_nruns, int64_t* h_run_first, int64_t* h_run_last, int32_t* h_run_qscore, int32_t* h_run_filter, double* h_run_median_count,
-                                       double* h_scalars2, int64_t* h_info4) {
+// the body of canvas_call_diploid, shared with canvas_call_diploid_ids (which builds the host tables from the bins' segment ids first)
+static int32_t cl_call_diploid(canvas_ctx* ctx, int64_t nbins, const float* d_count, int32_t nchr, const int64_t* h_chr_seg_offset, const int32_t* h_seg_begin,
+                               const int32_t* h_seg_end, const int64_t* h_seg_bin_offset, const int64_t* h_chr_site_offset, const int32_t* d_site_pos,
+                               const int32_t* d_site_ref, const int32_t* d_site_alt, const double* h_logistic4,
+                               double* h_seg_median_count, int64_t* h_seg_site_offset, int32_t* h_seg_informative, double* h_seg_median_maf, int32_t* h_seg_cn, int32_t* h_seg_mcc,
+                               double* h_seg_dist, double* h_seg_dist2, int32_t* h_seg_qscore,
+                               int64_t* h_nruns, int64_t* h_run_first, int64_t* h_run_last, int32_t* h_run_qscore, int32_t* h_run_filter, double* h_run_median_count,
+                               double* h_scalars2, int64_t* h_info4) {
     // every check of the host tables comes first and needs no context (no message without one): *h_nruns is set to 0 only when they have passed
 #define CL_REFUSE(msg) do { if (ctx) ctx->err = (msg); return CANVAS_ERR_INVALID; } while (0)
     if (nchr < 0 || nbins < 0 || !h_chr_seg_offset || !h_chr_site_offset || !h_logistic4 || !h_nruns || !h_scalars2) CL_REFUSE("canvas_call_diploid: bad arguments");
@@ -542,6 +543,38 @@ extern "C" int32_t canvas_call_diploid(canvas_ctx* ctx, int64_t nbins, const flo
     *h_nruns = nruns; h_scalars2[0] = diploidCoverage; h_scalars2[1] = meanCoverage;
     if (h_info4) { h_info4[0] = (int64_t)hSt->kept; h_info4[1] = integerPath; h_info4[2] = (int64_t)hSt->covSum; h_info4[3] = 0; }
     return CANVAS_OK;
+}
+
+extern "C" int32_t canvas_call_diploid(canvas_ctx* ctx, int64_t nbins, const float* d_count, int32_t nchr, const int64_t* h_chr_seg_offset, const int32_t* h_seg_begin,
+                                       const int32_t* h_seg_end, const int64_t* h_seg_bin_offset, const int64_t* h_chr_site_offset, const int32_t* d_site_pos,
+                                       const int32_t* d_site_ref, const int32_t* d_site_alt, const double* h_logistic4,
+                                       double* h_seg_median_count, int64_t* h_seg_site_offset, int32_t* h_seg_informative, double* h_seg_median_maf, int32_t* h_seg_cn, int32_t* h_seg_mcc,
+                                       double* h_seg_dist, double* h_seg_dist2, int32_t* h_seg_qscore,
+                                       int64_t* h_nruns, int64_t* h_run_first, int64_t* h_run_last, int32_t* h_run_qscore, int32_t* h_run_filter, double* h_run_median_count,
+                                       double* h_scalars2, int64_t* h_info4) {
+    return cl_call_diploid(ctx, nbins, d_count, nchr, h_chr_seg_offset, h_seg_begin, h_seg_end, h_seg_bin_offset, h_chr_site_offset, d_site_pos, d_site_ref, d_site_alt, h_logistic4,
+                           h_seg_median_count, h_seg_site_offset, h_seg_informative, h_seg_median_maf, h_seg_cn, h_seg_mcc, h_seg_dist, h_seg_dist2, h_seg_qscore,
+                           h_nruns, h_run_first, h_run_last, h_run_qscore, h_run_filter, h_run_median_count, h_scalars2, h_info4);
+}
+
+// canvas_segment_tables (segtab.hip), then the call on the tables and float counts it left: the germline sample from per-bin segment ids to copy-number calls without a
+// text hand-off and without a per-bin array leaving the device.  One wait for the tables (the selects build their classes from the host offsets) and the call's three.
+extern "C" int32_t canvas_call_diploid_ids(canvas_ctx* ctx, int64_t nbins, int32_t nchr, const int64_t* h_chr_offset, const int32_t* d_start, const int32_t* d_stop, const int32_t* d_segment_id,
+                                           const double* d_cov, int64_t cap_seg, const int64_t* h_chr_site_offset, const int32_t* d_site_pos, const int32_t* d_site_ref, const int32_t* d_site_alt,
+                                           const double* h_logistic4,
+                                           int64_t* h_nseg, int64_t* h_chr_seg_offset, int32_t* h_seg_begin, int32_t* h_seg_end, int64_t* h_seg_bin_offset, int32_t* h_seg_ci4, float* d_count_f32,
+                                           double* h_seg_median_count, int64_t* h_seg_site_offset, int32_t* h_seg_informative, double* h_seg_median_maf, int32_t* h_seg_cn, int32_t* h_seg_mcc,
+                                           double* h_seg_dist, double* h_seg_dist2, int32_t* h_seg_qscore,
+                                           int64_t* h_nruns, int64_t* h_run_first, int64_t* h_run_last, int32_t* h_run_qscore, int32_t* h_run_filter, double* h_run_median_count,
+                                           double* h_scalars2, int64_t* h_info4) {
+    if (!d_cov || !d_count_f32) { if (ctx) ctx->err = "canvas_call_diploid_ids: bad arguments (the call needs the coverage and room for the float counts)"; return CANVAS_ERR_INVALID; }
+    // canvas_segment_tables decides its host arguments before it looks at the context, so a NULL ctx still reports them
+    int32_t rc = canvas_segment_tables(ctx, nbins, nchr, h_chr_offset, d_start, d_stop, d_segment_id, d_cov, cap_seg, h_nseg, h_chr_seg_offset, h_seg_begin, h_seg_end, h_seg_bin_offset, h_seg_ci4,
+                                       d_count_f32);
+    if (rc) return rc;
+    return cl_call_diploid(ctx, nbins, d_count_f32, nchr, h_chr_seg_offset, h_seg_begin, h_seg_end, h_seg_bin_offset, h_chr_site_offset, d_site_pos, d_site_ref, d_site_alt, h_logistic4,
+                           h_seg_median_count, h_seg_site_offset, h_seg_informative, h_seg_median_maf, h_seg_cn, h_seg_mcc, h_seg_dist, h_seg_dist2, h_seg_qscore,
+                           h_nruns, h_run_first, h_run_last, h_run_qscore, h_run_filter, h_run_median_count, h_scalars2, h_info4);
 }
 
 // ================================================================ canvas_call_somatic: CanvasSomaticCaller.CallVariants around canvas_somatic_model_fit ======================

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "canvas_smooth", "canvas_smooth_lengths", "canvas_smooth_plan",
     "canvas_segment_select", "canvas_segment_select_plan", "canvas_call_diploid",
     "canvas_somatic_model_fit", "canvas_call_somatic",
+    "canvas_segment_tables", "canvas_call_diploid_ids",
 ]
 
 
@@ -779,19 +780,27 @@ class Canvas:
             raise CanvasError("call_diploid: the chromosomes' site offsets must end at the number of sites")
         b4 = np.ascontiguousarray(logistic, np.float64)
         assert b4.shape == (4,)
-        n1 = max(nseg, 1)
+        o, outs = self._diploid_outputs(max(nseg, 1))
+        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        self._check(self.lib.canvas_call_diploid(self.ctx, C.c_int64(counts.numel()), C.c_void_p(counts.data_ptr()), C.c_int32(nchr), _np_ptr(cso), _np_ptr(beg), _np_ptr(end), _np_ptr(sbo),
+                                                 _np_ptr(csi), C.c_void_p(site_pos.data_ptr()), C.c_void_p(site_ref.data_ptr()), C.c_void_p(site_alt.data_ptr()), _np_ptr(b4), *outs))
+        return self._diploid_result(o, nseg, beg, end, sbo, seg_start_ci, seg_end_ci)
+
+    @staticmethod
+    def _diploid_outputs(n1):
+        """the host arrays canvas_call_diploid / canvas_call_diploid_ids fill (room for n1 segments) and their pointers in the order of the C signature"""
         o = dict(median_count=np.zeros(n1, np.float64), site_offset=np.zeros(n1 + 1, np.int64), informative=np.zeros(n1, np.int32), median_maf=np.zeros(n1, np.float64),
                  cn=np.zeros(n1, np.int32), mcc=np.zeros(n1, np.int32), dist=np.zeros(n1, np.float64), dist2=np.zeros(n1, np.float64), qscore=np.zeros(n1, np.int32),
                  run_first=np.zeros(n1, np.int64), run_last=np.zeros(n1, np.int64), run_qscore=np.zeros(n1, np.int32), run_filter=np.zeros(n1, np.int32), run_median_count=np.zeros(n1, np.float64))
-        nruns = C.c_int64(0); scal = np.zeros(2, np.float64); info = np.zeros(4, np.int64)
-        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
-        self._check(self.lib.canvas_call_diploid(self.ctx, C.c_int64(counts.numel()), C.c_void_p(counts.data_ptr()), C.c_int32(nchr), _np_ptr(cso), _np_ptr(beg), _np_ptr(end), _np_ptr(sbo),
-                                                 _np_ptr(csi), C.c_void_p(site_pos.data_ptr()), C.c_void_p(site_ref.data_ptr()), C.c_void_p(site_alt.data_ptr()), _np_ptr(b4),
-                                                 _np_ptr(o["median_count"]), _np_ptr(o["site_offset"]), _np_ptr(o["informative"]), _np_ptr(o["median_maf"]), _np_ptr(o["cn"]), _np_ptr(o["mcc"]),
-                                                 _np_ptr(o["dist"]), _np_ptr(o["dist2"]), _np_ptr(o["qscore"]), C.byref(nruns), _np_ptr(o["run_first"]), _np_ptr(o["run_last"]),
-                                                 _np_ptr(o["run_qscore"]), _np_ptr(o["run_filter"]), _np_ptr(o["run_median_count"]), _np_ptr(scal), _np_ptr(info)))
-        r = nruns.value
-        out = {k: (v[:r] if k.startswith("run_") else v[:nseg]) for k, v in o.items() if k != "site_offset"}
+        o["_nruns"] = C.c_int64(0); o["_scal"] = np.zeros(2, np.float64); o["_info"] = np.zeros(4, np.int64)
+        outs = [_np_ptr(o[k]) for k in ("median_count", "site_offset", "informative", "median_maf", "cn", "mcc", "dist", "dist2", "qscore")] + [C.byref(o["_nruns"])] + \
+               [_np_ptr(o[k]) for k in ("run_first", "run_last", "run_qscore", "run_filter", "run_median_count", "_scal", "_info")]
+        return o, outs
+
+    @staticmethod
+    def _diploid_result(o, nseg, beg, end, sbo, seg_start_ci, seg_end_ci):
+        r, scal, info = o["_nruns"].value, o["_scal"], o["_info"]
+        out = {k: (v[:r] if k.startswith("run_") else v[:nseg]) for k, v in o.items() if k != "site_offset" and not k.startswith("_")}
         out["site_count"] = np.diff(o["site_offset"][:nseg + 1]); out["bin_count"] = np.diff(sbo)
         f, l = out["run_first"], out["run_last"]
         out.update(run_begin=beg[f], run_end=end[l], run_cn=out["cn"][f], run_mcc=out["mcc"][f], run_bin_count=sbo[l + 1] - sbo[f],
@@ -799,6 +808,109 @@ class Canvas:
         if seg_start_ci is not None and seg_end_ci is not None:
             out.update(run_start_ci=np.asarray(seg_start_ci)[f], run_end_ci=np.asarray(seg_end_ci)[l])
         return out
+
+    SEGMENT_TABLES_CAP = 65536                  # room Canvas.segment_tables / call_diploid_ids offer first when no cap_seg is given (a refused call reports the count: one repeat)
+
+    def _segment_table_args(self, what, chr_offset, start, stop, segment_id, cov, cap_seg, counts):
+        """checks the bins' tensors and picks the room for the tables: (n, nchr, cap, off, counts)"""
+        torch = self.torch
+        off = np.ascontiguousarray(chr_offset, np.int64)
+        if off.ndim != 1 or len(off) < 2:
+            raise CanvasError(what + ": chr_offset holds nchr + 1 entries, at least one chromosome")
+        n, nchr = int(off[-1]), len(off) - 1
+        for t in (start, stop, segment_id):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.numel() >= n and (t.numel() == 0 or t.device == self.device), what + ": start / stop / segment_id must be dense int32 tensors on the context's device"
+        if cov is not None:
+            assert cov.dtype == torch.float64 and cov.is_contiguous() and cov.dim() == 1 and cov.numel() >= n and cov.device == self.device, what + ": cov must be a dense float64 tensor on the context's device"
+            if counts is None:
+                counts = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)
+            assert counts.dtype == torch.float32 and counts.is_contiguous() and counts.dim() == 1 and counts.numel() >= n and counts.device == self.device
+        cap = max(0, min(n, self.SEGMENT_TABLES_CAP)) if cap_seg is None else int(cap_seg)
+        return n, nchr, cap, off, counts
+
+    @staticmethod
+    def _segment_tables(nchr, cap):
+        c1 = max(cap, 1)
+        return dict(nseg=C.c_int64(-1), chr_seg_offset=np.zeros(nchr + 1, np.int64), seg_begin=np.zeros(c1, np.int32), seg_end=np.zeros(c1, np.int32), seg_bin_offset=np.zeros(c1 + 1, np.int64),
+                    seg_ci4=np.zeros((c1, 4), np.int32))
+
+    @staticmethod
+    def _segment_tables_result(t, counts, n):
+        s = t["nseg"].value
+        ci = t["seg_ci4"][:s]
+        return dict(nseg=s, chr_seg_offset=t["chr_seg_offset"], seg_begin=t["seg_begin"][:s], seg_end=t["seg_end"][:s], seg_bin_offset=t["seg_bin_offset"][:s + 1], seg_ci4=ci,
+                    seg_start_ci=ci[:, 0:2], seg_end_ci=ci[:, 2:4], counts=None if counts is None else counts[:n])
+
+    def segment_tables(self, chr_offset, start, stop, segment_id, cov=None, cap_seg=None, counts=None):
+        """Segments.ReadSegments on device-resident bins (canvas_segment_tables): chr_offset[nchr + 1] as chromosome_offsets returns it, start / stop / segment_id int32 device
+        tensors (the first chr_offset[-1] entries count), cov the float64 coverage or None.  A segment starts at the first bin of a chromosome and wherever the id differs from the
+        bin before.  Returns dict(nseg, chr_seg_offset, seg_begin, seg_end, seg_bin_offset, seg_ci4 = [start.lo, start.hi, end.lo, end.hi] per segment, seg_start_ci, seg_end_ci,
+        counts): the host tables call_diploid / call_somatic take, and counts = float32 device tensor of (float)cov (None without cov; written into `counts` when given).
+        cap_seg: room for that many segments, more are refused; None: SEGMENT_TABLES_CAP first and, if the sample has more, once more with the count the refusal reported."""
+        n, nchr, cap, off, counts = self._segment_table_args("segment_tables", chr_offset, start, stop, segment_id, cov, cap_seg, counts)
+        self.torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        while True:
+            t = self._segment_tables(nchr, cap)
+            rc = self.lib.canvas_segment_tables(self.ctx, C.c_int64(n), C.c_int32(nchr), _np_ptr(off), C.c_void_p(start.data_ptr()), C.c_void_p(stop.data_ptr()), C.c_void_p(segment_id.data_ptr()),
+                                                C.c_void_p(cov.data_ptr()) if cov is not None else None, C.c_int64(cap), C.byref(t["nseg"]), _np_ptr(t["chr_seg_offset"]), _np_ptr(t["seg_begin"]),
+                                                _np_ptr(t["seg_end"]), _np_ptr(t["seg_bin_offset"]), _np_ptr(t["seg_ci4"]), C.c_void_p(counts.data_ptr()) if cov is not None else None)
+            if rc == -1 and cap_seg is None and cap < t["nseg"].value <= n:      # more segments than the first offer (any other refusal comes back from the repeat)
+                cap = t["nseg"].value
+                continue
+            self._check(rc)
+            return self._segment_tables_result(t, counts, n)
+
+    def call_diploid_ids(self, chr_offset, start, stop, segment_id, cov, chr_site_offset, site_pos, site_ref, site_alt, logistic=LOGISTIC_GERMLINE, cap_seg=None, counts=None):
+        """segment_tables, then call_diploid on its tables and float counts, in one library call (canvas_call_diploid_ids): the bins as for segment_tables (cov is required), the
+        sites as for call_diploid.  Returns call_diploid's dict (with run_start_ci / run_end_ci) plus `tables`, the dict of segment_tables.  cap_seg as for segment_tables."""
+        torch = self.torch
+        n, nchr, cap, off, counts = self._segment_table_args("call_diploid_ids", chr_offset, start, stop, segment_id, cov, cap_seg, counts)
+        if cov is None:
+            raise CanvasError("call_diploid_ids: the coverage is required")
+        csi = np.ascontiguousarray(chr_site_offset, np.int64)
+        for t in (site_pos, site_ref, site_alt):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.numel() == site_pos.numel() and (t.numel() == 0 or t.device == self.device)
+        if len(csi) != nchr + 1 or int(csi[-1]) != site_pos.numel():
+            raise CanvasError("call_diploid_ids: nchr + 1 site offsets that end at the number of sites")
+        b4 = np.ascontiguousarray(logistic, np.float64)
+        assert b4.shape == (4,)
+        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        while True:
+            t = self._segment_tables(nchr, cap)
+            o, outs = self._diploid_outputs(max(cap, 1))
+            rc = self.lib.canvas_call_diploid_ids(self.ctx, C.c_int64(n), C.c_int32(nchr), _np_ptr(off), C.c_void_p(start.data_ptr()), C.c_void_p(stop.data_ptr()), C.c_void_p(segment_id.data_ptr()),
+                                                  C.c_void_p(cov.data_ptr()), C.c_int64(cap), _np_ptr(csi), C.c_void_p(site_pos.data_ptr()), C.c_void_p(site_ref.data_ptr()),
+                                                  C.c_void_p(site_alt.data_ptr()), _np_ptr(b4), C.byref(t["nseg"]), _np_ptr(t["chr_seg_offset"]), _np_ptr(t["seg_begin"]), _np_ptr(t["seg_end"]),
+                                                  _np_ptr(t["seg_bin_offset"]), _np_ptr(t["seg_ci4"]), C.c_void_p(counts.data_ptr()), *outs)
+            if rc == -1 and cap_seg is None and cap < t["nseg"].value <= n:      # more segments than the first offer (any other refusal comes back from the repeat)
+                cap = t["nseg"].value
+                continue
+            self._check(rc)
+            tab = self._segment_tables_result(t, counts, n)
+            out = self._diploid_result(o, tab["nseg"], tab["seg_begin"], tab["seg_end"], tab["seg_bin_offset"], tab["seg_start_ci"], tab["seg_end_ci"])
+            out["tables"] = tab
+            return out
+
+    def germline_flow(self, bases, masks, hits, lens, is_autosome, chr_site_offset, site_pos, site_ref, site_alt, counts_per_bin=100, bin_size=-1, mode=MODE_TDR, flags=0,
+                      min_bins_per_gc=100, max_inter_bin_dist=1000000, is_y=None, pos0=None, logistic=LOGISTIC_GERMLINE, cap_bins=None):
+        """The germline sample from hit arrays to copy-number calls in one Python call, the counterpart of tumor_normal_flow: sample_pipeline (bin -> clean -> F2 -> PerSampleHMM ->
+        segment ids), then call_diploid_ids on the arrays it left on the device — no *.partitioned text and no per-bin array on the host in between.  The per-base inputs and
+        options are sample_pipeline's; the sites are call_diploid's (site_ref / site_alt may be the int32 counters snv_count filled).  Returns sample_pipeline's dict (bin_size,
+        total, n_out, lsd, off, nseg) plus bins (the cleaned chr / start / stop / gc / count tensors), cov, state, seg (device tensors, n_out entries) and calls =
+        call_diploid_ids' dict."""
+        torch = self.torch
+        cap = int(cap_bins) if cap_bins is not None else int(sum(int(l) for l in lens) // 50) + 64
+        mk = lambda dt: torch.empty(cap, dtype=dt, device=self.device)
+        out = dict(chr=mk(torch.int32), start=mk(torch.int32), stop=mk(torch.int32), gc=mk(torch.int32), count=mk(torch.float32))
+        cov, state, seg = mk(torch.float64), mk(torch.int32), mk(torch.int32)
+        torch.cuda.synchronize(self.device)        # the inputs may have been written on torch's stream
+        r = self.sample_pipeline(bases, masks, hits, lens, is_autosome, out, cov, state, seg, counts_per_bin=counts_per_bin, bin_size=bin_size, mode=mode, flags=flags,
+                                 min_bins_per_gc=min_bins_per_gc, max_inter_bin_dist=max_inter_bin_dist, is_y=is_y, pos0=pos0)
+        n = r["n_out"]
+        calls = self.call_diploid_ids(r["off"], out["start"], out["stop"], seg, cov, chr_site_offset, site_pos, site_ref, site_alt, logistic=logistic)
+        res = {k: r[k] for k in ("bin_size", "total", "n_out", "lsd", "off", "nseg")}
+        res.update(bins={k: v[:n] for k, v in out.items()}, cov=cov[:n], state=state[:n], seg=seg[:n], calls=calls)
+        return res
 
     def somatic_model_fit(self, coverage, maf, weight, length, coverage_weighting_factor, genome_length, min_coverage, max_coverage, minimum_purity_hard_limit=20,
                           min_minor_allele_coverage=0.0, is_enrichment=False, fixed_percent_purity=-1, fixed_coverage=-1, all_models=True, **params):

@@ -146,6 +146,17 @@ namespace CanvasHipInterop
             long[] chrSiteOffset, IntPtr dSitePos, IntPtr dSiteRef, IntPtr dSiteAlt, double[] logistic4,
             double[] segMedianCount, long[] segSiteOffset, int[] segInformative, double[] segMedianMaf, int[] segCn, int[] segMcc, double[] segDist, double[] segDist2, int[] segQScore,
             out long nRuns, long[] runFirst, long[] runLast, int[] runQScore, int[] runFilter, double[] runMedianCount, double[] scalars2, long[] info4);
+        // Segments.ReadSegments on device-resident bins: the host tables canvas_call_diploid / canvas_call_somatic take, from the per-bin segment ids a partition entry left
+        // (a segment starts at the first bin of a chromosome and wherever the id differs from the bin before).  Per-segment arrays hold capSeg entries (segBinOffset capSeg + 1,
+        // segCi4 4 * capSeg: {start.lo, start.hi, end.lo, end.hi}); more than capSeg segments are refused with nSeg set.  dCov (double, or IntPtr.Zero) given: dCountF32[i] = (float)dCov[i]
+        [DllImport(Lib)] public static extern int canvas_segment_tables(IntPtr ctx, long nbins, int nchr, long[] chrOffset, IntPtr dStart, IntPtr dStop, IntPtr dSegmentId, IntPtr dCov, long capSeg,
+            out long nSeg, long[] chrSegOffset, int[] segBegin, int[] segEnd, long[] segBinOffset, int[] segCi4, IntPtr dCountF32);
+        // canvas_segment_tables, then canvas_call_diploid on its tables and float counts (dCov and dCountF32 required; the call's arrays hold capSeg entries): four waits
+        [DllImport(Lib)] public static extern int canvas_call_diploid_ids(IntPtr ctx, long nbins, int nchr, long[] chrOffset, IntPtr dStart, IntPtr dStop, IntPtr dSegmentId, IntPtr dCov, long capSeg,
+            long[] chrSiteOffset, IntPtr dSitePos, IntPtr dSiteRef, IntPtr dSiteAlt, double[] logistic4,
+            out long nSeg, long[] chrSegOffset, int[] segBegin, int[] segEnd, long[] segBinOffset, int[] segCi4, IntPtr dCountF32,
+            double[] segMedianCount, long[] segSiteOffset, int[] segInformative, double[] segMedianMaf, int[] segCn, int[] segMcc, double[] segDist, double[] segDist2, int[] segQScore,
+            out long nRuns, long[] runFirst, long[] runLast, int[] runQScore, int[] runFilter, double[] runMedianCount, double[] scalars2, long[] info4);
 
         // CanvasSomaticCaller.ModelOverallCoverageAndPurity's grid search (SomaticCaller.cs:1870-2117) over the usable segments (coverage / maf / weight double, length int:
         // device arrays when inputsOnDevice != 0, host arrays otherwise); the structs mirror include/canvas_hip.h field by field.  The cluster term of ModelDeviation is not

@@ -653,6 +653,35 @@ int32_t canvas_call_diploid(canvas_ctx* ctx, int64_t nbins, const float* d_count
                             int64_t* h_nruns, int64_t* h_run_first, int64_t* h_run_last, int32_t* h_run_qscore, int32_t* h_run_filter, double* h_run_median_count,
                             double* h_scalars2, int64_t* h_info4);
 
+/* Segments.ReadSegments (CanvasCommon/Segments.cs:52-115) on device-resident bins: the host segment tables canvas_call_diploid / canvas_call_somatic take, from the per-bin
+ * d_segment_id every partition entry leaves (canvas_sample_pipeline, canvas_segment_ids*, ...).  Bins: d_start / d_stop / d_segment_id (int32[nbins]) grouped by chromosome,
+ * h_chr_offset[nchr+1] as canvas_chromosome_offsets returns it (empty chromosomes anywhere).  Bin i starts a segment when it is the first bin of its chromosome or
+ * d_segment_id[i] != d_segment_id[i-1] (GroupByAdjacent: only adjacency counts; an id that returns is a new segment, negative ids are ordinary values).
+ * *h_nseg = segments; h_chr_seg_offset[nchr+1] = segments in front of each chromosome; per segment Begin (start of its first bin), End (stop of its last bin),
+ * h_seg_bin_offset[nseg+1] (index of its first bin; [nseg] = nbins) and h_seg_ci4 = { start.lo, start.hi, end.lo, end.hi } (GetStartConfidenceInterval / GetEndConfidenceInterval:
+ * half length = (int)Math.Round((stop - start) / 2.0, AwayFromZero); the neighbouring bin is used only when it lies in the same chromosome and abuts).  The per-segment arrays
+ * hold cap_seg entries (h_seg_bin_offset cap_seg + 1, h_seg_ci4 4 * cap_seg); the copies from the device are sized by min(cap_seg, nbins) because the count is known only after
+ * the wait, so cap_seg is best near the expected count (a refused call reports the count).  d_cov (double[nbins], may be NULL) given: d_count_f32[i] = (float)d_cov[i] (device,
+ * nbins floats, caller-owned) — for a canvas_quantize_f2 coverage that is float.Parse of the text CanvasPartition writes (DESIGN 4 "Segment tables").
+ * CANVAS_ERR_INVALID, decided on the host arguments before the context is looked at (*h_nseg untouched): nbins < 1, a negative cap_seg, h_chr_offset that does not start
+ * at 0 / decreases / does not end at nbins.  Decided on the device (*h_nseg is written, the tables are not): a start that decreases within a chromosome (the message names
+ * the first such bin), stop < start, a non-finite d_cov, nseg >= 2^31, nseg > cap_seg.  The call waits once. */
+int32_t canvas_segment_tables(canvas_ctx* ctx, int64_t nbins, int32_t nchr, const int64_t* h_chr_offset /* nchr+1 */, const int32_t* d_start, const int32_t* d_stop,
+                              const int32_t* d_segment_id, const double* d_cov, int64_t cap_seg, int64_t* h_nseg, int64_t* h_chr_seg_offset /* nchr+1 */, int32_t* h_seg_begin,
+                              int32_t* h_seg_end, int64_t* h_seg_bin_offset /* cap_seg+1 */, int32_t* h_seg_ci4 /* 4*cap_seg */, float* d_count_f32);
+/* canvas_segment_tables, then canvas_call_diploid on the tables and the float counts it left: the bins' arrays, cap_seg and the table outputs of the former (d_cov and d_count_f32
+ * are required), the sites, coefficients and outputs of the latter (arrays of cap_seg entries, h_seg_site_offset cap_seg + 1).  The refusals of both, in that order.  The call
+ * waits four times. */
+int32_t canvas_call_diploid_ids(canvas_ctx* ctx, int64_t nbins, int32_t nchr, const int64_t* h_chr_offset /* nchr+1 */, const int32_t* d_start, const int32_t* d_stop,
+                                const int32_t* d_segment_id, const double* d_cov, int64_t cap_seg, const int64_t* h_chr_site_offset /* nchr+1 */, const int32_t* d_site_pos,
+                                const int32_t* d_site_ref, const int32_t* d_site_alt, const double* h_logistic4,
+                                int64_t* h_nseg, int64_t* h_chr_seg_offset /* nchr+1 */, int32_t* h_seg_begin, int32_t* h_seg_end, int64_t* h_seg_bin_offset /* cap_seg+1 */,
+                                int32_t* h_seg_ci4 /* 4*cap_seg */, float* d_count_f32,
+                                double* h_seg_median_count, int64_t* h_seg_site_offset /* cap_seg+1 */, int32_t* h_seg_informative, double* h_seg_median_maf, int32_t* h_seg_cn,
+                                int32_t* h_seg_mcc, double* h_seg_dist, double* h_seg_dist2, int32_t* h_seg_qscore,
+                                int64_t* h_nruns, int64_t* h_run_first, int64_t* h_run_last, int32_t* h_run_qscore, int32_t* h_run_filter, double* h_run_median_count,
+                                double* h_scalars2, int64_t* h_info4);
+
 /* ---- CanvasSomaticCaller: the purity / ploidy model fit (CanvasSomaticCaller/SomaticCaller.cs:1870-2117, ModelOverallCoverageAndPurity's grid search) ---- */
 #define CANVAS_SOMATIC_TILE 256                /* segments per tile of the device kernel: more segments than this take its tile loop */
 #define CANVAS_SOMATIC_MAX_CN 10               /* largest MaximumCopyNumber: PercentCN rows always hold CANVAS_SOMATIC_MAX_CN + 1 entries (0 beyond MaximumCopyNumber) */
