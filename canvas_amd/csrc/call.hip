@@ -708,11 +708,12 @@ static int sc_qscore(const canvas_somatic_call_params& p, long long binCount, in
 // Convert.ToInt32(float): round half to even; false when the result leaves int32 (OverflowException) or the value is NaN
 static bool sc_to_int32(float v, int& out) { const double r = nearbyint((double)v); if (!(r >= -2147483648.0 && r <= 2147483647.0)) return false; out = (int)r; return true; }
 
-extern "C" int32_t canvas_call_somatic(canvas_ctx* ctx, int64_t nbins, const float* d_count, int32_t nchr, const int64_t* h_chr_seg_offset, const int32_t* h_seg_begin,
-                                       const int32_t* h_seg_end, const int64_t* h_seg_bin_offset, const int64_t* h_chr_site_offset, const int32_t* d_site_pos,
-                                       const int32_t* d_site_ref, const int32_t* d_site_alt, const int32_t* h_seg_ref_cn, const int64_t* h_chr_excl_offset,
-                                       const int32_t* h_excl_start, const int32_t* h_excl_stop, const canvas_somatic_call_params* params, const canvas_somatic_call_out* out,
-                                       canvas_somatic_call_scalars* h_scalars, canvas_somatic_result* h_fit) {
+// the body of canvas_call_somatic, shared with canvas_call_somatic_ids (which builds the host tables and the reference copy numbers from the bins' segment ids first)
+static int32_t sc_call_somatic(canvas_ctx* ctx, int64_t nbins, const float* d_count, int32_t nchr, const int64_t* h_chr_seg_offset, const int32_t* h_seg_begin,
+                               const int32_t* h_seg_end, const int64_t* h_seg_bin_offset, const int64_t* h_chr_site_offset, const int32_t* d_site_pos,
+                               const int32_t* d_site_ref, const int32_t* d_site_alt, const int32_t* h_seg_ref_cn, const int64_t* h_chr_excl_offset,
+                               const int32_t* h_excl_start, const int32_t* h_excl_stop, const canvas_somatic_call_params* params, const canvas_somatic_call_out* out,
+                               canvas_somatic_call_scalars* h_scalars, canvas_somatic_result* h_fit) {
 #define SC_REFUSE(msg) do { if (ctx) ctx->err = std::string("canvas_call_somatic: ") + (msg); return CANVAS_ERR_INVALID; } while (0)
     if (nchr < 0 || nbins < 0 || !h_chr_seg_offset || !h_chr_site_offset || !params || !out || !h_scalars || !h_fit) SC_REFUSE("bad arguments");
     if (h_chr_seg_offset[0] != 0 || h_chr_site_offset[0] != 0) SC_REFUSE("the chromosome offsets start at 0");
@@ -1077,4 +1078,35 @@ extern "C" int32_t canvas_call_somatic(canvas_ctx* ctx, int64_t nbins, const flo
     R.nruns = nruns; R.reported_purity = reportedPurity; R.purity_model_fit = h_fit->deviation; R.inter_model_distance = h_fit->inter_model_distance;
     R.estimated_chromosome_count = overallCount; R.heterogeneity_proportion = 0; R.stages = 6; R.stage6_ms = lap();
     return CANVAS_OK;
+}
+
+extern "C" int32_t canvas_call_somatic(canvas_ctx* ctx, int64_t nbins, const float* d_count, int32_t nchr, const int64_t* h_chr_seg_offset, const int32_t* h_seg_begin,
+                                       const int32_t* h_seg_end, const int64_t* h_seg_bin_offset, const int64_t* h_chr_site_offset, const int32_t* d_site_pos,
+                                       const int32_t* d_site_ref, const int32_t* d_site_alt, const int32_t* h_seg_ref_cn, const int64_t* h_chr_excl_offset,
+                                       const int32_t* h_excl_start, const int32_t* h_excl_stop, const canvas_somatic_call_params* params, const canvas_somatic_call_out* out,
+                                       canvas_somatic_call_scalars* h_scalars, canvas_somatic_result* h_fit) {
+    return sc_call_somatic(ctx, nbins, d_count, nchr, h_chr_seg_offset, h_seg_begin, h_seg_end, h_seg_bin_offset, h_chr_site_offset, d_site_pos, d_site_ref, d_site_alt, h_seg_ref_cn,
+                           h_chr_excl_offset, h_excl_start, h_excl_stop, params, out, h_scalars, h_fit);
+}
+
+// canvas_segment_tables (segtab.hip), canvas_reference_copy_numbers (partstate.hip) on its tables, then the call: the somatic sample from per-bin segment ids to copy-number
+// calls without a per-bin array leaving the device.  One wait for the tables and the call's own.
+extern "C" int32_t canvas_call_somatic_ids(canvas_ctx* ctx, int64_t nbins, int32_t nchr, const int64_t* h_chr_offset, const int32_t* d_start, const int32_t* d_stop, const int32_t* d_segment_id,
+                                           const double* d_cov, int64_t cap_seg, const int64_t* h_chr_site_offset, const int32_t* d_site_pos, const int32_t* d_site_ref, const int32_t* d_site_alt,
+                                           const int64_t* h_ploidy_offset, const int32_t* h_ploidy_start, const int32_t* h_ploidy_end, const int32_t* h_ploidy_cn,
+                                           const int64_t* h_chr_excl_offset, const int32_t* h_excl_start, const int32_t* h_excl_stop, const canvas_somatic_call_params* params,
+                                           int64_t* h_nseg, int64_t* h_chr_seg_offset, int32_t* h_seg_begin, int32_t* h_seg_end, int64_t* h_seg_bin_offset, int32_t* h_seg_ci4, float* d_count_f32,
+                                           int32_t* h_seg_ref_cn, const canvas_somatic_call_out* out, canvas_somatic_call_scalars* h_scalars, canvas_somatic_result* h_fit) {
+    if (!d_cov || !d_count_f32 || (cap_seg > 0 && !h_seg_ref_cn)) {
+        if (ctx) ctx->err = "canvas_call_somatic_ids: bad arguments (the call needs the coverage, room for the float counts and for the reference copy numbers)";
+        return CANVAS_ERR_INVALID;
+    }
+    // canvas_segment_tables decides its host arguments before it looks at the context, so a NULL ctx still reports them
+    int32_t rc = canvas_segment_tables(ctx, nbins, nchr, h_chr_offset, d_start, d_stop, d_segment_id, d_cov, cap_seg, h_nseg, h_chr_seg_offset, h_seg_begin, h_seg_end, h_seg_bin_offset, h_seg_ci4,
+                                       d_count_f32);
+    if (rc) return rc;
+    rc = canvas_reference_copy_numbers(nchr, h_chr_seg_offset, h_seg_begin, h_seg_end, h_ploidy_offset, h_ploidy_start, h_ploidy_end, h_ploidy_cn, h_seg_ref_cn);
+    if (rc) { ctx->err = "canvas_call_somatic_ids: bad ploidy records (offsets that do not start at 0 or decrease, a missing array, or a copy number outside 0..4)"; return rc; }
+    return sc_call_somatic(ctx, nbins, d_count_f32, nchr, h_chr_seg_offset, h_seg_begin, h_seg_end, h_seg_bin_offset, h_chr_site_offset, d_site_pos, d_site_ref, d_site_alt, h_seg_ref_cn,
+                           h_chr_excl_offset, h_excl_start, h_excl_stop, params, out, h_scalars, h_fit);
 }

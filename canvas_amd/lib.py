@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "canvas_segment_select", "canvas_segment_select_plan", "canvas_call_diploid",
     "canvas_somatic_model_fit", "canvas_call_somatic",
     "canvas_segment_tables", "canvas_call_diploid_ids",
+    "canvas_partition_states_cbs", "canvas_partition_states_breakpoints", "canvas_reference_copy_numbers", "canvas_call_somatic_ids",
 ]
 
 
@@ -265,6 +266,23 @@ def segment_select_plan():
     if rc:
         raise CanvasError(f"canvas_segment_select_plan: error {rc}")
     return dict(wave_max=int(out[0]), lds_max=int(out[1]), tile=int(out[2]), launches=int(out[3]), forced=(None, "wave", "lds", "tiled")[int(out[4])])
+
+
+def reference_copy_numbers(chr_seg_offset, seg_begin, seg_end, ploidy=None):
+    """canvas_reference_copy_numbers (plain host code, no GPU): PloidyInfo.GetReferenceCopyNumber per segment.  Segments grouped by chromosome (chr_seg_offset[nchr + 1],
+    zero-based begins / ends); ploidy = per chromosome (one-based starts, ends, copy numbers) as Canvas.segment_ids takes it, None: 2 everywhere.  Returns an int32 array."""
+    lib = load_library()
+    cso = np.ascontiguousarray(chr_seg_offset, np.int64); beg = np.ascontiguousarray(seg_begin, np.int32); end = np.ascontiguousarray(seg_end, np.int32)
+    nchr = len(cso) - 1
+    if nchr < 0 or len(beg) != len(end) or int(cso[-1]) != len(beg):
+        raise CanvasError("reference_copy_numbers: one begin / end per segment, nchr + 1 chromosome offsets that end at the number of segments")
+    po, ps, pe, pc = Canvas._interval_tables(ploidy, nchr, columns=3)
+    out = np.zeros(len(beg), np.int32)
+    opt = lambda a: _np_ptr(a) if a is not None else None
+    rc = lib.canvas_reference_copy_numbers(C.c_int32(nchr), _np_ptr(cso), _np_ptr(beg), _np_ptr(end), opt(po), opt(ps), opt(pe), opt(pc), _np_ptr(out))
+    if rc:
+        raise CanvasError(f"canvas_reference_copy_numbers: error {rc} (offsets that do not start at 0 or decrease, or a copy number outside 0..4)")
+    return out
 
 
 class Canvas:
@@ -892,20 +910,44 @@ class Canvas:
             return out
 
     def germline_flow(self, bases, masks, hits, lens, is_autosome, chr_site_offset, site_pos, site_ref, site_alt, counts_per_bin=100, bin_size=-1, mode=MODE_TDR, flags=0,
-                      min_bins_per_gc=100, max_inter_bin_dist=1000000, is_y=None, pos0=None, logistic=LOGISTIC_GERMLINE, cap_bins=None):
+                      min_bins_per_gc=100, max_inter_bin_dist=1000000, is_y=None, pos0=None, logistic=LOGISTIC_GERMLINE, cap_bins=None, method="hmm", partition=None,
+                      excluded=None, ploidy=None):
         """The germline sample from hit arrays to copy-number calls in one Python call, the counterpart of tumor_normal_flow: sample_pipeline (bin -> clean -> F2 -> PerSampleHMM ->
         segment ids), then call_diploid_ids on the arrays it left on the device — no *.partitioned text and no per-bin array on the host in between.  The per-base inputs and
         options are sample_pipeline's; the sites are call_diploid's (site_ref / site_alt may be the int32 counters snv_count filled).  Returns sample_pipeline's dict (bin_size,
         total, n_out, lsd, off, nseg) plus bins (the cleaned chr / start / stop / gc / count tensors), cov, state, seg (device tensors, n_out entries) and calls =
-        call_diploid_ids' dict."""
+        call_diploid_ids' dict.
+        method "cbs" / "wavelets" (the methods the reference's workflows run): bin_sample -> clean -> quantize_f2 -> chromosome_offsets -> cbs / wavelets with the options in
+        `partition` (is_germline=True unless it says otherwise) -> partition_states -> segment_ids with max_inter_bin_dist and the optional excluded / ploidy ->
+        call_diploid_ids, stage by stage on the device; `state` then holds the partition states.  excluded / ploidy need one of these two methods."""
         torch = self.torch
+        if method not in ("hmm", "cbs", "wavelets"):
+            raise CanvasError("germline_flow: method is \"hmm\", \"cbs\" or \"wavelets\"")
+        if method == "hmm" and (partition or excluded is not None or ploidy is not None):
+            raise CanvasError("germline_flow: partition options, excluded intervals and ploidy records need method \"cbs\" or \"wavelets\"")
         cap = int(cap_bins) if cap_bins is not None else int(sum(int(l) for l in lens) // 50) + 64
         mk = lambda dt: torch.empty(cap, dtype=dt, device=self.device)
         out = dict(chr=mk(torch.int32), start=mk(torch.int32), stop=mk(torch.int32), gc=mk(torch.int32), count=mk(torch.float32))
         cov, state, seg = mk(torch.float64), mk(torch.int32), mk(torch.int32)
         torch.cuda.synchronize(self.device)        # the inputs may have been written on torch's stream
-        r = self.sample_pipeline(bases, masks, hits, lens, is_autosome, out, cov, state, seg, counts_per_bin=counts_per_bin, bin_size=bin_size, mode=mode, flags=flags,
-                                 min_bins_per_gc=min_bins_per_gc, max_inter_bin_dist=max_inter_bin_dist, is_y=is_y, pos0=pos0)
+        if method == "hmm":
+            r = self.sample_pipeline(bases, masks, hits, lens, is_autosome, out, cov, state, seg, counts_per_bin=counts_per_bin, bin_size=bin_size, mode=mode, flags=flags,
+                                     min_bins_per_gc=min_bins_per_gc, max_inter_bin_dist=max_inter_bin_dist, is_y=is_y, pos0=pos0)
+        else:
+            if pos0 is None:
+                _, _, total, bs = self.bin_sample(bases, masks, hits, lens, is_autosome, counts_per_bin, bin_size, mode, out=out)
+            else:
+                _, _, total, bs = self.bin_sample_packed(bases, hits, lens, pos0, is_autosome, counts_per_bin, bin_size, mode, out=out)
+            n_out, lsd, _ = self.clean(out, total, is_autosome, flags, min_bins_per_gc, is_y=is_y)
+            self.quantize_f2(out["count"], n_out, out=cov)
+            off = self.chromosome_offsets(out["chr"], n_out, len(lens))
+            if method == "cbs":
+                seg_len, nseg_chr, _ = self.cbs(cov, off, **(partition or {}))
+                self.partition_states(off, seg_len=seg_len, nseg=nseg_chr, out=state)
+            else:
+                self.partition_states(off, breakpoints=self.wavelets(cov, off, **dict(dict(is_germline=True), **(partition or {}))), out=state)
+            _, nseg = self.segment_ids(off, state, out["start"], out["stop"], max_inter_bin_dist, excluded, out=seg, ploidy=ploidy)
+            r = dict(bin_size=bs, total=total, n_out=n_out, lsd=lsd, off=off, nseg=nseg)
         n = r["n_out"]
         calls = self.call_diploid_ids(r["off"], out["start"], out["stop"], seg, cov, chr_site_offset, site_pos, site_ref, site_alt, logistic=logistic)
         res = {k: r[k] for k in ("bin_size", "total", "n_out", "lsd", "off", "nseg")}
@@ -998,22 +1040,9 @@ class Canvas:
         if seg_ref_cn is not None:
             ref = np.ascontiguousarray(seg_ref_cn, np.int32)
             assert ref.shape == (nseg,)
-        eo = es = ee = None
-        if excluded is not None:
-            assert len(excluded) == nchr
-            eo = np.concatenate([[0], np.cumsum([len(e[0]) for e in excluded])]).astype(np.int64)
-            es = np.ascontiguousarray(np.concatenate([np.asarray(e[0], np.int32) for e in excluded] + [np.zeros(1, np.int32)]), np.int32)
-            ee = np.ascontiguousarray(np.concatenate([np.asarray(e[1], np.int32) for e in excluded] + [np.zeros(1, np.int32)]), np.int32)
-        unknown = set(params) - set(SOMATIC_DEFAULTS) - set(SOMATIC_CALL_DEFAULTS)
-        if unknown:
-            raise TypeError("call_somatic: unknown parameters %s" % sorted(unknown))
-        fitp = SomaticParams(**dict(SOMATIC_DEFAULTS, **{k: v for k, v in params.items() if k in SOMATIC_DEFAULTS}))
-        own = dict(SOMATIC_CALL_DEFAULTS, genome_length=int(genome_length), **{k: v for k, v in params.items() if k in SOMATIC_CALL_DEFAULTS})
-        own["is_enrichment"] = int(bool(own["is_enrichment"]))
-        cp = SomaticCallParams(fit=fitp, **own)
-        n1 = max(nseg, 1)
-        arrays = {name: np.zeros(n1 + 1 if kind == "seg1" else n1, dt) for name, dt, kind in SOMATIC_CALL_OUT}
-        co = SomaticCallOut(*[arrays[name].ctypes.data for name, _, _ in SOMATIC_CALL_OUT])
+        eo, es, ee = self._interval_tables(excluded, nchr)
+        cp = self._somatic_call_params("call_somatic", genome_length, params)
+        arrays, co = self._somatic_call_outputs(max(nseg, 1))
         sc = SomaticCallScalars(); res = SomaticResult()
         fn = self.lib.canvas_call_somatic
         fn.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32] + [C.c_void_p] * 16
@@ -1021,17 +1050,96 @@ class Canvas:
         torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
         rc = fn(self.ctx, counts.numel(), C.c_void_p(counts.data_ptr()), nchr, _np_ptr(cso), _np_ptr(beg), _np_ptr(end), _np_ptr(sbo), _np_ptr(csi), C.c_void_p(site_pos.data_ptr()),
                 C.c_void_p(site_ref.data_ptr()), C.c_void_p(site_alt.data_ptr()), opt(ref), opt(eo), opt(es), opt(ee), C.byref(cp), C.byref(co), C.byref(sc), C.byref(res))
-        r = sc.nruns
-        out = {name: (arrays[name][:r] if kind == "run" else arrays[name][:nseg + 1] if kind == "seg1" else arrays[name][:nseg]) for name, _, kind in SOMATIC_CALL_OUT}
-        out["site_count"] = np.diff(out["seg_site_offset"])
-        out.update({name: getattr(sc, name) for name, _ in SomaticCallScalars._fields_})
-        out["fit"] = {name: (np.array(res.percent_cn[:fitp.maximum_copy_number + 1]) if name == "percent_cn" else getattr(res, name)) for name, _ in SomaticResult._fields_}
+        out = self._somatic_call_result(arrays, sc, res, cp, nseg)
         if rc != 0:
             e = CanvasError(f"libcanvas_hip error {rc}: {self.lib.canvas_last_error(self.ctx).decode()}")
             e.code = rc
             e.partial = out
             raise e
         return out
+
+    @staticmethod
+    def _interval_tables(intervals, nchr, columns=2):
+        """per chromosome (starts, stops[, values]) -> (offsets int64[nchr + 1], one int32 array per column, never empty); (None, ...) for None"""
+        if intervals is None:
+            return (None,) * (columns + 1)
+        assert len(intervals) == nchr
+        off = np.concatenate([[0], np.cumsum([len(e[0]) for e in intervals])]).astype(np.int64)
+        return (off,) + tuple(np.ascontiguousarray(np.concatenate([np.asarray(e[k], np.int32) for e in intervals] + [np.zeros(1, np.int32)]), np.int32) for k in range(columns))
+
+    @staticmethod
+    def _somatic_call_params(what, genome_length, params):
+        unknown = set(params) - set(SOMATIC_DEFAULTS) - set(SOMATIC_CALL_DEFAULTS)
+        if unknown:
+            raise TypeError("%s: unknown parameters %s" % (what, sorted(unknown)))
+        fitp = SomaticParams(**dict(SOMATIC_DEFAULTS, **{k: v for k, v in params.items() if k in SOMATIC_DEFAULTS}))
+        own = dict(SOMATIC_CALL_DEFAULTS, genome_length=int(genome_length), **{k: v for k, v in params.items() if k in SOMATIC_CALL_DEFAULTS})
+        own["is_enrichment"] = int(bool(own["is_enrichment"]))
+        return SomaticCallParams(fit=fitp, **own)
+
+    @staticmethod
+    def _somatic_call_outputs(n1):
+        """the host arrays of canvas_somatic_call_out (room for n1 segments) and the struct that points at them"""
+        arrays = {name: np.zeros(n1 + 1 if kind == "seg1" else n1, dt) for name, dt, kind in SOMATIC_CALL_OUT}
+        return arrays, SomaticCallOut(*[arrays[name].ctypes.data for name, _, _ in SOMATIC_CALL_OUT])
+
+    @staticmethod
+    def _somatic_call_result(arrays, sc, res, cp, nseg):
+        r = sc.nruns
+        out = {name: (arrays[name][:r] if kind == "run" else arrays[name][:nseg + 1] if kind == "seg1" else arrays[name][:nseg]) for name, _, kind in SOMATIC_CALL_OUT}
+        out["site_count"] = np.diff(out["seg_site_offset"])
+        out.update({name: getattr(sc, name) for name, _ in SomaticCallScalars._fields_})
+        out["fit"] = {name: (np.array(res.percent_cn[:cp.fit.maximum_copy_number + 1]) if name == "percent_cn" else getattr(res, name)) for name, _ in SomaticResult._fields_}
+        return out
+
+    def call_somatic_ids(self, chr_offset, start, stop, segment_id, cov, chr_site_offset, site_pos, site_ref, site_alt, genome_length, ploidy=None, excluded=None, cap_seg=None,
+                         counts=None, **params):
+        """segment_tables, the reference copy numbers of the segments from the optional ploidy records, then call_somatic on the tables and float counts, in one library call
+        (canvas_call_somatic_ids): the bins as for segment_tables (cov is required), the sites, excluded intervals and **params as for call_somatic, ploidy as for segment_ids
+        (per chromosome (one-based starts, ends, copy numbers); None: 2 everywhere).  Returns call_somatic's dict plus `tables`, the dict of segment_tables, and `seg_ref_cn`.
+        cap_seg as for segment_tables.  CanvasError carries .code and, for the somatic codes, .partial: the same dict with the stages that were filled."""
+        torch = self.torch
+        n, nchr, cap, off, counts = self._segment_table_args("call_somatic_ids", chr_offset, start, stop, segment_id, cov, cap_seg, counts)
+        if cov is None:
+            raise CanvasError("call_somatic_ids: the coverage is required")
+        csi = np.ascontiguousarray(chr_site_offset, np.int64)
+        for t in (site_pos, site_ref, site_alt):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.numel() == site_pos.numel() and (t.numel() == 0 or t.device == self.device)
+        if len(csi) != nchr + 1 or int(csi[-1]) != site_pos.numel():
+            raise CanvasError("call_somatic_ids: nchr + 1 site offsets that end at the number of sites")
+        eo, es, ee = self._interval_tables(excluded, nchr)
+        po, ps, pe, pc = self._interval_tables(ploidy, nchr, columns=3)
+        cp = self._somatic_call_params("call_somatic_ids", genome_length, params)
+        fn = self.lib.canvas_call_somatic_ids
+        fn.argtypes = [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 23
+        opt = lambda a: _np_ptr(a) if a is not None else None
+        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        while True:
+            t = self._segment_tables(nchr, cap)
+            arrays, co = self._somatic_call_outputs(max(cap, 1))
+            ref = np.zeros(max(cap, 1), np.int32)
+            sc = SomaticCallScalars(); res = SomaticResult()
+            rc = fn(self.ctx, n, nchr, _np_ptr(off), C.c_void_p(start.data_ptr()), C.c_void_p(stop.data_ptr()), C.c_void_p(segment_id.data_ptr()), C.c_void_p(cov.data_ptr()), cap,
+                    _np_ptr(csi), C.c_void_p(site_pos.data_ptr()), C.c_void_p(site_ref.data_ptr()), C.c_void_p(site_alt.data_ptr()), opt(po), opt(ps), opt(pe), opt(pc),
+                    opt(eo), opt(es), opt(ee), C.byref(cp), C.byref(t["nseg"]), _np_ptr(t["chr_seg_offset"]), _np_ptr(t["seg_begin"]), _np_ptr(t["seg_end"]),
+                    _np_ptr(t["seg_bin_offset"]), _np_ptr(t["seg_ci4"]), C.c_void_p(counts.data_ptr()), _np_ptr(ref), C.byref(co), C.byref(sc), C.byref(res))
+            if rc == -1 and cap_seg is None and cap < t["nseg"].value <= n:      # more segments than the first offer (any other refusal comes back from the repeat)
+                cap = t["nseg"].value
+                continue
+            if rc == -1:                      # refused by the tables, the ploidy records or the call's own checks: nothing to hand back
+                e = CanvasError(f"libcanvas_hip error {rc}: {self.lib.canvas_last_error(self.ctx).decode()}")
+                e.code = rc
+                e.partial = None
+                raise e
+            tab = self._segment_tables_result(t, counts, n)
+            out = self._somatic_call_result(arrays, sc, res, cp, tab["nseg"])
+            out.update(tables=tab, seg_ref_cn=ref[:tab["nseg"]])
+            if rc != 0:
+                e = CanvasError(f"libcanvas_hip error {rc}: {self.lib.canvas_last_error(self.ctx).decode()}")
+                e.code = rc
+                e.partial = out
+                raise e
+            return out
 
     def segment_ids(self, chr_offset, state, start, stop, max_inter_bin_dist=1000000, excluded=None, out=None, ploidy=None):
         """DeriveSegments + PostProcessSegments; excluded = per-chromosome list of (starts, stops) of the -b BED file; ploidy = per-chromosome list
@@ -1062,6 +1170,35 @@ class Canvas:
                                                              C.c_void_p(stop.data_ptr()), max_inter_bin_dist, _np_ptr(eo), _np_ptr(es), _np_ptr(ee),
                                                              C.c_void_p(seg.data_ptr()), C.byref(nseg)))
         return seg, nseg.value
+
+    def partition_states(self, chr_offset, seg_len=None, nseg=None, breakpoints=None, out=None):
+        """What cbs (seg_len device tensor + nseg per chromosome) or wavelets (breakpoints: one array of bin indices per chromosome) returned, as the per-bin state segment_ids
+        takes (canvas_partition_states_cbs / canvas_partition_states_breakpoints): the zero-based ordinal, within its chromosome, of the segment that holds the bin, -1
+        throughout a chromosome for which the method derives no segment.  Returns the int32 device tensor (chr_offset[-1] entries, a view of `out` when given)."""
+        torch = self.torch
+        off = np.ascontiguousarray(chr_offset, np.int64)
+        if off.ndim != 1 or len(off) < 2:
+            raise CanvasError("partition_states: chr_offset holds nchr + 1 entries, at least one chromosome")
+        if (seg_len is None) != (nseg is None) or (seg_len is None) == (breakpoints is None):
+            raise CanvasError("partition_states: either seg_len and nseg (CBS) or breakpoints (Wavelets)")
+        n, nchr = max(int(off[-1]), 0), len(off) - 1
+        if out is not None:
+            assert out.dtype == torch.int32 and out.is_contiguous() and out.dim() == 1 and out.numel() >= n and out.device == self.device, "partition_states: out must be a dense int32 tensor on the context's device"
+        state = out[:n] if out is not None else torch.empty(n, dtype=torch.int32, device=self.device)
+        torch.cuda.synchronize(self.device)        # the tensors may have been written on torch's stream
+        if breakpoints is None:
+            assert seg_len.dtype == torch.int32 and seg_len.is_contiguous() and seg_len.dim() == 1 and seg_len.numel() >= n and seg_len.device == self.device, "partition_states: seg_len must be a dense int32 tensor on the context's device"
+            hn = np.ascontiguousarray(nseg, np.int32)
+            if hn.shape != (nchr,):
+                raise CanvasError("partition_states: one nseg per chromosome")
+            self._check(self.lib.canvas_partition_states_cbs(self.ctx, C.c_int32(nchr), _np_ptr(off), C.c_void_p(seg_len.data_ptr()), _np_ptr(hn), C.c_void_p(state.data_ptr())))
+        else:
+            if len(breakpoints) != nchr:
+                raise CanvasError("partition_states: one array of breakpoints per chromosome")
+            bo = np.concatenate([[0], np.cumsum([len(b) for b in breakpoints])]).astype(np.int64)
+            bp = np.ascontiguousarray(np.concatenate([np.asarray(b, np.int32).reshape(-1) for b in breakpoints] + [np.zeros(1, np.int32)]), np.int32)
+            self._check(self.lib.canvas_partition_states_breakpoints(self.ctx, C.c_int32(nchr), _np_ptr(off), _np_ptr(bp), _np_ptr(bo), C.c_void_p(state.data_ptr())))
+        return state
 
     def cbs(self, cov, chr_offset, alpha=0.01, nperm=10000, undo=0, undo_sd=3.0):
         """CBSRunner.Run (CBSRunner.cs:40-151); undo: 0 None, 1 Prune, 2 SDUndo"""
@@ -1110,7 +1247,28 @@ class Canvas:
         return dict(bin_size=bs.value, total=total.value, n_out=nclean.value, lsd=lsd.value, off=off.copy(), nseg=nseg.value, prepared=prepared)
 
     def tumor_normal_flow(self, bases, masks, hits_t, fraglen_t, hits_n, lens, is_autosome, clean_flags, alpha=0.01, nperm=10000, counts_per_bin=100, is_y=None, keep=False, owner=None):
-        """BASELINE configs[4] in memory, the hand-offs of the reference's tumour / normal flow: CanvasBin -m GCContentWeighted on the tumour (bin size from
+        """BASELINE configs[4] in memory, from the hit arrays of a tumour / normal pair to the CBS segment lengths: see _tumor_normal, whose dict this returns."""
+        return self._tumor_normal(bases, masks, hits_t, fraglen_t, hits_n, lens, is_autosome, clean_flags, alpha, nperm, counts_per_bin, is_y, keep, owner)[0]
+
+    def somatic_flow(self, bases, masks, hits_t, fraglen_t, hits_n, lens, is_autosome, clean_flags, chr_site_offset, site_pos, site_ref, site_alt, genome_length, excluded=None,
+                     ploidy=None, alpha=0.01, nperm=10000, counts_per_bin=100, is_y=None, keep=False, max_inter_bin_dist=1000000, **somatic_params):
+        """The tumour / normal pair from hit arrays to somatic copy-number calls in one Python call: tumor_normal_flow, partition_states on the CBS lengths it left on the
+        device, segment_ids (max_inter_bin_dist, the optional excluded intervals and ploidy records) and call_somatic_ids (the sites, genome_length, the same excluded /
+        ploidy and **somatic_params, as call_somatic takes them) — no per-bin array on the host in between.  excluded reaches both segment_ids (which walks the intervals
+        of a chromosome by their end) and call_somatic (by their start): sort them by both.  Returns tumor_normal_flow's dict plus state and seg (int32 device tensors,
+        n_clean entries) and calls = call_somatic_ids' dict."""
+        res, dev = self._tumor_normal(bases, masks, hits_t, fraglen_t, hits_n, lens, is_autosome, clean_flags, alpha, nperm, counts_per_bin, is_y, keep, None)
+        off, R = dev["off"], dev["bins"]
+        state = self.partition_states(off, seg_len=dev["seg_len"], nseg=dev["nseg"])
+        seg, _ = self.segment_ids(off, state, R["start"], R["stop"], max_inter_bin_dist, excluded, ploidy=ploidy)
+        calls = self.call_somatic_ids(off, R["start"], R["stop"], seg, dev["cov"], chr_site_offset, site_pos, site_ref, site_alt, genome_length, ploidy=ploidy, excluded=excluded,
+                                      **somatic_params)
+        res.update(state=state, seg=seg, calls=calls)
+        return res
+
+    def _tumor_normal(self, bases, masks, hits_t, fraglen_t, hits_n, lens, is_autosome, clean_flags, alpha, nperm, counts_per_bin, is_y, keep, owner):
+        """tumor_normal_flow's work: (its dict, the arrays it left on the device: bins = the cleaned SoA, cov, off, seg_len, nseg).
+        BASELINE configs[4] in memory, the hand-offs of the reference's tumour / normal flow: CanvasBin -m GCContentWeighted on the tumour (bin size from
         the tumour's own rates) and -m TruncatedDynamicRange -z <that size> on the normal (same mask => same bins), CanvasNormalize's LSNorm ratio x 40
         (LSNormRatioCalculator.cs:31-44, CanvasNormalizeUtilities.cs:23-33), its "{count:F2}" file read back with float.Parse (IO.cs:21,40), CanvasClean,
         the F2 hand-off to CanvasPartition and CBS (alpha, nperm).  Returns a dict; with keep=True every intermediate array is kept for checking.
@@ -1159,7 +1317,7 @@ class Canvas:
         res.update(n_clean=n_out, local_sd=lsd, chr_offset=off, nseg=nseg, cbs_stats=stats, segments=int(nseg.sum()), stage_seconds=stage)
         if keep:
             res.update(cleaned={a: R[a][:n_out].clone() for a in R}, cov=cov.clone(), seg_len=seg_len)
-        return res
+        return res, dict(bins=R, cov=cov, off=off, seg_len=seg_len, nseg=nseg)
 
     def sample_pipeline_sharded(self, owner, bases, masks, hits, lens, is_autosome, out, cov, state, seg, counts_per_bin=100, bin_size=-1, mode=3, flags=0, min_bins_per_gc=100,
                                 max_inter_bin_dist=1000000, is_y=None, pos0=None):

@@ -224,6 +224,20 @@ namespace CanvasHipInterop
             long[] chrSiteOffset, IntPtr dSitePos, IntPtr dSiteRef, IntPtr dSiteAlt, int[] segRefCn, long[] chrExclOffset, int[] exclStart, int[] exclStop,
             ref canvas_somatic_call_params parameters, ref canvas_somatic_call_out output, out canvas_somatic_call_scalars scalars, out canvas_somatic_result result);
 
+        // Partition states: the segment lengths canvas_cbs leaves on the device, or the breakpoints canvas_wavelets returns, as the per-bin state canvas_segment_ids* takes
+        // (the zero-based ordinal of the bin's segment within its chromosome; -1 throughout a chromosome for which the method derives no segment).  One wait each
+        [DllImport(Lib)] public static extern int canvas_partition_states_cbs(IntPtr ctx, int nchr, long[] chrOffset, IntPtr dSegLen, int[] nSeg, IntPtr dState);
+        [DllImport(Lib)] public static extern int canvas_partition_states_breakpoints(IntPtr ctx, int nchr, long[] chrOffset, int[] breakpoints, long[] bpOffset, IntPtr dState);
+        // PloidyInfo.GetReferenceCopyNumber per segment (host code, no context): the ploidy records in the layout of canvas_segment_ids_ploidy (ploidyOffset null: 2 everywhere)
+        [DllImport(Lib)] public static extern int canvas_reference_copy_numbers(int nchr, long[] chrSegOffset, int[] segBegin, int[] segEnd, long[] ploidyOffset, int[] ploidyStart,
+            int[] ploidyEnd, int[] ploidyCn, int[] segRefCn);
+        // canvas_segment_tables, canvas_reference_copy_numbers, then canvas_call_somatic on the tables and float counts (dCov and dCountF32 required; the call's arrays hold capSeg entries)
+        [DllImport(Lib)] public static extern int canvas_call_somatic_ids(IntPtr ctx, long nbins, int nchr, long[] chrOffset, IntPtr dStart, IntPtr dStop, IntPtr dSegmentId, IntPtr dCov, long capSeg,
+            long[] chrSiteOffset, IntPtr dSitePos, IntPtr dSiteRef, IntPtr dSiteAlt, long[] ploidyOffset, int[] ploidyStart, int[] ploidyEnd, int[] ploidyCn,
+            long[] chrExclOffset, int[] exclStart, int[] exclStop, ref canvas_somatic_call_params parameters,
+            out long nSeg, long[] chrSegOffset, int[] segBegin, int[] segEnd, long[] segBinOffset, int[] segCi4, IntPtr dCountF32, int[] segRefCn,
+            ref canvas_somatic_call_out output, out canvas_somatic_call_scalars scalars, out canvas_somatic_result result);
+
         /// <summary>Turns a non-zero status into the module's own failure convention (message on stderr, exit code 1).</summary>
         public static void Check(IntPtr ctx, int status, string what)
         {

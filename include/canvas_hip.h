@@ -268,6 +268,23 @@ int32_t canvas_evenness_score(canvas_ctx* ctx, int32_t nchr, const double* d_cov
 /* GenomeSegmentationResults.SplitOverlappingSegments (GenomeSegmentationResults.cs:18-55) for one chromosome: host scalar code. */
 int32_t canvas_split_overlapping(int32_t nsamples, const uint32_t* const* h_start, const uint32_t* const* h_end, const int32_t* h_nseg,
                                  uint32_t* h_out_start, uint32_t* h_out_end, int32_t cap, int32_t* h_nout);
+/* Partition states: what canvas_cbs / canvas_cbs_undo (segment lengths on the device) and canvas_wavelets (breakpoints on the host) leave, as the per-bin d_state that
+ * canvas_segment_ids* takes.  d_state[i] (int32, h_chr_offset[nchr] entries) is the zero-based ordinal, within its chromosome, of the segment that holds bin i; every bin of a
+ * chromosome for which the method derives no segment gets -1.  canvas_segment_ids* starts a segment where state >= 0 && (first bin of the chromosome || state != previous
+ * state); on these states that is membership of the bin's start in the `starts` set SegmentationResultsProcessor.PostProcessSegments looks up, as long as the bins' starts
+ * increase strictly within a chromosome — so canvas_segment_ids*, unchanged, gives the ids CanvasPartition writes for that method.
+ * _cbs (CBSRunner.cs:127-137): the layout canvas_cbs documents, chromosome c has its h_nseg[c] lengths at d_seg_len + h_chr_offset[c]; segment k starts at the sum of the
+ *   lengths before it; h_nseg[c] == 0 gives -1 throughout.  CANVAS_ERR_INVALID, decided on the device through one error word and naming the first such chromosome:
+ *   h_nseg[c] outside 0 .. T_c, a length < 1, lengths that do not sum to T_c (h_nseg[c] > 0).  A refused call leaves d_state alone.
+ * _breakpoints (SegmentationInput.DeriveSegments, Segmentation.cs:83-125): chromosome c has the breakpoints h_bp_offset[c] .. h_bp_offset[c+1] of h_breakpoints (bin indices
+ *   within the chromosome, as canvas_wavelets returns them).  With at least two breakpoints and T_c > 10 the starts are bin 0 and every breakpoint (in any order, repeats
+ *   allowed); otherwise the chromosome is one segment (state 0).  T_c == 0 writes nothing.  CANVAS_ERR_INVALID before the context is looked at and before any launch:
+ *   offsets that do not start at 0 or decrease, a breakpoint outside [0, T_c).
+ * No per-bin array crosses to the host; each call waits once. */
+int32_t canvas_partition_states_cbs(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_offset /* nchr+1 */, const int32_t* d_seg_len, const int32_t* h_nseg /* nchr */,
+                                    int32_t* d_state);
+int32_t canvas_partition_states_breakpoints(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_offset /* nchr+1 */, const int32_t* h_breakpoints,
+                                            const int64_t* h_bp_offset /* nchr+1 */, int32_t* d_state);
 /* CBSRunner.Run / ChangePoint.ChangePoints (CBSRunner.cs:40-151, ChangePoint.cs:44-153), undo = None.
  * d_seg_len receives per chromosome the segment lengths, written at d_seg_len + h_chr_offset[c]; h_nseg[c] = count. */
 int32_t canvas_cbs(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, double alpha, uint32_t nperm,
@@ -856,6 +873,26 @@ int32_t canvas_call_somatic(canvas_ctx* ctx, int64_t nbins, const float* d_count
                             const int32_t* d_site_ref, const int32_t* d_site_alt, const int32_t* h_seg_ref_cn, const int64_t* h_chr_excl_offset /* nchr+1 */,
                             const int32_t* h_excl_start, const int32_t* h_excl_stop, const canvas_somatic_call_params* params, const canvas_somatic_call_out* out,
                             canvas_somatic_call_scalars* h_scalars, canvas_somatic_result* h_fit);
+
+/* PloidyInfo.GetReferenceCopyNumber (PloidyInfo.cs:56-72,92-110) per segment: plain host code, no context, no GPU.  Segments grouped by chromosome (h_chr_seg_offset[nchr+1],
+ * zero-based h_seg_begin / h_seg_end), the ploidy records in the layout of canvas_segment_ids_ploidy (h_ploidy_offset NULL: no records).  The counts run over the one-based
+ * interval [Begin + 1, End]; the first copy number with the strictly largest count wins; 2 when every count is 0 or the chromosome has no records.  CANVAS_ERR_INVALID for
+ * offsets that do not start at 0 or decrease, a missing array and a copy number outside 0..4. */
+int32_t canvas_reference_copy_numbers(int32_t nchr, const int64_t* h_chr_seg_offset /* nchr+1 */, const int32_t* h_seg_begin, const int32_t* h_seg_end,
+                                      const int64_t* h_ploidy_offset /* nchr+1 */, const int32_t* h_ploidy_start, const int32_t* h_ploidy_end, const int32_t* h_ploidy_cn,
+                                      int32_t* h_seg_ref_cn);
+/* canvas_segment_tables, canvas_reference_copy_numbers on its tables, then canvas_call_somatic on the tables and the float counts: the counterpart of canvas_call_diploid_ids.
+ * The bins' arrays, cap_seg and the table outputs of the first (d_cov and d_count_f32 are required), the ploidy records of the second (h_ploidy_offset NULL: 2 everywhere)
+ * with h_seg_ref_cn (cap_seg entries) as an output, the sites, excluded intervals, parameters and outputs of the third (arrays of cap_seg entries, seg_site_offset
+ * cap_seg + 1).  The refusals of the three, in that order; more than cap_seg segments are refused with *h_nseg set, as by canvas_call_diploid_ids. */
+int32_t canvas_call_somatic_ids(canvas_ctx* ctx, int64_t nbins, int32_t nchr, const int64_t* h_chr_offset /* nchr+1 */, const int32_t* d_start, const int32_t* d_stop,
+                                const int32_t* d_segment_id, const double* d_cov, int64_t cap_seg, const int64_t* h_chr_site_offset /* nchr+1 */, const int32_t* d_site_pos,
+                                const int32_t* d_site_ref, const int32_t* d_site_alt, const int64_t* h_ploidy_offset /* nchr+1 */, const int32_t* h_ploidy_start,
+                                const int32_t* h_ploidy_end, const int32_t* h_ploidy_cn, const int64_t* h_chr_excl_offset /* nchr+1 */, const int32_t* h_excl_start,
+                                const int32_t* h_excl_stop, const canvas_somatic_call_params* params,
+                                int64_t* h_nseg, int64_t* h_chr_seg_offset /* nchr+1 */, int32_t* h_seg_begin, int32_t* h_seg_end, int64_t* h_seg_bin_offset /* cap_seg+1 */,
+                                int32_t* h_seg_ci4 /* 4*cap_seg */, float* d_count_f32, int32_t* h_seg_ref_cn /* cap_seg */, const canvas_somatic_call_out* out,
+                                canvas_somatic_call_scalars* h_scalars, canvas_somatic_result* h_fit);
 
 /* ---- profiling hooks (hipEvent pairs recorded on the context's stream around the named kernels) --------------------- */
 /* on: 0 off; 1 every named scope; 2 only the scopes around the dominant (HBM-bound) kernel of CanvasBin — "bin_summary", "bin_summary_packed", "bin_pass",
