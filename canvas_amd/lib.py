@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "canvas_somatic_model_fit", "canvas_call_somatic",
     "canvas_segment_tables", "canvas_call_diploid_ids",
     "canvas_partition_states_cbs", "canvas_partition_states_breakpoints", "canvas_reference_copy_numbers", "canvas_call_somatic_ids",
+    "canvas_hits_from_bam",
 ]
 
 
@@ -712,6 +713,35 @@ class Canvas:
                                               C.c_void_p(site_alt.data_ptr()), ns, C.c_void_p(ref_counts.data_ptr()), C.c_void_p(alt_counts.data_ptr()),
                                               _np_ptr(info) if want_info else None))
         return ref_counts, alt_counts, info
+
+    def hits_from_bam(self, records, offsets, ref_id, length, mode=MODE_TDR, paired_end=False, hits=None, frag=None, state=None, nbytes=None, want_info=True):
+        """LoadObservedAlignmentsBAM (CanvasBin.cs:207-275) over one chunk of raw BAM records (the chunk format of snv_count: uint8 record bytes, int64 offsets).
+        hits (uint8, `length` positions), frag (int16, mode 5 only) and state (int64[8]) are updated; zeroed tensors are created when None — pass the returned ones
+        to the next chunk of the chromosome.  Returns (hits, frag or None, state, info[8] or None: stopped, seen, kept, kept out of range, malformed, position of the
+        last kept record, two reserved words).  want_info=False only queues the work."""
+        torch = self.torch
+        L = int(length)
+        created = hits is None or state is None or (frag is None and mode == MODE_GCW)
+        if hits is None:
+            hits = torch.zeros(max(L, 1), dtype=torch.uint8, device=self.device)
+        if frag is None and mode == MODE_GCW:
+            frag = torch.zeros(max(L, 1), dtype=torch.int16, device=self.device)
+        if state is None:
+            state = torch.zeros(8, dtype=torch.int64, device=self.device)
+        if created:                  # torch zeroes on its own stream; the kernels update the arrays on the context's
+            torch.cuda.current_stream(self.device).synchronize()
+        assert records.dtype == torch.uint8 and offsets.dtype == torch.int64 and hits.dtype == torch.uint8 and state.dtype == torch.int64
+        assert hits.numel() >= L and state.numel() >= 8 and (frag is None or (frag.dtype == torch.int16 and frag.numel() >= L))
+        for t in (records, offsets, hits, state) + (() if frag is None else (frag,)):      # the kernels read and write dense arrays on this context's device
+            assert t.is_contiguous() and t.dim() == 1 and (t.numel() == 0 or t.device == self.device), "hits_from_bam: tensors must be dense, one-dimensional and on the context's device"
+        nb = int(records.numel()) if nbytes is None else int(nbytes)
+        assert 0 <= nb <= records.numel()
+        info = np.zeros(8, np.int64) if want_info else None
+        self._check(self.lib.canvas_hits_from_bam(self.ctx, C.c_void_p(records.data_ptr()), C.c_uint64(nb), C.c_void_p(offsets.data_ptr()), C.c_int64(int(offsets.numel())),
+                                                  C.c_int32(int(ref_id)), C.c_int32(1 if paired_end else 0), C.c_int32(int(mode)), C.c_int64(L), C.c_void_p(hits.data_ptr()),
+                                                  C.c_void_p(frag.data_ptr()) if frag is not None else None, C.c_void_p(state.data_ptr()),
+                                                  _np_ptr(info) if want_info else None))
+        return hits, frag, state, info
 
     # ---- reference preparation (Tools/FlagUniqueKmers)
     def flag_unique_kmers(self, bases, lens, masks=None, max_table_bytes=0):

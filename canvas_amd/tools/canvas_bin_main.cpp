@@ -2,8 +2,9 @@
 // (CanvasBin.Run, CanvasBin.cs:955-972):
 //   CanvasBin -b S.bam -r kmer.fa -c chr1 -o chr1.dat -d 100 [-f filter.bed] [-p] [-m mode]            BAM -> per-chromosome intermediate
 //   CanvasBin -b S.bam -r kmer.fa -i chr1.dat -i chr2.dat ... -o S.binned -d 100 [-z size] [-y] [-m]   intermediates -> S.binned
-// Phase 1 keeps the reference's host work (FASTA and BAM parsing; BGZF inflate through zlib) and runs the per-base array
-// preparation on the GPU (possible mask from the FASTA case, BED exclusion, hit screening).  Phase 2 is canvas_bin_sample /
+// Phase 1 parses the FASTA on the host, inflates the BAM's BGZF blocks on the host threads and hands the raw record bytes to canvas_hits_from_bam (the read
+// filters, the hit counts and the fragment lengths are made on the GPU; load_bam is the same loop on the host, kept for input the device path hands back), then runs
+// the per-base array preparation on the GPU (possible mask from the FASTA case, BED exclusion, hit screening).  Phase 2 is canvas_bin_sample /
 // canvas_bin_sample_gcweighted.  The intermediate file is the reference's: protobuf-net's encoding of CanvasBin.IntermediateData (CanvasBin.cs:1037-1148,
 // protobuf_dat.hpp) including the bit-order quirk of its writer / reader pair, so the C# CanvasBin -c and this CanvasBin -i (or the other way round) can be mixed.
 // BAM flag semantics follow the SAM specification; Isas.SequencingFiles.BamReader is not part of /root/reference (parity unpinned):
@@ -88,6 +89,49 @@ static int load_bam(const std::string& bam, bool pairedEnd, const std::string& c
     }
     if (z.bad) return damaged_bam(bam);
     printf("Kept %ld of %ld total reads\n", kept, readCount);
+    return 0;
+}
+
+// The same loop on the device: the BAM travels as chunks of raw record bytes (tool_common.hpp: BamChunkLoop, inflation on the worker threads) and canvas_hits_from_bam
+// filters, counts and writes into dHits / dFrag (zeroed by the caller); the state is read once, behind the last chunk.  The host frames the records and evaluates the
+// read filters only to know where it may stop reading (a passing record of another reference: it is the last one uploaded) and, for GCContentWeighted, that the kept
+// positions do not go backwards — the one thing the fragment lengths on the device depend on.
+// 0: done, the line is printed.  1: the device or the runtime failed.  2: not done, nothing printed — load_bam has to answer: a file that is damaged, truncated or (mode 5)
+// not sorted gets load_bam's message, exit code and arrays, whatever they are.
+static int load_bam_device(const std::string& bam, const BamAt& b, bool pairedEnd, int mode, int64_t L, AsyncCtx& actx, canvas_ctx*& ctx, Dev& dHits, Dev* dFrag, Phases& ph) {
+    const double tLoop0 = Phases::now();
+    BamChunkLoop loop; loop.tool = "CanvasBin"; loop.bam = bam; loop.voff = b.voff; loop.quiet = true; loop.profile = "hits_from_bam"; loop.chunk_bytes_from("CANVAS_BIN_CHUNK_BYTES");
+    const int desired = b.ref; int32_t lastKept = INT32_MIN;
+    std::unique_ptr<Dev> dState;
+    const int rc = loop.run(actx, ctx, tLoop0,
+        [&](canvas_ctx* c) -> int {
+            dState.reset(new Dev(c, 64)); if (!dState->p) { fprintf(stderr, "CanvasBin: device allocation failed: %s\n", canvas_last_error(c)); return 1; }
+            const int64_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            TOOL_TRY(c, canvas_memcpy_h2d(c, dState->p, zero, 64));
+            return 0;
+        },
+        [&](const uint8_t* r, const BamFixed& a, int32_t bs) -> BamFrame {
+            if (32 + (int64_t)a.l_read_name + 4 * (int64_t)a.n_cigar > bs) return BamFrame::Fail;          // read_bam_record's check
+            if (a.refID == desired && mode != CANVAS_MODE_GC_CONTENT_WEIGHTED) return BamFrame::Take;       // cannot stop, and its position does not matter
+            if ((a.flag & (0x4 | 0x200 | 0x400 | 0x10 | 0x900)) || a.n_cigar == 0) return BamFrame::Take;
+            const uint32_t c0 = le32(r + 32 + a.l_read_name);
+            if ((c0 & 0xF) != 0 || (c0 >> 4) < 35 || (pairedEnd && !(a.flag & 0x2))) return BamFrame::Take;
+            if (a.refID != desired) return BamFrame::TakeAndStop;
+            if (a.pos < lastKept) return BamFrame::Fail;
+            lastKept = a.pos; return BamFrame::Take;
+        },
+        [&](void* dRec, uint64_t used, void* dOff, int64_t nrec) -> int32_t {
+            return canvas_hits_from_bam(ctx, (const uint8_t*)dRec, used, (const uint64_t*)dOff, nrec, desired, pairedEnd ? 1 : 0, mode, L, dHits.as<uint8_t>(),
+                                        dFrag ? dFrag->as<int16_t>() : nullptr, dState->as<int64_t>(), nullptr);
+        });
+    if (rc == 1) return 1;
+    int64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rc == 0) TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, st, dState->p, 64));
+    { const double tEnd = Phases::now(), rest = std::max(0.0, (tEnd - tLoop0) - loop.tInflate - loop.tDevice); ph.v.push_back({"inflate", tLoop0 + loop.tInflate + rest}); ph.v.push_back({"device_bam", tEnd}); }
+    if (getenv("CANVAS_TOOL_TIMING")) fprintf(stderr, "[bam] {\"records\": %lld, \"chunks\": %lld, \"record_bytes\": %lld, \"kernel_ms\": %.4f, \"inflate_s\": %.4f, \"device_wait_s\": %.4f, \"threads\": %d, \"host_path\": %d}\n",
+                                              loop.records, loop.chunks, loop.bytesUp, loop.kernelMs, loop.tInflate, loop.tDevice, io_threads(), rc != 0 || st[4] != 0 ? 1 : 0);
+    if (rc != 0 || st[4] != 0) return 2;          // (a record the kernels call malformed passed the framing: not expected; load_bam decides)
+    printf("Kept %ld of %ld total reads\n", (long)st[2], (long)st[1]);
     return 0;
 }
 
@@ -269,13 +313,34 @@ int main(int argc, char** argv) {
         std::vector<uint64_t> mw(words, 0);
         d.hits.assign(L, 0); if (mode == CANVAS_MODE_GC_CONTENT_WEIGHTED) d.frag.assign(L, 0);
         printf("Initialized alignment arrays\n");
-        if (int rc = load_bam(bam, a.has("paired-end"), chrom, mode, d.hits, d.frag)) return rc;
+        ph.mark("fasta");
+        // the observed alignments are made on the device (load_bam_device) unless the chromosome is empty or the test hook CANVAS_TOOL_HOST_BAM asks for the host loop
+        const bool gcw = mode == CANVAS_MODE_GC_CONTENT_WEIGHTED;
+        bool hostBam = L == 0 || (getenv("CANVAS_TEST_HOOKS") && getenv("CANVAS_TOOL_HOST_BAM")), onDevice = false;
+        std::unique_ptr<Dev> dHitsP, dFragP;
+        if (!hostBam) {
+            BamAt b; if (int rc = open_bam_at(bam, chrom, b)) return rc;
+            if (b.any) {                                     // (no reads for this chromosome: nothing to load and no line, as in load_bam)
+                if (!need_ctx()) return 1;
+                dHitsP.reset(new Dev(ctx, L)); if (gcw) dFragP.reset(new Dev(ctx, L * 2));
+                if (!dHitsP->p || (gcw && !dFragP->p)) { fprintf(stderr, "CanvasBin: device allocation of %lld bytes failed: %s\n", (long long)L * (gcw ? 3 : 1), canvas_last_error(ctx)); return 1; }
+                TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dHitsP->p, d.hits.data(), L));                      // zeros
+                if (gcw) TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dFragP->p, d.frag.data(), L * 2));
+                const int rc = load_bam_device(bam, b, a.has("paired-end"), mode, L, actx, ctx, *dHitsP, dFragP.get(), ph);
+                if (rc == 1) return 1;
+                if (rc == 2) hostBam = true; else onDevice = true;
+            }
+        }
+        if (hostBam) { if (int rc = load_bam(bam, a.has("paired-end"), chrom, mode, d.hits, d.frag)) return rc; }
         printf("Loaded observed alignments\n");
+        ph.mark("bam");
         if (!need_ctx()) return 1;
         if (L > 0) {
-            Dev dBases(ctx, L), dHits(ctx, L), dMask(ctx, words * 8);
+            if (!dHitsP) dHitsP.reset(new Dev(ctx, L));
+            Dev& dHits = *dHitsP;
+            Dev dBases(ctx, L), dMask(ctx, words * 8);
             TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dBases.p, fa[0].data(), L));
-            TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dHits.p, d.hits.data(), L));
+            if (!onDevice) TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dHits.p, d.hits.data(), L));
             TOOL_TRY(ctx, canvas_mask_from_fasta(ctx, dBases.as<uint8_t>(), L, dMask.as<uint64_t>()));
             if (!filter.empty()) {
                 std::map<std::string, std::vector<std::pair<int, int>>> bed; load_bed(filter, bed);
@@ -286,12 +351,16 @@ int main(int argc, char** argv) {
             TOOL_TRY(ctx, canvas_screen_hits(ctx, dHits.as<uint8_t>(), dMask.as<uint64_t>(), L));
             TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, mw.data(), dMask.p, words * 8));
             TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, d.hits.data(), dHits.p, L));
+            if (onDevice && gcw) TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, d.frag.data(), dFragP->p, L * 2));
         }
+        dHitsP.reset(); dFragP.reset();
+        ph.mark("device");
         pbdat::Data pd; pbdat::Chromosome& pc = pd[chrom];
         pbdat::pack_possible_msb(mw.data(), L, pc.possibleBytes, pc.bitsInLastByte);        // most significant bit first, as the C# writer (Q2)
         pc.observed.swap(d.hits); pc.fragmentLengths.swap(d.frag);
         if (!pbdat::write_file(out, pd, mode == CANVAS_MODE_GC_CONTENT_WEIGHTED)) { fprintf(stderr, "CanvasBin: cannot write %s\n", out.c_str()); return 1; }
         printf("Intermediate observedAlignments serialized\n");
+        ph.mark("write");
         return 0;
     }
 

@@ -3,7 +3,7 @@
 // LoadVariants (SNVReviewer.cs:86-152) and the two writers (:276-365) are host code as in the reference; ProcessBamFile + ProcessReadBases (:172-271) is
 // canvas_snv_count.  The host's part of the pileup is to INFLATE: the BAM file is mapped, the BGZF blocks of a chunk are inflated on the worker threads straight into
 // a pinned staging buffer, the block_size chain is walked once for the byte offset of every record (with the shape checks that need only the fixed fields), and the
-// chunk travels as raw record bytes.  Two staging buffers: chunk k + 1 is inflated while chunk k is uploaded and counted.
+// chunk travels as raw record bytes.  Two staging buffers: chunk k + 1 is inflated while chunk k is uploaded and counted.  (The loop: tool_common.hpp, BamChunkLoop.)
 // Not built: -c histogram / -c regionhistogram (HistogramVF.cs, developer modes): exit code 1 with a message.  Input that is not sorted by position (VCF records of the
 // chromosome, BAM records) is refused with exit code 1: the reference's answer for it depends on its scan pointer, and this library has no host pileup to reproduce it.
 // The reference's VcfReader (Isas.SequencingFiles) is not part of the reference tree: records are parsed by the VCF specification.
@@ -131,100 +131,39 @@ int main(int argc, char** argv) {
 
     // ---- the pileup
     printf("Looping over bam records from %s\nJump to refid %d %s\n", bamPath.c_str(), refId, chrom.c_str());
-    double tInflate = 0, tDevice = 0; const double tLoop0 = Phases::now();
-    long long overall = 0, chunks = 0, bytesUp = 0; double kernelMs = 0;
+    const double tLoop0 = Phases::now();
+    BamChunkLoop loop; loop.tool = "CanvasSNV"; loop.bam = bamPath; loop.voff = voff; loop.profile = "snv_count"; loop.chunk_bytes_from("CANVAS_SNV_CHUNK_BYTES");
     canvas_ctx* ctx = nullptr;
     if (anyReads && nsites > 0) {          // (no site: the reference leaves its loop at the first read that passes the filters; no read: nothing to count)
-        MappedFile mf; if (!mf.open(bamPath)) { fprintf(stderr, "CanvasSNV: cannot map %s\n", bamPath.c_str()); return 1; }
-        const uint8_t* F = (const uint8_t*)mf.p; const size_t FN = mf.n;
-        size_t chunkBytes = (size_t)32 << 20;
-        if (const char* e = getenv("CANVAS_SNV_CHUNK_BYTES")) { const long long v = atoll(e); if (v >= 65536) chunkBytes = (size_t)v; }
-        // blocks of the first chunk: sizes the buffers (a small file gets small ones: pinning costs time per megabyte)
-        size_t fileAt = (size_t)(voff >> 16); size_t skip = (size_t)(voff & 0xFFFF);
-        std::vector<BgzfBlock> blocks; bool eof = false;          // (`in` made an offset in the file)
-        auto collect = [&](size_t& total) -> bool {
-            blocks.clear(); total = 0;
-            while (total < chunkBytes) {
-                if (fileAt >= FN) { eof = true; break; }
-                BgzfBlock b; const size_t size = bgzf_parse(F + fileAt, FN - fileAt, b);
-                if (size == 0 || size > FN - fileAt) { fprintf(stderr, "CanvasSNV: %s: truncated or damaged BGZF block at byte %zu\n", bamPath.c_str(), fileAt); return false; }
-                b.in += fileAt; blocks.push_back(b); total += b.isize; fileAt += size;
-            }
-            return true;
-        };
-        size_t total = 0; if (!collect(total)) return 1;
-        const size_t cap = 2 * std::min(chunkBytes + 65536, std::max<size_t>(total, 65536)) + 2 * 65536, offCap = cap / 36 + 16;
-        if (!(ctx = actx.require("CanvasSNV"))) return 1;
-        const bool timing = getenv("CANVAS_TOOL_TIMING") != nullptr;
-        if (timing) (void)canvas_profile_enable(ctx, 1);
-        std::unique_ptr<uint8_t[]> hRec[2] = {std::unique_ptr<uint8_t[]>(new uint8_t[cap]), std::unique_ptr<uint8_t[]>(new uint8_t[cap])};
-        std::unique_ptr<uint64_t[]> hOff[2] = {std::unique_ptr<uint64_t[]>(new uint64_t[offCap]), std::unique_ptr<uint64_t[]>(new uint64_t[offCap])};
-        for (int i = 0; i < 2; i++) { TOOL_TRY(ctx, canvas_host_register(ctx, hRec[i].get(), (int64_t)cap)); TOOL_TRY(ctx, canvas_host_register(ctx, hOff[i].get(), (int64_t)(offCap * 8))); }
-        Dev dRec0(ctx, (int64_t)cap), dRec1(ctx, (int64_t)cap), dOff0(ctx, (int64_t)(offCap * 8)), dOff1(ctx, (int64_t)(offCap * 8));
-        Dev dPos(ctx, ((int64_t)nsites + 1) * 4), dRef(ctx, nsites + 1), dAlt(ctx, nsites + 1), dCr(ctx, ((int64_t)nsites + 1) * 4), dCa(ctx, ((int64_t)nsites + 1) * 4);
-        if (!dRec0.p || !dRec1.p || !dOff0.p || !dOff1.p || !dPos.p || !dRef.p || !dAlt.p || !dCr.p || !dCa.p) { fprintf(stderr, "CanvasSNV: device allocation failed: %s\n", canvas_last_error(ctx)); return 1; }
-        void* dRec[2] = {dRec0.p, dRec1.p}; void* dOff[2] = {dOff0.p, dOff1.p};
-        TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dPos.p, sitePos.data(), (int64_t)nsites * 4)); TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dRef.p, siteRef.data(), nsites)); TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dAlt.p, siteAlt.data(), nsites));
-        TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dCr.p, cntRef.data(), (int64_t)nsites * 4)); TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dCa.p, cntAlt.data(), (int64_t)nsites * 4));
-        tDevice += Phases::now() - tLoop0;
-
-        size_t carry = 0; int cur = 0; bool done = false; int32_t lastPos = -1; std::vector<size_t> pre;
-        for (;;) {
-            const double t0 = Phases::now();
-            uint8_t* buf = hRec[cur].get(); uint64_t* offs = hOff[cur].get();
-            if (carry + total > cap) { fprintf(stderr, "CanvasSNV: %s: an alignment record larger than %zu bytes\n", bamPath.c_str(), cap / 2); return 1; }
-            pre.assign(blocks.size() + 1, carry);
-            for (size_t i = 0; i < blocks.size(); i++) pre[i + 1] = pre[i] + blocks[i].isize;
-            std::atomic<bool> ok(true);
-            parallel_for((int64_t)blocks.size(), [&](int64_t i) {
-                const BgzfBlock& b = blocks[(size_t)i];
-                if (b.isize && !inflate_raw(F + b.in, b.clen, buf + pre[(size_t)i], b.isize)) ok = false;
-            });
-            if (!ok) { fprintf(stderr, "CanvasSNV: %s: a BGZF block does not inflate to its recorded size\n", bamPath.c_str()); return 1; }
-            const size_t len = carry + total;
-            // the block_size chain: one offset per record of the wanted reference; the shape of every record is checked here (the kernel checks it again)
-            size_t at = skip; skip = 0; int64_t nrec = 0;
-            if (at > len) { fprintf(stderr, "CanvasSNV: %s.bai points behind the end of a block\n", bamPath.c_str()); return 1; }
-            while (at + 4 <= len) {
-                const int32_t bs = (int32_t)le32(buf + at);
-                if (bs >= 32 && (size_t)bs > len - at - 4) break;                            // completed by the next chunk
-                const uint8_t* r = buf + at + 4; BamFixed fx;
-                if (!fx.decode(r, bs)) { fprintf(stderr, "CanvasSNV: %s: malformed alignment record (block_size %d)\n", bamPath.c_str(), bs); return 1; }
+        std::unique_ptr<Dev> dPos, dRef, dAlt, dCr, dCa;
+        int32_t lastPos = -1;
+        const int rc = loop.run(actx, ctx, tLoop0,
+            [&](canvas_ctx* c) -> int {
+                dPos.reset(new Dev(c, ((int64_t)nsites + 1) * 4)); dRef.reset(new Dev(c, nsites + 1)); dAlt.reset(new Dev(c, nsites + 1));
+                dCr.reset(new Dev(c, ((int64_t)nsites + 1) * 4)); dCa.reset(new Dev(c, ((int64_t)nsites + 1) * 4));
+                if (!dPos->p || !dRef->p || !dAlt->p || !dCr->p || !dCa->p) { fprintf(stderr, "CanvasSNV: device allocation failed: %s\n", canvas_last_error(c)); return 1; }
+                TOOL_TRY(c, canvas_memcpy_h2d(c, dPos->p, sitePos.data(), (int64_t)nsites * 4)); TOOL_TRY(c, canvas_memcpy_h2d(c, dRef->p, siteRef.data(), nsites)); TOOL_TRY(c, canvas_memcpy_h2d(c, dAlt->p, siteAlt.data(), nsites));
+                TOOL_TRY(c, canvas_memcpy_h2d(c, dCr->p, cntRef.data(), (int64_t)nsites * 4)); TOOL_TRY(c, canvas_memcpy_h2d(c, dCa->p, cntAlt.data(), (int64_t)nsites * 4));
+                return 0;
+            },
+            [&](const uint8_t* r, const BamFixed& fx, int32_t bs) -> BamFrame {
                 const int32_t rid = fx.refID, pos = fx.pos, lseq = fx.l_seq; const uint32_t lname = fx.l_read_name, ncig = fx.n_cigar;
-                if (lseq < 0 || 32ull + lname + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > (uint64_t)bs) { fprintf(stderr, "CanvasSNV: %s: malformed alignment record at position %d (its name, CIGAR and bases do not fit its block_size)\n", bamPath.c_str(), pos); return 1; }
-                if (rid < 0 || pos < 0 || rid > refId) { done = true; break; }               // past the chromosome of interest
-                if (rid == refId) {
-                    if (pos < lastPos) { fprintf(stderr, "CanvasSNV (MI355X): %s is not sorted by position: read '%.*s' at %s:%d follows position %d (unsorted input is refused)\n", bamPath.c_str(), (int)(lname ? lname - 1 : 0), (const char*)(r + 32), chrom.c_str(), pos + 1, lastPos + 1); return 1; }
-                    lastPos = pos; offs[nrec++] = (uint64_t)at;
-                }
-                at += 4 + (size_t)bs;
-            }
-            const size_t used = at;
-            if (!done && eof && at < len) { fprintf(stderr, "CanvasSNV: %s: the file ends inside an alignment record (truncated)\n", bamPath.c_str()); return 1; }
-            carry = done ? 0 : len - at;
-            const double t1 = Phases::now(); tInflate += t1 - t0;
-            TOOL_TRY(ctx, canvas_synchronize(ctx));                            // chunk k - 1 ran while this one was inflated
-            if (carry) memcpy(hRec[cur ^ 1].get(), buf + at, carry);          // only now: the other buffer was the source of chunk k - 1's upload until the wait above
-            if (nrec > 0) {
-                TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dRec[cur], buf, (int64_t)used)); TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dOff[cur], offs, nrec * 8));
-                TOOL_TRY(ctx, canvas_snv_count(ctx, (const uint8_t*)dRec[cur], (uint64_t)used, (const uint64_t*)dOff[cur], nrec, refId, minMapQ, 20, dPos.as<int32_t>(), dRef.as<uint8_t>(), dAlt.as<uint8_t>(),
-                                               nsites, dCr.as<int32_t>(), dCa.as<int32_t>(), nullptr));
-                overall += nrec; chunks++; bytesUp += (long long)used;
-            }
-            tDevice += Phases::now() - t1;
-            if (done || eof) break;
-            cur ^= 1;
-            const double t2 = Phases::now();
-            if (!collect(total)) return 1;
-            tInflate += Phases::now() - t2;
-        }
+                if (lseq < 0 || 32ull + lname + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > (uint64_t)bs) { fprintf(stderr, "CanvasSNV: %s: malformed alignment record at position %d (its name, CIGAR and bases do not fit its block_size)\n", bamPath.c_str(), pos); return BamFrame::Fail; }
+                if (rid < 0 || pos < 0 || rid > refId) return BamFrame::Stop;                 // past the chromosome of interest
+                if (rid != refId) return BamFrame::Skip;
+                if (pos < lastPos) { fprintf(stderr, "CanvasSNV (MI355X): %s is not sorted by position: read '%.*s' at %s:%d follows position %d (unsorted input is refused)\n", bamPath.c_str(), (int)(lname ? lname - 1 : 0), (const char*)(r + 32), chrom.c_str(), pos + 1, lastPos + 1); return BamFrame::Fail; }
+                lastPos = pos; return BamFrame::Take;
+            },
+            [&](void* dRec, uint64_t used, void* dOff, int64_t nrec) -> int32_t {
+                return canvas_snv_count(ctx, (const uint8_t*)dRec, used, (const uint64_t*)dOff, nrec, refId, minMapQ, 20, dPos->as<int32_t>(), dRef->as<uint8_t>(), dAlt->as<uint8_t>(),
+                                        nsites, dCr->as<int32_t>(), dCa->as<int32_t>(), nullptr);
+            });
+        if (rc) return 1;
         const double t3 = Phases::now();
-        TOOL_TRY(ctx, canvas_synchronize(ctx));
-        TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, cntRef.data(), dCr.p, (int64_t)nsites * 4)); TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, cntAlt.data(), dCa.p, (int64_t)nsites * 4));
-        if (timing) { int32_t launches = 0; (void)canvas_profile_get(ctx, "snv_count", &kernelMs, &launches, 1); }
-        for (int i = 0; i < 2; i++) { (void)canvas_host_unregister(ctx, hRec[i].get()); (void)canvas_host_unregister(ctx, hOff[i].get()); }
-        tDevice += Phases::now() - t3;
+        TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, cntRef.data(), dCr->p, (int64_t)nsites * 4)); TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, cntAlt.data(), dCa->p, (int64_t)nsites * 4));
+        loop.tDevice += Phases::now() - t3;
     }
+    const double tInflate = loop.tInflate, tDevice = loop.tDevice, kernelMs = loop.kernelMs; const long long overall = loop.records, chunks = loop.chunks, bytesUp = loop.bytesUp;
     printf("Looped over %lld bam records in all\n", overall);
     // (inflation and the device overlap: `inflate` is the time the main thread spent inflating and framing, `device` the time it spent queueing work and waiting for the
     // device — what of the device's work did not hide behind inflation.  Together they are the loop's wall time.)

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <functional>
 #include <map>
+#include <memory>
 #include <atomic>
 #include <set>
 #include <string>
@@ -273,5 +274,110 @@ static inline int finish(Phases& ph, int rc) {
 struct ExitStamp { const char* what; explicit ExitStamp(const char* w) : what(w) {}
     ~ExitStamp() { if (getenv("CANVAS_TOOL_TIMING") && getenv("CANVAS_TOOL_FULL_TEARDOWN")) fprintf(stderr, "[teardown] %.4f s  %s\n", Phases::now(), what); } };
 #define TOOL_TRY(ctx, expr) do { int32_t rc_ = (expr); if (rc_ != 0) { fprintf(stderr, "%s failed (%d): %s\n", #expr, rc_, canvas_last_error(ctx)); return 1; } } while (0)
+
+// ---- a BAM as chunks of raw record bytes on the device (CanvasSNV's pileup, CanvasBin -c): the chunk format of canvas_snv_count / canvas_hits_from_bam.
+// The file is mapped, the BGZF blocks of a chunk are inflated on the worker threads straight into one of two staging buffers (registered with the runtime), the
+// block_size chain is walked once for the byte offset of every record the tool takes, a record the chunk ends inside is carried over to the next one, and the chunk is
+// uploaded asynchronously: chunk k + 1 is inflated while chunk k is uploaded and consumed.  What the tools differ in comes as three callables:
+//   setup(ctx)                        once, when the staging buffers exist and before the first chunk is framed (the tool's own device arrays); 0 or the exit code
+//   frame(r, fx, block_size)          one record: r = its 32 fixed bytes (the whole record lies behind them), fx = the same decoded (block_size >= 32 is checked)
+//   consume(dRec, used, dOff, nrec)   queue the device work of a chunk of nrec taken records (nrec > 0); the library's return code
+enum class BamFrame { Take, Skip, TakeAndStop, Stop, Fail };      // TakeAndStop / Stop: nothing behind this record is read; Fail: the tool has said why (unless quiet)
+struct BamChunkLoop {
+    const char* tool; std::string bam; uint64_t voff = 0; size_t chunkBytes = (size_t)32 << 20;
+    bool quiet = false;               // no message for input the loop itself refuses (the caller has an answer of its own for such a file)
+    const char* profile = nullptr;    // with CANVAS_TOOL_TIMING: the library scope whose device time goes to kernelMs
+    double tInflate = 0, tDevice = 0, kernelMs = 0; long long records = 0, chunks = 0, bytesUp = 0;
+    void chunk_bytes_from(const char* envName) { if (const char* e = getenv(envName)) { const long long v = atoll(e); if (v >= 65536) chunkBytes = (size_t)v; } }
+    // 0: the file was read to its end or to the record that stopped it, everything is queued and waited for.  1: the device or the runtime failed (message printed).
+    // 2: the input was refused (message printed unless quiet, or by frame).  Any other value: what setup returned.
+    template <class Setup, class Frame, class Consume>
+    int run(AsyncCtx& actx, canvas_ctx*& ctx, double tLoop0, Setup setup, Frame frame, Consume consume) {
+        MappedFile mf; if (!mf.open(bam)) { fprintf(stderr, "%s: cannot map %s\n", tool, bam.c_str()); return 1; }
+        const uint8_t* F = (const uint8_t*)mf.p; const size_t FN = mf.n;
+        // blocks of the first chunk: sizes the buffers (a small file gets small ones: pinning costs time per megabyte)
+        size_t fileAt = (size_t)(voff >> 16); size_t skip = (size_t)(voff & 0xFFFF);
+        std::vector<BgzfBlock> blocks; bool eof = false;          // (`in` made an offset in the file)
+        auto collect = [&](size_t& total) -> bool {
+            blocks.clear(); total = 0;
+            while (total < chunkBytes) {
+                if (fileAt >= FN) { eof = true; break; }
+                BgzfBlock b; const size_t size = bgzf_parse(F + fileAt, FN - fileAt, b);
+                if (size == 0 || size > FN - fileAt) { if (!quiet) fprintf(stderr, "%s: %s: truncated or damaged BGZF block at byte %zu\n", tool, bam.c_str(), fileAt); return false; }
+                b.in += fileAt; blocks.push_back(b); total += b.isize; fileAt += size;
+            }
+            return true;
+        };
+        size_t total = 0; if (!collect(total)) return 2;
+        const size_t cap = 2 * std::min(chunkBytes + 65536, std::max<size_t>(total, 65536)) + 2 * 65536, offCap = cap / 36 + 16;
+        if (!(ctx = actx.require(tool))) return 1;
+        const bool timing = getenv("CANVAS_TOOL_TIMING") != nullptr;
+        if (timing && profile) (void)canvas_profile_enable(ctx, 1);
+        std::unique_ptr<uint8_t[]> hRec[2] = {std::unique_ptr<uint8_t[]>(new uint8_t[cap]), std::unique_ptr<uint8_t[]>(new uint8_t[cap])};
+        std::unique_ptr<uint64_t[]> hOff[2] = {std::unique_ptr<uint64_t[]>(new uint64_t[offCap]), std::unique_ptr<uint64_t[]>(new uint64_t[offCap])};
+        struct Registered { canvas_ctx* c; std::vector<void*> v; ~Registered() { for (void* p : v) (void)canvas_host_unregister(c, p); } } reg{ctx, {}};
+        for (int i = 0; i < 2; i++) { TOOL_TRY(ctx, canvas_host_register(ctx, hRec[i].get(), (int64_t)cap)); reg.v.push_back(hRec[i].get());
+                                      TOOL_TRY(ctx, canvas_host_register(ctx, hOff[i].get(), (int64_t)(offCap * 8))); reg.v.push_back(hOff[i].get()); }
+        Dev dRec0(ctx, (int64_t)cap), dRec1(ctx, (int64_t)cap), dOff0(ctx, (int64_t)(offCap * 8)), dOff1(ctx, (int64_t)(offCap * 8));
+        if (!dRec0.p || !dRec1.p || !dOff0.p || !dOff1.p) { fprintf(stderr, "%s: device allocation failed: %s\n", tool, canvas_last_error(ctx)); return 1; }
+        void* dRec[2] = {dRec0.p, dRec1.p}; void* dOff[2] = {dOff0.p, dOff1.p};
+        if (int rc = setup(ctx)) return rc;
+        tDevice += Phases::now() - tLoop0;
+
+        size_t carry = 0; int cur = 0; bool done = false; std::vector<size_t> pre;
+        for (;;) {
+            const double t0 = Phases::now();
+            uint8_t* buf = hRec[cur].get(); uint64_t* offs = hOff[cur].get();
+            if (carry + total > cap) { if (!quiet) fprintf(stderr, "%s: %s: an alignment record larger than %zu bytes\n", tool, bam.c_str(), cap / 2); (void)canvas_synchronize(ctx); return 2; }
+            pre.assign(blocks.size() + 1, carry);
+            for (size_t i = 0; i < blocks.size(); i++) pre[i + 1] = pre[i] + blocks[i].isize;
+            std::atomic<bool> ok(true);
+            parallel_for((int64_t)blocks.size(), [&](int64_t i) {
+                const BgzfBlock& b = blocks[(size_t)i];
+                if (b.isize && !inflate_raw(F + b.in, b.clen, buf + pre[(size_t)i], b.isize)) ok = false;
+            });
+            const size_t len = carry + total;
+            // the block_size chain: one offset per record the tool takes; the shape of every record is checked here (the kernels check it again)
+            size_t at = skip; skip = 0; int64_t nrec = 0; bool failed = false;
+            if (at > len) { if (!quiet) fprintf(stderr, "%s: %s.bai points behind the end of a block\n", tool, bam.c_str()); (void)canvas_synchronize(ctx); return 2; }
+            if (ok) while (at + 4 <= len) {
+                const int32_t bs = (int32_t)le32(buf + at);
+                if (bs >= 32 && (size_t)bs > len - at - 4) break;                            // completed by the next chunk
+                const uint8_t* r = buf + at + 4; BamFixed fx;
+                if (!fx.decode(r, bs)) { if (!quiet) fprintf(stderr, "%s: %s: malformed alignment record (block_size %d)\n", tool, bam.c_str(), bs); failed = true; break; }
+                const BamFrame f = frame(r, fx, bs);
+                if (f == BamFrame::Fail) { failed = true; break; }
+                if (f == BamFrame::Stop) { done = true; break; }
+                if (f != BamFrame::Skip) offs[nrec++] = (uint64_t)at;
+                at += 4 + (size_t)bs;
+                if (f == BamFrame::TakeAndStop) { done = true; break; }
+            }
+            if (!ok && !quiet) fprintf(stderr, "%s: %s: a BGZF block does not inflate to its recorded size\n", tool, bam.c_str());
+            if (!ok || failed) { (void)canvas_synchronize(ctx); return 2; }
+            const size_t used = at;
+            if (!done && eof && at < len) { if (!quiet) fprintf(stderr, "%s: %s: the file ends inside an alignment record (truncated)\n", tool, bam.c_str()); (void)canvas_synchronize(ctx); return 2; }
+            carry = done ? 0 : len - at;
+            const double t1 = Phases::now(); tInflate += t1 - t0;
+            TOOL_TRY(ctx, canvas_synchronize(ctx));                            // chunk k - 1 ran while this one was inflated
+            if (carry) memcpy(hRec[cur ^ 1].get(), buf + at, carry);          // only now: the other buffer was the source of chunk k - 1's upload until the wait above
+            if (nrec > 0) {
+                TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dRec[cur], buf, (int64_t)used)); TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dOff[cur], offs, nrec * 8));
+                TOOL_TRY(ctx, consume(dRec[cur], (uint64_t)used, dOff[cur], nrec));
+                records += nrec; chunks++; bytesUp += (long long)used;
+            }
+            tDevice += Phases::now() - t1;
+            if (done || eof) break;
+            cur ^= 1;
+            const double t2 = Phases::now();
+            if (!collect(total)) { (void)canvas_synchronize(ctx); return 2; }
+            tInflate += Phases::now() - t2;
+        }
+        const double t3 = Phases::now();
+        TOOL_TRY(ctx, canvas_synchronize(ctx));
+        if (timing && profile) { int32_t launches = 0; (void)canvas_profile_get(ctx, profile, &kernelMs, &launches, 1); }
+        tDevice += Phases::now() - t3;
+        return 0;
+    }
+};
 
 }  // namespace tool

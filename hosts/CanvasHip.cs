@@ -126,6 +126,9 @@ namespace CanvasHipInterop
         // CanvasSNV: allele counts at the variant sites from chunks of raw BAM record bytes (SNVReviewer.ProcessBamFile + ProcessReadBases); info = long[5] or null (queue only)
         [DllImport(Lib)] public static extern int canvas_snv_count(IntPtr ctx, IntPtr dRecords, ulong nbytes, IntPtr dRecordOffsets, long nrecords, int refId, int minMapQ, int minBaseQ,
             IntPtr dSitePos, IntPtr dSiteRef, IntPtr dSiteAlt, int nsites, IntPtr dRefCounts, IntPtr dAltCounts, long[] info);
+        // CanvasBin: observed-alignment arrays (byte hits, short fragment lengths for mode 5 or IntPtr.Zero) from the same chunks; dState = 8 zeroed longs on the device, info = long[8] or null (queue only)
+        [DllImport(Lib)] public static extern int canvas_hits_from_bam(IntPtr ctx, IntPtr dRecords, ulong nbytes, IntPtr dRecordOffsets, long nrecords, int refId, int pairedEnd, int mode,
+            long len, IntPtr dHits, IntPtr dFrag, IntPtr dState, long[] info);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d_async(IntPtr ctx, IntPtr dDst, IntPtr hSrc, long bytes);
         // Tools/FlagUniqueKmers (KmerChecker): unique-35-mer masks of all contigs at once (stats = long[8] or null), and the letter case of kmer.fa from a mask
         [DllImport(Lib)] public static extern int canvas_flag_unique_kmers(IntPtr ctx, int nchr, IntPtr[] dBases, long[] len, IntPtr[] dMask, long maxTableBytes, long[] stats);

@@ -600,6 +600,29 @@ int32_t canvas_snv_count(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nby
                          int32_t min_mapq, int32_t min_base_q, const int32_t* d_site_pos, const uint8_t* d_site_ref, const uint8_t* d_site_alt, int32_t nsites,
                          int32_t* d_ref_counts, int32_t* d_alt_counts, int64_t* h_info);
 
+/* ---- CanvasBin: observed-alignment arrays from BAM records (LoadObservedAlignmentsBAM, CanvasBin/CanvasBin.cs:207-275) ------------------------------ */
+/* One chunk of alignments as RAW BAM record bytes plus the byte offset of every record: the chunk format of canvas_snv_count, no field decoded on the host.
+ * A chromosome is any number of chunks, in file order, starting anywhere at or before its first record.  d_hits (uint8 per base) and d_frag (int16 per base,
+ * mode 5 only, NULL otherwise) are UPDATED and never cleared: the caller zeroes them, and zeroes d_state (8 words) before the first chunk of a chromosome.
+ *   per record  in file order (CanvasBin.cs:235-272): counted as seen; skipped on flag 0x4 / 0x200 / 0x400 / 0x10 / 0x900, on n_cigar == 0, on a first CIGAR
+ *               operation that is not M or is shorter than 35, and with paired_end on a missing 0x2; a record that passed all of these and has refID != ref_id
+ *               STOPS the chromosome: it is seen, and nothing behind it counts or writes, in this chunk or a later one (a skipped record of another reference
+ *               does not stop); otherwise the record is kept.  A kept record with pos outside [0, len) is counted and writes nothing (the reference throws).
+ *   writes      mode 0 (Binary): hits[pos] = 1.  Modes 3 and 5: hits[pos] = min(255, hits[pos] + 1) (an atomic update of the aligned 32-bit word that holds
+ *               the byte: nothing else may write the up to three bytes in front of d_hits[0] or behind d_hits[len - 1] in that word while a call runs).
+ *               Mode 5 (GCContentWeighted) also frag[pos] = clamp(tlen, 0, 32767) of the LAST kept record of the position in file order.
+ *   order       hits is right for records in ANY order (a saturating count does not depend on it).  frag requires the positions of the kept records to be
+ *               non-decreasing within and across the chunks of a chromosome (the caller's to check: any indexed BAM is).
+ *   malformed   an offset that does not leave 4 + 32 bytes inside nbytes, a block_size below 32 or past the chunk, a record whose 32 + l_read_name + 4 n_cigar
+ *               exceeds block_size: skipped whole, counted, never read past its bounds (as in canvas_snv_count).
+ *   d_state     device memory, accumulated over the chunks, written by the kernels only: [0] stopped (0 / 1), [1] records seen (up to and including the stopping
+ *               one), [2] kept, [3] kept but out of range, [4] malformed, [5] position of the last kept record, [6] [7] reserved (the library's own).
+ *   h_info      NULL: the call only queues work on the context's stream (arrays and state complete after canvas_synchronize).  Otherwise int64[8]: the call
+ *               waits and copies d_state out.
+ * CANVAS_ERR_INVALID: NULL context or buffers, mode not 0 / 3 / 5, mode 5 without d_frag, len outside [0, 2^31). */
+int32_t canvas_hits_from_bam(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nbytes, const uint64_t* d_record_offsets, int64_t nrecords, int32_t ref_id,
+                             int32_t paired_end, int32_t mode, int64_t len, uint8_t* d_hits, int16_t* d_frag, int64_t* d_state, int64_t* h_info);
+
 /* ---- reference preparation: Tools/FlagUniqueKmers ---------------------------------------------------------------------- */
 /* Tools/FlagUniqueKmers (KmerChecker.cs): d_mask[c] (ceil(len/64) words, BitArray layout, bits >= len written 0) gets bit p = 1 iff position p of
  * chromosome c starts a 35-mer whose canonical key occurs once in the whole input.  d_bases: ASCII, any case, not modified.
