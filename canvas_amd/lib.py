@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "canvas_somatic_model_fit", "canvas_call_somatic",
     "canvas_segment_tables", "canvas_call_diploid_ids",
     "canvas_partition_states_cbs", "canvas_partition_states_breakpoints", "canvas_reference_copy_numbers", "canvas_call_somatic_ids",
-    "canvas_hits_from_bam",
+    "canvas_hits_from_bam", "canvas_fragments_from_bam",
 ]
 
 
@@ -742,6 +742,49 @@ class Canvas:
                                                   C.c_void_p(frag.data_ptr()) if frag is not None else None, C.c_void_p(state.data_ptr()),
                                                   _np_ptr(info) if want_info else None))
         return hits, frag, state, info
+
+    def fragments_from_bam(self, records, offsets, ref_id, bin_start, bin_stop, quality_threshold=3, counts=None, carry=None, state=None, nbytes=None, carry_capacity=None):
+        """FragmentBinner.BinTask (FragmentBinner.cs:186-369) over one chunk of raw BAM records of one chromosome (the chunk format of snv_count); bin_start / bin_stop
+        (int32) are the chromosome's BED bins in file order.  counts (int32 per bin), carry (uint8, the library's list of open read names) and state (int64[16]) are
+        updated; zeroed counts / state and a carry of carry_capacity bytes (default 1 MiB) are created when None — pass the returned ones to the next chunk.  A carry
+        that is too small is replaced by a larger one with the old contents and the call is repeated once.  Returns (counts, carry, state, info[16]: stopped, seen,
+        paired, usable, malformed, last position, unsorted, carried entries, carry bytes, groups split by a byte comparison, longest group, ...)."""
+        torch = self.torch
+        nbins = int(bin_start.numel())
+        created = counts is None or state is None or carry is None
+        if counts is None:
+            counts = torch.zeros(max(nbins, 1), dtype=torch.int32, device=self.device)
+        if state is None:
+            state = torch.zeros(16, dtype=torch.int64, device=self.device)
+        if carry is None:
+            carry = torch.zeros(max(int(carry_capacity) if carry_capacity is not None else 1 << 20, 8), dtype=torch.uint8, device=self.device)
+        if created:                  # torch zeroes on its own stream; the kernels update the arrays on the context's
+            torch.cuda.current_stream(self.device).synchronize()
+        assert records.dtype == torch.uint8 and offsets.dtype == torch.int64 and bin_start.dtype == torch.int32 and bin_stop.dtype == torch.int32
+        assert counts.dtype == torch.int32 and carry.dtype == torch.uint8 and state.dtype == torch.int64
+        assert bin_stop.numel() == nbins and counts.numel() >= nbins and state.numel() >= 16
+        for t in (records, offsets, bin_start, bin_stop, counts, carry, state):      # the kernels read and write dense arrays on this context's device
+            assert t.is_contiguous() and t.dim() == 1 and (t.numel() == 0 or t.device == self.device), "fragments_from_bam: tensors must be dense, one-dimensional and on the context's device"
+        nb = int(records.numel()) if nbytes is None else int(nbytes)
+        assert 0 <= nb <= records.numel()
+        cap = int(carry.numel()) if carry_capacity is None else int(carry_capacity)
+        assert 0 <= cap <= carry.numel()
+        info = np.zeros(16, np.int64)
+
+        def call(carry, cap):
+            return self.lib.canvas_fragments_from_bam(self.ctx, C.c_void_p(records.data_ptr()), C.c_uint64(nb), C.c_void_p(offsets.data_ptr()), C.c_int64(int(offsets.numel())),
+                                                      C.c_int32(int(ref_id)), C.c_void_p(bin_start.data_ptr()), C.c_void_p(bin_stop.data_ptr()), C.c_int64(nbins),
+                                                      C.c_int32(int(quality_threshold)), C.c_void_p(counts.data_ptr()), C.c_void_p(carry.data_ptr()), C.c_uint64(cap),
+                                                      C.c_void_p(state.data_ptr()), _np_ptr(info))
+        rc = call(carry, cap)
+        if rc == -4:                 # CANVAS_ERR_CAPACITY: info[8] bytes are needed
+            grown = torch.zeros(max(int(info[8]), 2 * int(carry.numel())), dtype=torch.uint8, device=self.device)
+            grown[:carry.numel()] = carry
+            torch.cuda.current_stream(self.device).synchronize()
+            carry, cap = grown, int(grown.numel())
+            rc = call(carry, cap)
+        self._check(rc)
+        return counts, carry, state, info
 
     # ---- reference preparation (Tools/FlagUniqueKmers)
     def flag_unique_kmers(self, bases, lens, masks=None, max_table_bytes=0):

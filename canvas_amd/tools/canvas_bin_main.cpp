@@ -10,9 +10,10 @@
 // BAM flag semantics follow the SAM specification; Isas.SequencingFiles.BamReader is not part of /root/reference (parity unpinned):
 // IsMainAlignment := neither secondary (0x100) nor supplementary (0x800).
 //   CanvasBin -b S.bam -r kmer.fa -i ... -n bins.bed -o S.binned -d 100 [-m 0|3|5]                     predefined bins (canvas_bin_predefined)
-//   CanvasBin -b S.bam -r genome.fa -n bins.bed -o S.binned -m Fragment -p                              FragmentBinner.Bin (FragmentBinner.cs:26-80): host code
-// Fragment mode is a sequential dictionary algorithm over the BAM stream keyed by read name (the mate confirms or undoes what the first read of the pair did): its cost is
-// BGZF inflation and string hashing, there is no data-parallel part, so it runs on the host exactly as in the reference.
+//   CanvasBin -b S.bam -r genome.fa -n bins.bed -o S.binned -m Fragment -p                              FragmentBinner.Bin (FragmentBinner.cs:26-80)
+// Fragment mode reads like a sequential dictionary algorithm over the BAM stream keyed by read name (the mate confirms or undoes what the first read of the pair did), but
+// reads of different names only meet in integer sums and in a forward pointer that depends on the fragment alone: per chromosome the BAM travels as chunks of raw record
+// bytes to canvas_fragments_from_bam (frag.hip; bin_fragments_device below), and bin_fragments — the reference's loop on the host — answers for input the device path hands back.
 // Not built (exit code 1 with a message): -t manifest (the Nextera manifest parser lives in Isas.Manifests, outside /root/reference).  -j behaves as in this version of the
 // reference: the json file must exist and is never read, nothing is binned or written (CanvasBin.cs:936-944), exit code 0; with -i it is the reference's ArgumentException.
 #include "tool_common.hpp"
@@ -224,6 +225,65 @@ static int bin_fragments(const std::string& bam, const std::string& chrom, std::
     return 0;
 }
 
+// The same loop on the device: the chromosome's bins are uploaded once, the BAM travels as chunks of raw record bytes (BamChunkLoop) and every chunk is one
+// canvas_fragments_from_bam call (the call waits: it has to know the size of the carried names before it commits; the carry is enlarged when it says so); counts and
+// state are read once, behind the last chunk.  The host frames the records and looks at refID only, to know where it may stop reading.
+// 0: done.  1: the device or the runtime failed, or the reference's "No paired alignments".  2: not done, nothing printed — bin_fragments has to answer: a file the framing
+// rejects, a chromosome that is not sorted (state[6]) or holds a record the kernels call malformed (state[4]) gets bin_fragments' message and exit code.
+static int bin_fragments_device(const std::string& bam, const std::string& chrom, const BamAt& b, std::vector<PreBin>& bins, long& usableFragmentCount, AsyncCtx& actx, canvas_ctx*& ctx) {
+    const double tLoop0 = Phases::now();
+    BamChunkLoop loop; loop.tool = "CanvasBin"; loop.bam = bam; loop.voff = b.voff; loop.quiet = true; loop.profile = "fragments_from_bam"; loop.chunk_bytes_from("CANVAS_BIN_CHUNK_BYTES");
+    const int desired = b.ref; const int64_t nbins = (int64_t)bins.size();
+    std::unique_ptr<Dev> dState, dStart, dStop, dCount, dCarry; uint64_t carryCap = (uint64_t)1 << 20;
+    long long maxCarried = 0, sumCarried = 0, longest = 0, grown = 0;
+    const int rc = loop.run(actx, ctx, tLoop0,
+        [&](canvas_ctx* c) -> int {
+            dState.reset(new Dev(c, 128)); dStart.reset(new Dev(c, nbins * 4)); dStop.reset(new Dev(c, nbins * 4)); dCount.reset(new Dev(c, nbins * 4)); dCarry.reset(new Dev(c, (int64_t)carryCap));
+            if (!dState->p || !dStart->p || !dStop->p || !dCount->p || !dCarry->p) { fprintf(stderr, "CanvasBin: device allocation failed: %s\n", canvas_last_error(c)); return 1; }
+            std::vector<int32_t> hs((size_t)nbins), he((size_t)nbins), zero((size_t)nbins, 0);
+            for (int64_t i = 0; i < nbins; i++) { hs[(size_t)i] = bins[(size_t)i].start; he[(size_t)i] = bins[(size_t)i].stop; }
+            const int64_t zstate[16] = {0};
+            TOOL_TRY(c, canvas_memcpy_h2d(c, dState->p, zstate, 128));
+            if (nbins > 0) { TOOL_TRY(c, canvas_memcpy_h2d(c, dStart->p, hs.data(), nbins * 4)); TOOL_TRY(c, canvas_memcpy_h2d(c, dStop->p, he.data(), nbins * 4)); TOOL_TRY(c, canvas_memcpy_h2d(c, dCount->p, zero.data(), nbins * 4)); }
+            return 0;
+        },
+        [&](const uint8_t*, const BamFixed& a, int32_t bs) -> BamFrame {
+            if (32 + (int64_t)a.l_read_name + 4 * (int64_t)a.n_cigar > bs) return BamFrame::Fail;          // read_bam_record's check
+            return a.refID != desired ? BamFrame::TakeAndStop : BamFrame::Take;                            // (:221: every record of another reference ends the chromosome)
+        },
+        [&](void* dRec, uint64_t used, void* dOff, int64_t nrec) -> int32_t {
+            int64_t info[16];
+            for (int attempt = 0;; attempt++) {
+                const int32_t r = canvas_fragments_from_bam(ctx, (const uint8_t*)dRec, used, (const uint64_t*)dOff, nrec, desired, dStart->as<int32_t>(), dStop->as<int32_t>(), nbins, 3,
+                                                            dCount->as<int32_t>(), dCarry->as<uint8_t>(), carryCap, dState->as<int64_t>(), info);
+                if (r != CANVAS_ERR_CAPACITY || attempt > 0) { if (r) return r; break; }
+                // the carried names do not fit: a larger buffer with the old contents, and the same chunk again
+                const uint64_t want = std::max<uint64_t>((uint64_t)info[8], 2 * carryCap);
+                std::unique_ptr<Dev> bigger(new Dev(ctx, (int64_t)want)); if (!bigger->p) return CANVAS_ERR_HIP;
+                std::vector<uint8_t> old((size_t)carryCap);
+                int32_t rr = canvas_memcpy_d2h(ctx, old.data(), dCarry->p, (int64_t)carryCap); if (rr) return rr;
+                rr = canvas_memcpy_h2d(ctx, bigger->p, old.data(), (int64_t)carryCap); if (rr) return rr;
+                dCarry.swap(bigger); carryCap = want; grown++;
+            }
+            maxCarried = std::max<long long>(maxCarried, info[7]); sumCarried += info[7]; longest = std::max<long long>(longest, info[10]);
+            return 0;
+        });
+    if (rc == 1) return 1;
+    int64_t st[16] = {0};
+    std::vector<int32_t> counts((size_t)nbins, 0);
+    if (rc == 0) { TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, st, dState->p, 128)); if (nbins > 0) TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, counts.data(), dCount->p, nbins * 4)); }
+    const bool handBack = rc != 0 || st[4] != 0 || st[6] != 0;
+    if (getenv("CANVAS_TOOL_TIMING")) fprintf(stderr, "[frag] {\"chrom\": \"%s\", \"records\": %lld, \"chunks\": %lld, \"record_bytes\": %lld, \"kernel_ms\": %.4f, \"inflate_s\": %.4f, \"device_wait_s\": %.4f, \"threads\": %d, "
+                                              "\"carried_max\": %lld, \"carried_mean\": %.1f, \"longest_group\": %lld, \"carry_grown\": %lld, \"host_path\": %d}\n",
+                                              chrom.c_str(), loop.records, loop.chunks, loop.bytesUp, loop.kernelMs, loop.tInflate, loop.tDevice, io_threads(), maxCarried,
+                                              loop.chunks ? (double)sumCarried / (double)loop.chunks : 0.0, longest, grown, handBack ? 1 : 0);
+    if (handBack) return 2;
+    for (int64_t i = 0; i < nbins; i++) bins[(size_t)i].count = (float)counts[(size_t)i];
+    usableFragmentCount = (long)st[3];
+    if (st[2] == 0) { fprintf(stderr, "No paired alignments found for %s in %s\n", chrom.c_str(), bam.c_str()); return 1; }
+    return 0;
+}
+
 static int parse_mode(const std::string& m) {       // Utilities.ParseCanvasCoverageMode (CanvasCommon/Utilities.cs:56-74)
     std::string s; for (char c : m) if (c != ' ' && c != '\t') s.push_back((char)tolower(c));
     if (s == "0" || s == "binary") return CANVAS_MODE_BINARY;
@@ -276,6 +336,12 @@ int main(int argc, char** argv) {
         BamHeader bh; { Bgzf z; if (!z.open(bam) || !read_bam_header(z, bh)) { fprintf(stderr, "CanvasBin: %s is not a BAM file\n", bam.c_str()); return 1; } }
         for (auto& kv : predefined) if (std::find(bh.refNames.begin(), bh.refNames.end(), kv.first) == bh.refNames.end()) {
             fprintf(stderr, "Not all chromosomes in %s are found in %s.\n", a.get("bins").c_str(), bam.c_str()); return 1; }
+        // the counts are made on the device (bin_fragments_device) unless the test hook CANVAS_TOOL_HOST_BAM asks for the host loop or there is no usable GPU (quietly: this
+        // mode has a host loop that answers); the context comes up while the header and the bins are read
+        const bool hostBam = getenv("CANVAS_TEST_HOOKS") && getenv("CANVAS_TOOL_HOST_BAM");
+        std::unique_ptr<AsyncCtx> actx; if (!hostBam) actx.reset(new AsyncCtx());
+        struct CtxGuard { std::unique_ptr<AsyncCtx>& a; ~CtxGuard() { if (a) if (canvas_ctx* c = a->get()) canvas_destroy(c); } } guard{actx};
+        canvas_ctx* ctx = nullptr;
         long usable = 0;
         for (auto& chromName : bh.refNames) {
             auto it = predefined.find(chromName); if (it == predefined.end()) continue;
@@ -287,13 +353,24 @@ int main(int argc, char** argv) {
                 for (auto& b : it->second) { double nt = 0, gcn = 0; for (int p = b.start; p < b.stop && p < (int)nbases; p++) { if (bases[p] == 'n') continue; nt++; const char ch = bases[p]; if (ch == 'C' || ch == 'c' || ch == 'G' || ch == 'g') gcn++; }
                     b.gc = nt > 0 ? (int)(100 * gcn / nt) : 0; }
             }
-            long u = 0; if (int rc = bin_fragments(bam, chromName, it->second, u)) return rc;
+            long u = 0; bool onDevice = false;
+            if (actx && actx->get()) {
+                BamAt b; if (int rc = open_bam_at(bam, chromName, b)) return rc;
+                if (b.any) {                                                          // (no reads for this chromosome: bin_fragments says what that means)
+                    const int rc = bin_fragments_device(bam, chromName, b, it->second, u, *actx, ctx);
+                    if (rc == 1) return 1;
+                    onDevice = rc == 0;
+                }
+            }
+            if (!onDevice) { if (int rc = bin_fragments(bam, chromName, it->second, u)) return rc; }
             usable += u;
         }
+        ph.mark("fragments");
         if (usable == 0) { fprintf(stderr, "No passing-filter fragments overlapping bins are found in %s\n", bam.c_str()); return 1; }
         GzWriter wr(out); if (!wr.ok()) { fprintf(stderr, "CanvasBin: cannot write %s\n", out.c_str()); return 1; }
         for (auto& chromName : bh.refNames) { auto it = predefined.find(chromName); if (it == predefined.end()) continue;
             for (auto& b : it->second) wr.line(chromName + "\t" + std::to_string(b.start) + "\t" + std::to_string(b.stop) + "\t" + format_f2(b.count) + "\t" + std::to_string(b.gc)); }
+        ph.mark("write");
         printf("Output complete\n");
         return 0;
     }

@@ -129,6 +129,10 @@ namespace CanvasHipInterop
         // CanvasBin: observed-alignment arrays (byte hits, short fragment lengths for mode 5 or IntPtr.Zero) from the same chunks; dState = 8 zeroed longs on the device, info = long[8] or null (queue only)
         [DllImport(Lib)] public static extern int canvas_hits_from_bam(IntPtr ctx, IntPtr dRecords, ulong nbytes, IntPtr dRecordOffsets, long nrecords, int refId, int pairedEnd, int mode,
             long len, IntPtr dHits, IntPtr dFrag, IntPtr dState, long[] info);
+        // CanvasBin -m Fragment: fragment counts of one chromosome's BED bins from the same chunks; dCount (int per bin) and dState (16 longs) zeroed before the first chunk, dCarry = the
+        // library's own list of open read names (CANVAS_ERR_CAPACITY: info[8] bytes are needed; enlarge it, keep its contents, call again); info = long[16], the call waits
+        [DllImport(Lib)] public static extern int canvas_fragments_from_bam(IntPtr ctx, IntPtr dRecords, ulong nbytes, IntPtr dRecordOffsets, long nrecords, int refId, IntPtr dBinStart,
+            IntPtr dBinStop, long nbins, int qualityThreshold, IntPtr dCount, IntPtr dCarry, ulong carryCapacity, IntPtr dState, long[] info);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d_async(IntPtr ctx, IntPtr dDst, IntPtr hSrc, long bytes);
         // Tools/FlagUniqueKmers (KmerChecker): unique-35-mer masks of all contigs at once (stats = long[8] or null), and the letter case of kmer.fa from a mask
         [DllImport(Lib)] public static extern int canvas_flag_unique_kmers(IntPtr ctx, int nchr, IntPtr[] dBases, long[] len, IntPtr[] dMask, long maxTableBytes, long[] stats);

@@ -623,6 +623,31 @@ int32_t canvas_snv_count(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nby
 int32_t canvas_hits_from_bam(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nbytes, const uint64_t* d_record_offsets, int64_t nrecords, int32_t ref_id,
                              int32_t paired_end, int32_t mode, int64_t len, uint8_t* d_hits, int16_t* d_frag, int64_t* d_state, int64_t* h_info);
 
+/* ---- CanvasBin -m Fragment: fragment counts of predefined bins from BAM records (FragmentBinner.BinTask, CanvasBin/FragmentBinner.cs:186-369) -------- */
+/* One chunk of one chromosome in the chunk format above.  d_bin_start / d_bin_stop: the chromosome's BED bins in FILE order (not assumed sorted or disjoint).
+ * d_count (int32 per bin), d_carry and d_state (16 words) carry over from chunk to chunk; the caller zeroes d_count and d_state before the first chunk.
+ *   stop        the first record with refID != ref_id stops the chromosome (every record counts here, filtered or not): it is seen, nothing behind it has any
+ *               effect, in this chunk or a later one.
+ *   per record  before the stop: counted in `paired` on flag 0x1; checked for sortedness; skipped on 0x4 / 0x8 / 0x100 or unless 0x1 and 0x2 are both set
+ *               (0x800 passes, as in the reference).  The surviving records drive, per READ NAME (the l_read_name - 1 bytes at offset 36, compared as bytes) and in
+ *               file order, BinOneAlignment: bad = flag & 0x600 || mapq == 255 || mapq < quality_threshold.  Name binned: undo the count when bad, forget the name.
+ *               Otherwise done when bad, refID != next_refID or pos > next_pos; pos == next_pos toggles the same-position state and is done when it was set; done when
+ *               tlen == 0; otherwise the fragment [pos, pos + tlen) (32-bit wrap-around) goes to FindBestBin from the first bin whose running maximum of Stop exceeds
+ *               pos: largest overlap, the first bin on ties, the walk ends at the first bin with overlap <= 0.  A hit: count[best]++, usable++, the name is binned.
+ *   carry       after a chunk every name that is binned or in the same-position set is an entry of d_carry (8-byte aligned; layout: the library's own, with the name bytes);
+ *               resolved names leave it.  If the entries do not fit in carry_capacity the call returns CANVAS_ERR_CAPACITY with d_count, d_carry and d_state
+ *               UNCHANGED and h_info[8] = the bytes needed: enlarge the buffer, keep its contents, repeat the call.
+ *   sortedness  a record (before the stop) whose pos is below the previous record's sets d_state[6] to 1 + its ordinal among the records seen; the counts are void
+ *               from then on (the reference throws).
+ *   malformed   as in canvas_hits_from_bam: skipped whole, counted, never read past their bounds.
+ *   d_state     [0] stopped, [1] seen, [2] paired, [3] usable fragments (net), [4] malformed, [5] last position, [6] unsorted, [7] carried entries, [8] carry bytes
+ *               used, [9] groups in which a byte comparison separated names of equal hash, [10] longest group, [11..15] the library's own.
+ *   h_info      int64[16], required: the call always waits (it has to know the carry's size before it commits) and copies d_state out.
+ * CANVAS_ERR_INVALID: NULL context or buffers, ref_id < 0, nbins outside [0, 2^31), quality_threshold < 0. */
+int32_t canvas_fragments_from_bam(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nbytes, const uint64_t* d_record_offsets, int64_t nrecords, int32_t ref_id,
+                                  const int32_t* d_bin_start, const int32_t* d_bin_stop, int64_t nbins, int32_t quality_threshold, int32_t* d_count,
+                                  uint8_t* d_carry, uint64_t carry_capacity, int64_t* d_state, int64_t* h_info);
+
 /* ---- reference preparation: Tools/FlagUniqueKmers ---------------------------------------------------------------------- */
 /* Tools/FlagUniqueKmers (KmerChecker.cs): d_mask[c] (ceil(len/64) words, BitArray layout, bits >= len written 0) gets bit p = 1 iff position p of
  * chromosome c starts a 35-mer whose canonical key occurs once in the whole input.  d_bases: ASCII, any case, not modified.

@@ -1,0 +1,399 @@
+"""Canvas.fragments_from_bam (canvas_amd/csrc/frag.hip) against the sequential restatement of FragmentBinner.cs (tests/fragment_ref.py, (a)): the bin counts and
+state[0..8] are compared exactly.  A workgroup of frag.hip takes 256 items (four waves of 64); carried entries are items in front of the records.
+Where the input is not sorted the reference throws and the counts are void: those cases compare the words that are defined (stopped, seen, paired, malformed, last
+position, unsorted)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import fragment_ref as F
+import hits_ref as H
+from gpu_common import get_canvas, to_dev
+
+pytestmark = pytest.mark.gpu
+WG, WAVE, TAIL = 256, 64, 8
+
+
+@pytest.fixture(scope="module")
+def cv():
+    return get_canvas()
+
+
+def dev_chunk(cv, reads, pad=0, extra_offsets=()):
+    import torch
+    buf, offs, nbytes = H.chunk_of(reads, pad, extra_offsets)
+    d_buf = to_dev(buf, cv.device) if len(buf) else torch.zeros(1, dtype=torch.uint8, device=cv.device)
+    d_off = to_dev(offs, cv.device) if len(offs) else torch.zeros(0, dtype=torch.int64, device=cv.device)
+    return d_buf, d_off, nbytes
+
+
+def dev_bins(cv, bins):
+    import torch
+    if not bins:
+        z = torch.zeros(0, dtype=torch.int32, device=cv.device)
+        return z, z.clone()
+    a = np.array(bins, np.int64)
+    return to_dev(a[:, 0].astype(np.int32), cv.device), to_dev(a[:, 1].astype(np.int32), cv.device)
+
+
+def gpu_run(cv, chunks, bins, q=3, pad=0, extra_offsets=None, carry_capacity=None):
+    """the chunks one after the other through the wrapper; counts is TAIL elements longer than the bins and those must stay as they were -> (counts, info, carry)"""
+    import torch
+    nb = len(bins)
+    counts = torch.full((nb + TAIL,), 7, dtype=torch.int32, device=cv.device)
+    counts[:nb] = 0
+    d_start, d_stop = dev_bins(cv, bins)
+    state = carry = None
+    info = np.zeros(16, np.int64)
+    torch.cuda.synchronize()
+    for k, reads in enumerate(chunks):
+        d_buf, d_off, nbytes = dev_chunk(cv, reads, pad, (extra_offsets or {}).get(k, ()))
+        counts, carry, state, info = cv.fragments_from_bam(d_buf, d_off, 0, d_start, d_stop, q, counts, carry, state, nbytes=nbytes,
+                                                           carry_capacity=carry_capacity if carry is None else None)
+    c = counts.cpu().numpy()
+    assert (c[nb:] == 7).all(), "values behind count[nbins - 1] changed"
+    return c[:nb], info, carry
+
+
+def reference(chunks, bins, q=3):
+    counts = st = None
+    for reads in chunks:
+        counts, st = F.sequential(reads, 0, bins, q, counts, st)
+    return counts, st
+
+
+def check(cv, chunks, bins, q=3, ref_chunks=None, what="", sorted_input=True, **kw):
+    ec, est = reference(ref_chunks or chunks, bins, q)
+    c, info, _ = gpu_run(cv, chunks, bins, q, **kw)
+    got, exp = [int(x) for x in info[:9]], F.state_words(est)
+    if not sorted_input:
+        keep = (0, 1, 2, 4, 5, 6)
+        assert [got[k] for k in keep] == [exp[k] for k in keep], (what, got, exp)
+        return c, info, est
+    assert (c == ec).all(), (what, np.flatnonzero(c != ec)[:8], c[c != ec][:8], ec[c != ec][:8])
+    assert got == exp, (what, got, exp)
+    return c, info, est
+
+
+def stream(pairs, extra=()):
+    """pairs: lists of records; merged and sorted by position (stable)"""
+    out = [r for p in pairs for r in p] + list(extra)
+    out.sort(key=lambda r: r["pos"])
+    return out
+
+
+GRID = [(s, s + 100) for s in range(0, 6000, 100)]
+
+
+def test_record_counts(cv):
+    for n in (0, 1, 63, 64, 65, 255, 256, 257, 3 * WG + 1):
+        pairs = [F.pair("p%d" % k, 10 * k, 10 * k + 25) for k in range(n)]
+        reads = stream(pairs)[:n]
+        c, info, est = check(cv, [reads], GRID, what=n)
+        assert info[1] == n
+        if n >= 63:
+            assert c.sum() > 0 and info[7] > 0          # the cut leaves mates outstanding
+
+
+@pytest.mark.parametrize("distance", [1, 63, 64, 255, 256, 600])
+def test_mate_distances(cv, distance):
+    """the mate `distance` records behind its read, at every phase of the wave: filler records in between"""
+    reads = []
+    for k in range(70):
+        reads.append(F.rd(k, "a%d" % k, 0x63, 30, 5000 + k, 5008))
+    reads += [F.rd(100 + i, "fill%d" % i, 0x63, 30, 130 + i, 38) for i in range(distance - 1 + 5)]
+    for k in range(70):                                  # mates: good, bad (undo), alternating
+        reads.append(F.rd(5000 + k, "a%d" % k, 0x93, 30 if k % 2 else 1, k, -5008))
+    reads.sort(key=lambda r: r["pos"])
+    bins = [(0, 40), (40, 100), (90, 3000), (3000, 9000)]
+    c, info, est = check(cv, [reads], bins, what=distance)
+    assert est["usable"] > 0 and c.sum() == est["usable"]
+
+
+def test_flags_single_bits_and_pairs(cv):
+    bits = [1 << b for b in range(12)]
+    combos = bits + [a | b for i, a in enumerate(bits) for b in bits[i + 1:]]
+    pairs, k = [], 0
+    for base in (0, 0x3):
+        for combo in combos:
+            for which in (0, 1):
+                fl = [0x3, 0x3]
+                fl[which] = base | combo
+                pairs.append(F.pair("f%d" % k, 7 * k, 7 * k + 40, flags=tuple(fl)))
+                k += 1
+    bins = [(s, s + 64) for s in range(0, 7 * k + 200, 64)]
+    c, info, est = check(cv, [stream(pairs)], bins)
+    assert est["usable"] > 100 and est["paired"] < est["seen"]
+
+
+@pytest.mark.parametrize("q", [0, 3, 60])
+def test_mapq_and_threshold(cv, q):
+    vals = [0, 2, 3, 254, 255]
+    pairs = [F.pair("m%d_%d" % (a, b), 50 * (5 * i + j), 50 * (5 * i + j) + 20, mapqs=(a, b)) for i, a in enumerate(vals) for j, b in enumerate(vals)]
+    c, info, est = check(cv, [stream(pairs)], GRID, q=q)
+    expected = sum(1 for a in vals for b in vals if a != 255 and b != 255 and a >= q and b >= q)
+    assert info[3] == expected
+
+
+def test_groups(cv):
+    bins = [(0, 50), (50, 1000), (1000, 5000)]
+    for size in (1, 2, 3, 5, 300):
+        for spread in (0, 3):
+            reads = [F.rd(10 + spread * i, "g", 0x63 if i % 2 == 0 else 0x93, 30 if i % 7 else 2, 10 + spread * i + (40 if i % 2 == 0 else -40), 60 if i % 2 == 0 else -60)
+                     for i in range(size)]
+            reads += [F.rd(2000 + i, "other%d" % i, 0x63, 30, 2100 + i, 120) for i in range(5)]
+            reads.sort(key=lambda r: r["pos"])
+            c, info, est = check(cv, [reads], bins, what=(size, spread))
+            assert info[10] == max(size, 1)
+    # a supplementary third record between a read and its mate: it takes the mate's place (FragmentBinner does not look at 0x800)
+    reads = [F.rd(10, "s", 0x63, 30, 200, 200), F.rd(50, "s", 0x863, 30, 200, 160), F.rd(200, "s", 0x93, 30, 10, -200)]
+    c, info, est = check(cv, [reads], bins)
+    assert info[3] == 1 and info[7] == 0 and c[1] == 1      # binned by the left read, forgotten at the supplementary record; the right mate then does nothing
+    # same-position pair and triple
+    for n in (2, 3):
+        reads = [F.rd(100, "sp", 0x63 if i == 0 else 0x93, 30, 100, 80) for i in range(n)]
+        c, info, est = check(cv, [reads], bins, what=("same position", n))
+    # a name whose mate never arrives
+    c, info, est = check(cv, [[F.rd(10, "lonely", 0x63, 30, 300, 300)]], bins)
+    assert info[7] == 1 and info[8] == F.carry_bytes([b"lonely"]) and c[1] == 1
+
+
+def test_names(cv):
+    long_a, long_b = "x" * 253 + "a", "x" * 253 + "b"
+    names = ["", "q", long_a, long_b, "pre", "prefix", "x" * 254]
+    pairs = [F.pair(n, 20 * k, 20 * k + 300) for k, n in enumerate(names)]
+    c, info, est = check(cv, [stream(pairs)], GRID)
+    assert info[3] == len(names) and info[7] == 0
+    # ... and with the mates in a second chunk, the names in the carry
+    reads = stream(pairs)
+    c, info, est = check(cv, [reads[:len(names)], reads[len(names):]], GRID)
+    assert info[7] == 0 and info[8] == 0
+    # l_read_name = 0 is the empty name too
+    reads = [F.rd(10, "", 0x63, 30, 200, 200, l_read_name=0), F.rd(200, "", 0x93, 2, 10, -200)]
+    c, info, est = check(cv, [reads], GRID)
+    assert info[3] == 0 and c.sum() == 0
+
+
+def mixed_sample(n=600, seed=5):
+    rng = np.random.RandomState(seed)
+    reads = F.random_reads(rng, 260, max_group=9, span=5000)
+    assert len(reads) >= n
+    return reads[:n], F.random_bins(np.random.RandomState(seed + 1), 60, span=5000)
+
+
+def test_hash_bits_hook(cv):
+    reads, bins = mixed_sample()
+    ec, est = reference([reads[:350], reads[350:]], bins)
+    assert np.abs(ec).sum() > 20
+    saved = os.environ.get("CANVAS_FRAG_HASH_BITS")
+    try:
+        for bits in ("0", "1", "4", None):
+            if bits is None:
+                os.environ.pop("CANVAS_FRAG_HASH_BITS", None)
+            else:
+                os.environ["CANVAS_FRAG_HASH_BITS"] = bits
+            c, info, _ = gpu_run(cv, [reads[:350], reads[350:]], bins)
+            assert (c == ec).all() and [int(x) for x in info[:9]] == F.state_words(est), bits
+            assert (info[9] > 0) == (bits is not None), (bits, info[9])
+    finally:
+        if saved is None:
+            os.environ.pop("CANVAS_FRAG_HASH_BITS", None)
+        else:
+            os.environ["CANVAS_FRAG_HASH_BITS"] = saved
+
+
+def test_bins(cv):
+    pairs = [F.pair("b%d" % k, 37 * k, 37 * k + 60) for k in range(120)]
+    reads = stream(pairs)
+    for bins in ([], [(100, 2000)], [(3000, 3100), (0, 500), (400, 900), (100, 200), (2000, 2500), (600, 2600)],      # unsorted BED order, overlapping, nested
+                 [(0, 5000), (100, 200), (150, 160), (300, 4000), (4000, 4500)]):
+        check(cv, [reads], bins, what=bins)
+    # an overlap tie: the first bin wins; a fragment that ends exactly where a bin starts; one beyond the last bin; one spanning 50 bins
+    bins = [(0, 100), (100, 200)] + [(200 + 10 * k, 210 + 10 * k) for k in range(60)]
+    reads = stream([F.pair("tie", 50, 120, tlen=100), F.pair("touch", 60, 90, tlen=40), F.pair("span", 195, 400, tlen=505), F.pair("beyond", 900, 950, tlen=80)])
+    c, info, est = check(cv, [reads], bins)
+    assert c[0] == 2 and c[1] == 0 and info[3] == 3 and c[2:].sum() == 1
+
+
+def test_tlen(cv):
+    bins = [(0, 1000), (2 ** 31 - 500, 2 ** 31 - 1)]
+    reads = [F.rd(10, "neg", 0x63, 30, 100, -120), F.rd(20, "zero", 0x63, 30, 100, 0), F.rd(100, "neg", 0x93, 30, 10, 120), F.rd(100, "zero", 0x93, 30, 20, 0)]
+    reads += F.pair("wrap", 2 ** 31 - 300, 2 ** 31 - 200, tlen=1000)
+    c, info, est = check(cv, [reads], bins)
+    assert c.tolist() == [0, 1]            # a negative length on the left mate overlaps nothing; pos + tlen past 2^31 wraps twice (fragment_ref.find_best_bin)
+
+
+@pytest.fixture(scope="module")
+def scenario40():
+    rng = np.random.RandomState(11)
+    bins = F.random_bins(rng, 30)
+    reads = F.random_reads(rng, 30, max_group=6)[:40]
+    return reads, bins
+
+
+def test_every_two_chunk_split(cv, scenario40):
+    reads, bins = scenario40
+    whole, wst = reference([reads], bins)
+    assert np.abs(whole).sum() > 0
+    for cut in range(41):
+        c, info, est = check(cv, [reads[:cut], reads[cut:]], bins, what=cut)
+        assert (c == whole).all() and F.state_words(est) == F.state_words(wst)
+
+
+def test_three_chunks_and_the_carry_empties(cv):
+    n = 3 * WG + 1
+    pairs = [F.pair("t%d" % k, 5 * k, 5 * k + 1500, flags=(0x63, 0x93), mapqs=(30, 30 if k % 3 else 0)) for k in range(n)]
+    reads = stream(pairs)[:n]
+    bins = [(s, s + 250) for s in range(0, 8000, 250)]
+    c, info, est = check(cv, [reads[:WG - 3], reads[WG - 3:2 * WG + 10], reads[2 * WG + 10:]], bins)
+    assert info[7] > 100
+    full = stream(pairs)
+    c, info, est = check(cv, [full[:700], full[700:]], bins)
+    assert info[7] == 0 and info[8] == 0 and info[3] == sum(1 for k in range(n) if k % 3)
+
+
+def raw_call(cv, d_buf, d_off, nbytes, d_start, d_stop, counts, carry, cap, state, ref_id=0, q=3, nbins=None):
+    info = np.zeros(16, np.int64)
+    rc = cv.lib.canvas_fragments_from_bam(cv.ctx, C.c_void_p(d_buf.data_ptr()), C.c_uint64(nbytes), C.c_void_p(d_off.data_ptr()), C.c_int64(int(d_off.numel())), C.c_int32(ref_id),
+                                          C.c_void_p(d_start.data_ptr()), C.c_void_p(d_stop.data_ptr()), C.c_int64(int(d_start.numel()) if nbins is None else nbins), C.c_int32(q),
+                                          C.c_void_p(counts.data_ptr()), C.c_void_p(carry.data_ptr()), C.c_uint64(cap), C.c_void_p(state.data_ptr()),
+                                          info.ctypes.data_as(C.c_void_p))
+    return rc, info
+
+
+def test_carry_capacity(cv):
+    import torch
+    lefts = [F.rd(10 * k, "left%d" % k, 0x63, 30, 4000 + k, 4000) for k in range(20)]
+    bins = GRID
+    d_start, d_stop = dev_bins(cv, bins)
+    d_buf, d_off, nbytes = dev_chunk(cv, lefts)
+    counts = torch.zeros(len(bins), dtype=torch.int32, device=cv.device)
+    state = torch.zeros(16, dtype=torch.int64, device=cv.device)
+    carry = torch.full((4096,), 0x5A, dtype=torch.uint8, device=cv.device)
+    torch.cuda.synchronize()
+    # a first chunk that fits: one entry
+    d1_buf, d1_off, nb1 = dev_chunk(cv, [F.rd(1, "first", 0x63, 30, 5000, 5000)])
+    rc, info = raw_call(cv, d1_buf, d1_off, nb1, d_start, d_stop, counts, carry, F.carry_bytes([b"first"]), state)
+    assert rc == 0 and info[7] == 1 and info[8] == F.carry_bytes([b"first"])
+    before = (counts.cpu().numpy().copy(), carry.cpu().numpy().copy(), state.cpu().numpy().copy())
+    # the second does not (its capacity is what the first chunk used, and then 16 bytes below what is needed)
+    names = [b"first"] + [("left%d" % k).encode() for k in range(20)]
+    need = F.carry_bytes(names)
+    for cap in (F.carry_bytes([b"first"]), need - 16, need - 1):
+        rc, info = raw_call(cv, d_buf, d_off, nbytes, d_start, d_stop, counts, carry, cap, state)
+        assert rc == -4 and info[8] == need, (cap, rc, info)                     # CANVAS_ERR_CAPACITY
+        after = (counts.cpu().numpy(), carry.cpu().numpy(), state.cpu().numpy())
+        assert all((a == b).all() for a, b in zip(before, after)), "a refused call changed counts, carry or state"
+    rc, info = raw_call(cv, d_buf, d_off, nbytes, d_start, d_stop, counts, carry, need, state)
+    ec, est = reference([[F.rd(1, "first", 0x63, 30, 5000, 5000)], lefts], bins)
+    assert rc == 0 and [int(x) for x in info[:9]] == F.state_words(est) and (counts.cpu().numpy() == ec).all()
+    # a 16-byte carry from the start
+    counts.zero_(); state.zero_()
+    small = torch.zeros(16, dtype=torch.uint8, device=cv.device)
+    torch.cuda.synchronize()
+    rc, info = raw_call(cv, d_buf, d_off, nbytes, d_start, d_stop, counts, small, 16, state)
+    assert rc == -4 and info[8] == F.carry_bytes(names[1:]) and not counts.cpu().numpy().any() and not state.cpu().numpy().any() and not small.cpu().numpy().any()
+    exact = torch.zeros(int(info[8]), dtype=torch.uint8, device=cv.device)      # ... and exactly the bytes it asked for suffice
+    torch.cuda.synchronize()
+    rc, info = raw_call(cv, d_buf, d_off, nbytes, d_start, d_stop, counts, exact, int(exact.numel()), state)
+    assert rc == 0 and info[7] == 20 and info[8] == exact.numel() and info[3] == 20
+    # the wrapper grows it
+    mates = [F.rd(4000 + k, "left%d" % k, 0x93, 30, 10 * k, -4000) for k in range(20)]
+    c, info, carry2 = gpu_run(cv, [lefts, mates], bins, carry_capacity=16)
+    ec, est = reference([lefts, mates], bins)
+    assert (c == ec).all() and [int(x) for x in info[:9]] == F.state_words(est) and carry2.numel() >= F.carry_bytes(names[1:]) and info[3] == 20
+
+
+def test_stop(cv):
+    bins = GRID
+    mine = stream([F.pair("s%d" % k, 20 * k, 20 * k + 30) for k in range(150)])
+    behind = [F.rd(5000 + k, "late%d" % k, 0x63, 30, 5100, 150) for k in range(40)] + [F.rd(1, "s3", 0x93, 1, 0, -50)]
+    for where in (0, 1, 150, 299, 300):
+        for flag in (0x63, 0x4):                         # a record of another reference stops whether it passes the skip filters or not
+            other = F.rd(7, "o", flag, 30, 57, 60, ref=1)
+            chunk = mine[:where] + [other] + mine[where:] + behind
+            c, info, est = check(cv, [chunk, behind], bins, what=(where, flag))
+            assert info[0] == 1 and info[1] == where + 1
+    # as the last record of a chunk; the next chunk does nothing
+    c, info, est = check(cv, [mine + [F.rd(7, "o", 0x63, ref=1)], behind], bins)
+    assert info[0] == 1 and info[1] == len(mine) + 1
+
+
+def test_sortedness(cv):
+    bins = GRID
+    base = [F.rd(10 * k, "u%d" % k, 0x63, 30, 10 * k + 50, 70) for k in range(2 * WG + 40)]
+    for at in (1, 17, 63, 64, WG - 1, WG, WG + 1, 2 * WG):
+        reads = [dict(r) for r in base]
+        reads[at]["pos"] = reads[at - 1]["pos"] - 1
+        c, info, est = check(cv, [reads], bins, sorted_input=False, what=at)
+        assert info[6] == at + 1
+    # across a chunk boundary (through state[5]); the ordinal counts the records of both chunks.  Only the first one is reported.
+    reads = [dict(r) for r in base]
+    reads[300]["pos"] = 5
+    reads[400]["pos"] = 3
+    c, info, est = check(cv, [reads[:300], reads[300:]], bins, sorted_input=False)
+    assert info[6] == 301
+    # equal positions and a first record at -1 are in order
+    reads = [F.rd(-1, "m1", 0x63, 30, 40, 60), F.rd(-1, "m2", 0x63, 30, 40, 60), F.rd(0, "m3", 0x63, 30, 40, 60)]
+    c, info, est = check(cv, [reads], bins)
+    assert info[6] == 0
+
+
+def test_malformed(cv):
+    """every damaged record is the LAST bytes of a buffer of exactly the records' size (pad 0): reading past a bound would leave it"""
+    bins = GRID
+    good = F.pair("g1", 3, 40) + [F.rd(50, "g2", 0x63, 30, 90, 60)]
+    good.sort(key=lambda r: r["pos"])
+    stand_in = dict(malformed=True)
+    cases = {
+        "block_size 31": F.rd(9, block_size=31),
+        "block_size past the chunk": None,
+        "name and CIGAR past block_size": F.rd(9, n_cigar=60000),
+        "name past block_size": F.rd(9, l_read_name=255, cigar=[], seq=""),
+        "negative block_size": F.rd(9, block_size=-8),
+    }
+    for what, bad in cases.items():
+        past_chunk = bad is None
+        if past_chunk:
+            bad = F.rd(9)
+            bad["block_size"] = len(H.encode_record(bad)) - 4 + 1
+        c, info, est = check(cv, [good + [bad]], bins, ref_chunks=[good + [stand_in]], what=what)
+        assert info[4] == 1 and info[1] == 4 and info[3] == 2
+        if past_chunk:
+            continue
+        c, info, est = check(cv, [[bad] + good], bins, ref_chunks=[[stand_in] + good], what=what + " first")
+        assert info[4] == 1 and info[3] == 2
+    buf_len = sum(len(H.encode_record(r)) for r in good)
+    for where, off in (("nbytes - 20", -20), ("nbytes - 35", -35), ("nbytes", buf_len), ("nbytes + 1", buf_len + 1), ("2^63 - 1", 2 ** 63 - 1)):
+        for idx in (0, 2, 3):
+            ref = list(good)
+            ref.insert(idx, stand_in)
+            c, info, est = check(cv, [good], bins, ref_chunks=[ref], extra_offsets={0: [(idx, off)]}, what="offset %s at %d" % (where, idx))
+            assert info[4] == 1 and info[1] == 4 and info[3] == 2
+    # many of them among many records, over a workgroup edge; a malformed record does not take part in the order of positions
+    reads, ref = [], []
+    for i in range(2 * WG + 9):
+        if i % 5 == 2:
+            reads.append(F.rd(0, n_cigar=50000)); ref.append(stand_in)
+        else:
+            reads.append(F.rd(i, "k%d" % (i // 2), 0x63 if i % 2 == 0 else 0x93, 30, i + 1 if i % 2 == 0 else i - 1, 9 if i % 2 == 0 else -9)); ref.append(reads[-1])
+    c, info, est = check(cv, [reads], bins, ref_chunks=[ref])
+    assert info[4] == sum(1 for r in ref if r is stand_in) and info[6] == 0
+
+
+def test_arguments(cv):
+    import torch
+    d_buf, d_off, nb = dev_chunk(cv, [F.rd(1)])
+    d_start, d_stop = dev_bins(cv, [(0, 10)])
+    counts = torch.zeros(4, dtype=torch.int32, device=cv.device)
+    carry = torch.zeros(64, dtype=torch.uint8, device=cv.device)
+    state = torch.zeros(16, dtype=torch.int64, device=cv.device)
+    torch.cuda.synchronize()
+    assert raw_call(cv, d_buf, d_off, nb, d_start, d_stop, counts, carry, 64, state, ref_id=-1)[0] == -1
+    assert raw_call(cv, d_buf, d_off, nb, d_start, d_stop, counts, carry, 64, state, q=-1)[0] == -1
+    assert raw_call(cv, d_buf, d_off, nb, d_start, d_stop, counts, carry, 64, state, nbins=-1)[0] == -1
+    assert raw_call(cv, d_buf, d_off, nb, d_start, d_stop, counts, carry, 64, state, nbins=2 ** 31)[0] == -1
+    assert not state.cpu().numpy().any()
+    assert raw_call(cv, d_buf, d_off, nb, d_start, d_stop, counts, carry, 64, state)[0] == 0
