@@ -7,8 +7,8 @@
 // first bin whose prefix maximum of Stop exceeds the fragment's start, whatever the order of the BED file.  What is left is, per NAME, a two-variable state machine
 // (binned into bin b or not, in the same-position set or not) driven by the records of that name in file order.
 //   k_frag_prefmax   one workgroup: running maximum of d_bin_stop into the workspace.
-//   k_frag_classify  one lane per record: fixed fields with byte loads (a record starts at any address), the shape checks of obs.hip, the smallest index of a record of
-//                    another reference (ballot, LDS, ONE atomicMax per workgroup on a word of the call's control block), the skip filters, a 64-bit hash of the name
+//   k_frag_classify  one lane per record: the fixed fields with their shape checks (bam_record.hpp: bam_rec_load), the smallest index of a record of another reference
+//                    (bam_block_first, then ONE atomicMax per workgroup on a word of the call's control block, with bam_record.hpp's stop key), the skip filters, a 64-bit hash of the name
 //                    bytes.  32 bytes per record go to the workspace {pos, next_pos, tlen, class, hash, offset of the record}.
 //   k_frag_insert    one lane per item — the carried entries first ("records in front of index 0"), then the records below the stop: paired / malformed counters
 //                    (ballot, one atomic per wave), sortedness against the nearest well-formed record on the left (the summaries; the chunk before through state[5]),
@@ -26,8 +26,8 @@
 // a name has one entry, and every entry lies in front of every record).
 // Bytes per record: 36 fixed + the name (read twice: hash, and the comparison with its mate) from the chunk; 32 written and about three times read as summary; 4 of link,
 // 4 of leader, 4 of event, 8 of slot head.
-// Every offset formed is checked first: a hostile chunk cannot make the kernels read outside [d_records, d_records + nbytes).
-#include "common.hpp"
+// Byte loads, offsets and their checks are bam_record.hpp's.
+#include "bam_record.hpp"
 
 #define FRAG_BLOCK 256
 #define FRAG_WAVES (FRAG_BLOCK / WAVE)
@@ -47,11 +47,6 @@ struct FragArgs {
     unsigned long long* ctl; int32_t* prefMax; FragRec* summary; int32_t* head; uint32_t slotMask; int32_t* next; int32_t* leader; uint32_t* ev; FragHdr* newHdr; uint8_t* newNames; uint64_t nameCap;
 };
 
-__device__ __forceinline__ uint32_t frag_ld8(const uint8_t* __restrict__ p, uint64_t at) { return p[at]; }
-__device__ __forceinline__ uint32_t frag_ld16(const uint8_t* __restrict__ p, uint64_t at) { return (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8); }
-__device__ __forceinline__ uint32_t frag_ld32(const uint8_t* __restrict__ p, uint64_t at) {
-    return (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8) | ((uint32_t)p[at + 2] << 16) | ((uint32_t)p[at + 3] << 24);
-}
 __device__ __forceinline__ unsigned long long frag_hash(const uint8_t* __restrict__ p, uint32_t n) {      // FNV-1a with a final mix
     unsigned long long h = 0xcbf29ce484222325ull;
     for (uint32_t i = 0; i < n; i++) h = (h ^ (unsigned long long)p[i]) * 0x100000001b3ull;
@@ -62,7 +57,7 @@ __device__ __forceinline__ unsigned long long frag_hash(const uint8_t* __restric
 __device__ __forceinline__ int64_t frag_limit(const FragArgs& a, bool* stopHere) {
     const unsigned long long key = a.ctl[FK_STOP_KEY];
     if (stopHere) *stopHere = key != 0ull;
-    return key ? (int64_t)(0xFFFFFFFFu - (uint32_t)key) : a.nrec;
+    return key ? bam_stop_index(key) : a.nrec;
 }
 // item i: a carried entry (i < ncarry) or record i - ncarry.  Name bytes and hash.
 __device__ __forceinline__ const uint8_t* frag_item_name(const FragArgs& a, int64_t i, uint32_t* len, unsigned long long* hash) {
@@ -76,7 +71,7 @@ __device__ __forceinline__ const uint8_t* frag_item_name(const FragArgs& a, int6
     }
     const FragRec s = a.summary[i - a.ncarry];
     *len = s.cls >> FC_NAME_SHIFT; *hash = s.hash;
-    return a.rec + s.off + 36;
+    return a.rec + bam_name_at(s.off);
 }
 __device__ __forceinline__ bool frag_same_bytes(const uint8_t* __restrict__ x, const uint8_t* __restrict__ y, uint32_t n) {
     for (uint32_t i = 0; i < n; i++) if (x[i] != y[i]) return false;
@@ -107,42 +102,31 @@ __global__ void __launch_bounds__(1024) k_frag_prefmax(const int32_t* __restrict
 
 __global__ void __launch_bounds__(FRAG_BLOCK) k_frag_classify(FragArgs a) {
     __shared__ int32_t sStop[FRAG_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t r = (int64_t)blockIdx.x * FRAG_BLOCK + tid;
     bool stop = false;
     if (r < a.nrec) {
         FragRec s; s.pos = 0; s.nextPos = 0; s.tlen = 0; s.cls = FC_MALFORMED; s.hash = 0ull; s.off = 0ull;
-        const uint64_t off = a.offs[r];
-        if (!(off > a.nbytes || a.nbytes - off < 36)) {                                         // block_size + the 32 fixed bytes
-            const uint8_t* __restrict__ rec = a.rec;
-            const uint32_t bs = frag_ld32(rec, off), rid = frag_ld32(rec, off + 4), p = frag_ld32(rec, off + 8), lname = frag_ld8(rec, off + 12), mapq = frag_ld8(rec, off + 13);
-            const uint32_t ncig = frag_ld16(rec, off + 16), flag = frag_ld16(rec, off + 18), nrid = frag_ld32(rec, off + 24), np = frag_ld32(rec, off + 28), tlen = frag_ld32(rec, off + 32);
-            if (!((int32_t)bs < 32 || (uint64_t)bs > a.nbytes - off - 4 || 32ull + lname + 4ull * ncig > (uint64_t)bs)) {
-                const uint32_t nlen = lname ? lname - 1u : 0u;                                  // the name without its NUL: inside the record (32 + l_read_name <= block_size)
-                uint32_t cls = nlen << FC_NAME_SHIFT;
-                if ((int32_t)rid != a.refId) { cls |= FC_OTHER_REF; stop = true; }
-                else {
-                    if (flag & 0x1u) cls |= FC_PAIRED;
-                    if (!(flag & (0x4u | 0x8u | 0x100u)) && (flag & 0x3u) == 0x3u) {           // IsMapped, IsMateMapped, IsPrimaryAlignment, IsPaired && IsProperPair
-                        cls |= FC_LIVE;
-                        if ((flag & 0x600u) || mapq == 255u || (int32_t)mapq < a.quality) cls |= FC_BAD;
-                        if (rid != nrid) cls |= FC_REF_MISMATCH;
-                        s.hash = frag_hash(rec + off + 36, nlen) & a.hashMask;
-                    }
+        const uint64_t off = a.offs[r]; BamRec b;
+        if (bam_rec_load(a.rec, a.nbytes, off, b)) {
+            const uint32_t flag = b.flag, nlen = b.l_read_name ? b.l_read_name - 1u : 0u;       // the name without its NUL: inside the record (32 + l_read_name <= block_size)
+            uint32_t cls = nlen << FC_NAME_SHIFT;
+            if (b.refID != a.refId) { cls |= FC_OTHER_REF; stop = true; }
+            else {
+                if (flag & 0x1u) cls |= FC_PAIRED;
+                if (!(flag & (0x4u | 0x8u | 0x100u)) && (flag & 0x3u) == 0x3u) {               // IsMapped, IsMateMapped, IsPrimaryAlignment, IsPaired && IsProperPair
+                    cls |= FC_LIVE;
+                    if ((flag & 0x600u) || b.mapq == 255u || (int32_t)b.mapq < a.quality) cls |= FC_BAD;
+                    if (b.refID != b.next_refID) cls |= FC_REF_MISMATCH;
+                    s.hash = frag_hash(a.rec + bam_name_at(off), nlen) & a.hashMask;
                 }
-                s.pos = (int32_t)p; s.nextPos = (int32_t)np; s.tlen = (int32_t)tlen; s.cls = cls; s.off = off;
             }
+            s.pos = b.pos; s.nextPos = b.next_pos; s.tlen = b.tlen; s.cls = cls; s.off = off;
         }
         a.summary[r] = s;
     }
-    const unsigned long long mStop = __ballot(stop);
-    if (lane == 0) sStop[wave] = mStop ? wave * WAVE + __ffsll((long long)mStop) - 1 : -1;
-    __syncthreads();
-    if (tid == 0) {
-        int s = -1;
-        for (int w = FRAG_WAVES - 1; w >= 0; w--) if (sStop[w] >= 0) s = sStop[w];
-        if (s >= 0) atomicMax(&a.ctl[FK_STOP_KEY], (1ull << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)((int64_t)blockIdx.x * FRAG_BLOCK + s)));      // the smallest index wins
-    }
+    const int first = bam_block_first(stop, sStop);
+    if (tid == 0 && first >= 0) atomicMax(&a.ctl[FK_STOP_KEY], bam_stop_key(1u, (int64_t)blockIdx.x * FRAG_BLOCK + first));      // the smallest index wins
 }
 
 __global__ void __launch_bounds__(FRAG_BLOCK) k_frag_insert(FragArgs a) {
@@ -159,7 +143,7 @@ __global__ void __launch_bounds__(FRAG_BLOCK) k_frag_insert(FragArgs a) {
         if (valid) {                                                                           // the nearest well-formed record on the left: almost always r - 1
             bool have = a.state[FRAG_HAVE_LAST] != 0; int32_t prev = have ? (int32_t)a.state[FRAG_LAST_POS] : -1;
             for (int64_t q = r - 1; q >= 0; q--) { const FragRec t = a.summary[q]; if (!(t.cls & FC_MALFORMED)) { prev = t.pos; break; } }
-            if (s.pos < prev) atomicMax(&a.ctl[FK_UNSORTED_KEY], (1ull << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)r));
+            if (s.pos < prev) atomicMax(&a.ctl[FK_UNSORTED_KEY], bam_stop_key(1u, r));
         }
     }
     const unsigned long long mPaired = __ballot(paired), mBad = __ballot(malformed), mValid = __ballot(valid);
@@ -267,7 +251,7 @@ __global__ void __launch_bounds__(FRAG_BLOCK) k_frag_commit(FragArgs a, int32_t*
         state[FRAG_USABLE] += (long long)a.ctl[FK_USABLE];
         state[FRAG_MALFORMED] += (long long)a.ctl[FK_MALFORMED];
         const unsigned long long u = a.ctl[FK_UNSORTED_KEY];
-        if (u && state[FRAG_UNSORTED] == 0) state[FRAG_UNSORTED] = seenBefore + (long long)(0xFFFFFFFFu - (uint32_t)u) + 1;      // 1 + its ordinal among the records seen
+        if (u && state[FRAG_UNSORTED] == 0) state[FRAG_UNSORTED] = seenBefore + bam_stop_index(u) + 1;      // 1 + its ordinal among the records seen
         const unsigned long long lastKey = a.ctl[FK_LAST_KEY];
         if (lastKey) { state[FRAG_LAST_POS] = (long long)a.summary[lastKey - 1ull].pos; state[FRAG_HAVE_LAST] = 1; }
         state[FRAG_ENTRIES] = (long long)n; state[FRAG_CARRY_BYTES] = (long long)need;

@@ -3,11 +3,10 @@
 //
 // The reference's loop is sequential in two places only: it ENDS at the first record that passes the read filters and belongs to another reference (a prefix rule), and
 // the fragment length of a position is the one of the LAST kept read that starts there.  Everything else is a filter per record and a saturating count per position.
-//   k_obs_classify  one lane per record: the fixed fields and the first CIGAR word (byte loads — a record starts at any address), shape checks against the record's and the
-//                   chunk's length, the filters in the reference's order (:239-262).  8 bytes per record go to the workspace {pos, clamped tlen, class}, 8 bytes per tile of
-//                   256 records {lane of the tile's first kept record, its pos}.  The smallest index of a stopping record: ballot inside the wave, four words of LDS, ONE
-//                   atomic per workgroup on d_state[6].  That word holds (epoch << 32 | ~index) and is raised with atomicMax: the smallest index of the newest chunk wins, a
-//                   zeroed word means "never stopped", and a word of an older epoch "stopped in an earlier chunk" — no launch or fill is needed to reset it between chunks.
+//   k_obs_classify  one lane per record: the fixed fields with their shape checks against the record's and the chunk's length (bam_record.hpp: bam_rec_load) and the first
+//                   CIGAR word, the filters in the reference's order (:239-262).  8 bytes per record go to the workspace {pos, clamped tlen, class}, 8 bytes per tile of
+//                   256 records {lane of the tile's first kept record, its pos}.  The smallest index of a stopping record: bam_block_first, then ONE atomicMax per
+//                   workgroup on d_state[6] with the stop key of bam_record.hpp (epoch and index in one word, so that nothing has to reset it between chunks).
 //   k_obs_apply     one lane per record below the stop: counters (reduced per workgroup), hits, fragment lengths.
 //                   hits, mode 0: a byte store of 1.  Modes 3 / 5: a compare-and-swap on the aligned 32-bit word that holds the byte, adding 1 << shift only while the byte is
 //                   below 255 — the sum cannot carry into the neighbour, and a byte that has reached 255 costs a load and no atomic.  Expected contention is low (a fraction
@@ -18,62 +17,40 @@
 //                   costs one 512-byte read per 16 384 of them.  One store per position; across chunks the stream's order makes the later chunk win.
 // The record bytes are read once (36 + l_read_name-dependent 4 bytes per record, through the sectors they touch); the 8-byte record summaries are written and read once,
 // coalesced; hits / frag are touched only where a kept read starts.
-// Every offset formed is checked first: a hostile chunk cannot make the kernels read outside [d_records, d_records + nbytes).
-#include "common.hpp"
+// Byte loads, offsets and their checks are bam_record.hpp's.
+#include "bam_record.hpp"
 
 #define OBS_BLOCK 256
 #define OBS_WAVES (OBS_BLOCK / WAVE)
 enum { OBS_STOPPED = 0, OBS_SEEN = 1, OBS_KEPT = 2, OBS_OOR = 3, OBS_MALFORMED = 4, OBS_LAST_POS = 5, OBS_STOP_KEY = 6, OBS_NSTATE = 8 };
 enum { OBS_CLS_SKIPPED = 0, OBS_CLS_KEPT = 1, OBS_CLS_MALFORMED = 2 };
 
-__device__ __forceinline__ uint32_t obs_ld8(const uint8_t* __restrict__ p, uint64_t at) { return p[at]; }
-__device__ __forceinline__ uint32_t obs_ld16(const uint8_t* __restrict__ p, uint64_t at) { return (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8); }
-__device__ __forceinline__ uint32_t obs_ld32(const uint8_t* __restrict__ p, uint64_t at) {
-    return (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8) | ((uint32_t)p[at + 2] << 16) | ((uint32_t)p[at + 3] << 24);
-}
-// the stop word: (epoch << 32) | (0xFFFFFFFF - index).  Epochs are never 0.
-__device__ __forceinline__ bool obs_stopped_before(unsigned long long key, uint32_t epoch) { return key != 0ull && (uint32_t)(key >> 32) != epoch; }
-
 __global__ void __launch_bounds__(OBS_BLOCK) k_obs_classify(const uint8_t* __restrict__ rec, uint64_t nbytes, const uint64_t* __restrict__ offs, int64_t nrec, int32_t refId,
                                                             int32_t pairedEnd, uint32_t epoch, uint2* __restrict__ summary, int2* __restrict__ tiles,
                                                             unsigned long long* __restrict__ state) {
-    __shared__ int32_t sStop[OBS_WAVES], sFirst[OBS_WAVES], sFirstPos[OBS_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (obs_stopped_before(state[OBS_STOP_KEY], epoch)) return;          // uniform over the grid: a word of this epoch is only written when no older one stood there
+    __shared__ int32_t sStop[OBS_WAVES], sFirst[OBS_WAVES];
+    const int tid = threadIdx.x;
+    if (bam_stopped_before(state[OBS_STOP_KEY], epoch)) return;          // uniform over the grid: a word of this epoch is only written when no older one stood there
     const int64_t r = (int64_t)blockIdx.x * OBS_BLOCK + tid;
     uint32_t cls = OBS_CLS_SKIPPED; bool stop = false; int32_t pos = 0, frag = 0;
     if (r < nrec) {
-        const uint64_t off = offs[r];
-        if (off > nbytes || nbytes - off < 36) cls = OBS_CLS_MALFORMED;                     // block_size + the 32 fixed bytes
-        else {
-            // every fixed field is requested before the first decision (a load under a condition is waited for where the condition ends)
-            const uint32_t bs = obs_ld32(rec, off), rid = obs_ld32(rec, off + 4), p = obs_ld32(rec, off + 8), lname = obs_ld8(rec, off + 12);
-            const uint32_t ncig = obs_ld16(rec, off + 16), flag = obs_ld16(rec, off + 18), tlen = obs_ld32(rec, off + 32);
-            if ((int32_t)bs < 32 || (uint64_t)bs > nbytes - off - 4 || 32ull + lname + 4ull * ncig > (uint64_t)bs) cls = OBS_CLS_MALFORMED;
-            else if (!(flag & (0x4u | 0x200u | 0x400u | 0x10u | 0x900u)) && ncig != 0u) {
-                const uint32_t c0 = obs_ld32(rec, off + 36 + lname);                        // inside the record: 32 + l_read_name + 4 n_cigar <= block_size
-                if ((c0 & 15u) == 0u && (c0 >> 4) >= 35u && !(pairedEnd && !(flag & 0x2u))) {
-                    if ((int32_t)rid != refId) stop = true;
-                    else if ((int32_t)rid != -1) {
-                        cls = OBS_CLS_KEPT; pos = (int32_t)p;
-                        frag = (int32_t)tlen < 0 ? 0 : ((int32_t)tlen > 32767 ? 32767 : (int32_t)tlen);
-                    }
+        const uint64_t off = offs[r]; BamRec b;
+        if (!bam_rec_load(rec, nbytes, off, b)) cls = OBS_CLS_MALFORMED;
+        else if (!(b.flag & (0x4u | 0x200u | 0x400u | 0x10u | 0x900u)) && b.n_cigar_op != 0u) {
+            const uint32_t c0 = bam_ld32(rec, bam_cigar_at(off, b.l_read_name));            // inside the record: 32 + l_read_name + 4 n_cigar <= block_size
+            if ((c0 & 15u) == 0u && (c0 >> 4) >= 35u && !(pairedEnd && !(b.flag & 0x2u))) {
+                if (b.refID != refId) stop = true;
+                else if (b.refID != -1) {
+                    cls = OBS_CLS_KEPT; pos = b.pos;
+                    frag = b.tlen < 0 ? 0 : (b.tlen > 32767 ? 32767 : b.tlen);
                 }
             }
         }
         summary[r] = make_uint2((uint32_t)pos, (uint32_t)frag | (cls << 16));
     }
-    const unsigned long long mStop = __ballot(stop), mKept = __ballot(cls == OBS_CLS_KEPT);
-    const int firstKept = mKept ? __ffsll((long long)mKept) - 1 : -1;
-    if (lane == 0) { sStop[wave] = mStop ? wave * WAVE + __ffsll((long long)mStop) - 1 : -1; sFirst[wave] = firstKept < 0 ? -1 : wave * WAVE + firstKept; }
-    if (lane == firstKept) sFirstPos[wave] = pos;
-    __syncthreads();
-    if (tid == 0) {
-        int s = -1, f = -1, fp = 0;
-        for (int w = OBS_WAVES - 1; w >= 0; w--) { if (sStop[w] >= 0) s = sStop[w]; if (sFirst[w] >= 0) { f = sFirst[w]; fp = sFirstPos[w]; } }
-        tiles[blockIdx.x] = make_int2(f, fp);
-        if (s >= 0) atomicMax(&state[OBS_STOP_KEY], ((unsigned long long)epoch << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)((int64_t)blockIdx.x * OBS_BLOCK + s)));
-    }
+    const int s = bam_block_first(stop, sStop), f = bam_block_first(cls == OBS_CLS_KEPT, sFirst);
+    if (tid == (f < 0 ? 0 : f)) tiles[blockIdx.x] = make_int2(f, f < 0 ? 0 : pos);          // the tile's first kept record writes its own position
+    if (tid == 0 && s >= 0) atomicMax(&state[OBS_STOP_KEY], bam_stop_key(epoch, (int64_t)blockIdx.x * OBS_BLOCK + s));
 }
 
 __global__ void __launch_bounds__(OBS_BLOCK) k_obs_apply(const uint2* __restrict__ summary, const int2* __restrict__ tiles, int64_t nrec, int64_t ntiles, uint32_t epoch,
@@ -87,8 +64,8 @@ __global__ void __launch_bounds__(OBS_BLOCK) k_obs_apply(const uint2* __restrict
     // records [0, limit) act; seenAdd of them are seen (the stopping record is seen and does nothing)
     const unsigned long long key = state[OBS_STOP_KEY];                  // (not written by this kernel)
     int64_t limit = nrec, seenAdd = nrec; bool stopHere = false;
-    if (obs_stopped_before(key, epoch)) { limit = 0; seenAdd = 0; }
-    else if (key != 0ull) { limit = (int64_t)(0xFFFFFFFFu - (uint32_t)key); seenAdd = limit + 1; stopHere = true; }
+    if (bam_stopped_before(key, epoch)) { limit = 0; seenAdd = 0; }
+    else if (key != 0ull) { limit = bam_stop_index(key); seenAdd = limit + 1; stopHere = true; }
     if (blockIdx.x == 0 && tid == 0) { state[OBS_SEEN] += (unsigned long long)seenAdd; if (stopHere) state[OBS_STOPPED] = 1ull; }
     const int64_t tile0 = (int64_t)blockIdx.x * OBS_BLOCK;
     if (tile0 >= limit) return;
@@ -152,14 +129,6 @@ __global__ void __launch_bounds__(OBS_BLOCK) k_obs_apply(const uint2* __restrict
     if (tid < 3 && sCnt[tid]) atomicAdd(&state[OBS_KEPT + tid], (unsigned long long)sCnt[tid]);
 }
 
-// the state travels through the context's pinned mailbox (common.hpp: payload, system fence, sequence word last)
-__global__ void k_obs_mail(const unsigned long long* __restrict__ state, long long* pin, unsigned* seqWord, unsigned seq) {
-    if (threadIdx.x < OBS_NSTATE) pin[threadIdx.x] = (long long)state[threadIdx.x];
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) cvx_mail_publish(seqWord, seq);
-}
-
 static std::atomic<uint32_t> g_obs_epoch{0};
 
 extern "C" int32_t canvas_hits_from_bam(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nbytes, const uint64_t* d_record_offsets, int64_t nrecords, int32_t ref_id,
@@ -188,13 +157,5 @@ extern "C" int32_t canvas_hits_from_bam(canvas_ctx* ctx, const uint8_t* d_record
     }
     CANVAS_HIP_TRY(ctx, hipGetLastError());
     if (!h_info) return CANVAS_OK;                        // asynchronous: arrays and state are complete once the stream has been waited for
-    int32_t rc = canvas_pin_reserve(ctx, 128); if (rc) return rc;
-    long long* pin = (long long*)ctx->pin; unsigned* seqWord = (unsigned*)(pin + OBS_NSTATE);
-    const unsigned seq = cvx_mail_arm(ctx, seqWord);
-    hipLaunchKernelGGL(k_obs_mail, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)dState, pin, seqWord, seq);
-    CANVAS_HIP_TRY(ctx, hipGetLastError());
-    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    rc = cvx_mail_await(ctx, seqWord, seq, "canvas_hits_from_bam"); if (rc) return rc;
-    for (int i = 0; i < OBS_NSTATE; i++) h_info[i] = pin[i];
-    return CANVAS_OK;
+    return bam_mail_fetch(ctx, dState, OBS_NSTATE, h_info, "canvas_hits_from_bam");      // the state, through the pinned mailbox
 }

@@ -1,8 +1,8 @@
 // CanvasSNV's pileup: SNVReviewer.ProcessBamFile + ProcessReadBases (CanvasSNV/SNVReviewer.cs:172-271) over RAW BAM record bytes.
 //
 // The host (tools/canvas_snv_main.cpp) inflates BGZF blocks and finds where each record starts; nothing of a record is decoded there.  One lane takes one record:
-//   1. the fixed fields (block_size, refID, pos, l_read_name, mapq, n_cigar_op, flag, l_seq: bytes 0-23 of the record, byte loads — a record starts at any address),
-//      requested before anything is decided; shape checks against the record's and the chunk's length; the read filters (:200-203);
+//   1. the fixed fields and the shape checks against the record's and the chunk's length (bam_record.hpp: bam_rec_load, and bam_rec_holds_seq for the bases and
+//      qualities); the read filters (:200-203);
 //   2. k = first site with pos1 >= pos (the reference's scan pointer, :206, found by bisection: per read, needs no state from the read before as long as reads and
 //      sites are sorted); no such site or pos + 1000 < pos1[k] (:213) -> the lane is done.  That is where most lanes leave: 24 bytes + ~log2(nsites) site words;
 //   3. the survivors are compacted within the workgroup (LDS list), so that the waves that walk CIGARs are full and the others retire;
@@ -12,18 +12,12 @@
 // Expected to be bound by the latency of the dependent loads (offset -> fixed fields -> bisection steps), with HBM traffic limited to the sectors those 24 bytes touch:
 // an expectation from the access pattern, to be held against tools/snv_probe.py's figures, not a measurement.  A walking lane reads its CIGAR words
 // twice (the pre-pass that rejects a CIGAR outrunning l_seq, then the walk): nothing for short reads, a second pass over up to 65 535 words for a long read's CIGAR.
-// Every offset formed is checked first: a hostile chunk cannot make the kernel read outside [d_records, d_records + nbytes).  Loops are bounded by n_cigar_op
-// (16 bits) and by the sites inside one M run.  Statistics are reduced per workgroup (LDS) before they reach the five global words.
-#include "common.hpp"
+// Byte loads, offsets and their checks are bam_record.hpp's.  Loops are bounded by n_cigar_op (16 bits) and by the sites inside one M run.  Statistics are reduced per
+// workgroup (LDS) before they reach the five global words.
+#include "bam_record.hpp"
 
 #define SNV_BLOCK 256
 enum { SNV_SEEN = 0, SNV_PASSED = 1, SNV_WALKED = 2, SNV_STOPPED = 3, SNV_MALFORMED = 4, SNV_NINFO = 5 };
-
-__device__ __forceinline__ uint32_t snv_ld8(const uint8_t* __restrict__ p, uint64_t at) { return p[at]; }
-__device__ __forceinline__ uint32_t snv_ld16(const uint8_t* __restrict__ p, uint64_t at) { return (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8); }
-__device__ __forceinline__ uint32_t snv_ld32(const uint8_t* __restrict__ p, uint64_t at) {
-    return (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8) | ((uint32_t)p[at + 2] << 16) | ((uint32_t)p[at + 3] << 24);
-}
 
 struct SnvWork { uint64_t off; int32_t pos; int32_t k; uint32_t lname_ncig; int32_t lseq; };      // a record that has a site in reach
 
@@ -43,23 +37,16 @@ __global__ void __launch_bounds__(SNV_BLOCK) k_snv_count(const uint8_t* __restri
     bool seen = r < nrec, malformed = false, passed = false, survive = false;
     SnvWork w; w.off = 0; w.pos = 0; w.k = 0; w.lname_ncig = 0; w.lseq = 0;
     if (seen) {
-        const uint64_t off = offs[r];
-        if (off > nbytes || nbytes - off < 36) malformed = true;         // block_size + the 32 fixed bytes
-        else {
-            // every fixed field is requested before the first decision (a load under a condition is waited for where the condition ends)
-            const uint32_t bs = snv_ld32(rec, off), rid = snv_ld32(rec, off + 4), pos = snv_ld32(rec, off + 8), lname = snv_ld8(rec, off + 12), mapq = snv_ld8(rec, off + 13);
-            const uint32_t ncig = snv_ld16(rec, off + 16), flag = snv_ld16(rec, off + 18), lseq = snv_ld32(rec, off + 20);
-            const uint64_t need = 32ull + lname + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq;
-            if ((int32_t)bs < 32 || (uint64_t)bs > nbytes - off - 4 || (int32_t)lseq < 0 || need > (uint64_t)bs) malformed = true;
-            else if ((int32_t)rid == refId && (int32_t)pos >= 0 && !(flag & (0x100u | 0x4u | 0x400u)) && (int32_t)mapq > minMapq) {
-                passed = true;
-                const int32_t p = (int32_t)pos;
-                int lo = 0, hi = nsites;                                  // first site with pos1 >= p
-                while (lo < hi) { const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1); if (sitePos[mid] < p) lo = mid + 1; else hi = mid; }
-                if (lo < nsites && !((int64_t)p + 1000 < (int64_t)sitePos[lo])) {
-                    survive = true;
-                    w.off = off; w.pos = p; w.k = lo; w.lname_ncig = lname | (ncig << 8); w.lseq = (int32_t)lseq;
-                }
+        const uint64_t off = offs[r]; BamRec b;
+        if (!bam_rec_load(rec, nbytes, off, b) || !bam_rec_holds_seq(b)) malformed = true;
+        else if (b.refID == refId && b.pos >= 0 && !(b.flag & (0x100u | 0x4u | 0x400u)) && (int32_t)b.mapq > minMapq) {
+            passed = true;
+            const int32_t p = b.pos;
+            int lo = 0, hi = nsites;                                      // first site with pos1 >= p
+            while (lo < hi) { const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1); if (sitePos[mid] < p) lo = mid + 1; else hi = mid; }
+            if (lo < nsites && !((int64_t)p + 1000 < (int64_t)sitePos[lo])) {
+                survive = true;
+                w.off = off; w.pos = p; w.k = lo; w.lname_ncig = b.l_read_name | (b.n_cigar_op << 8); w.lseq = b.l_seq;
             }
         }
     }
@@ -81,11 +68,11 @@ __global__ void __launch_bounds__(SNV_BLOCK) k_snv_count(const uint8_t* __restri
     if (tid < (int)nwork) {
         const SnvWork W = work[tid];
         const uint32_t lname = W.lname_ncig & 0xFFu, ncig = W.lname_ncig >> 8;
-        const uint64_t cigAt = W.off + 36 + lname, seqAt = cigAt + 4ull * ncig, qualAt = seqAt + ((uint64_t)W.lseq + 1) / 2;       // all inside the record (checked above)
+        const uint64_t cigAt = bam_cigar_at(W.off, lname), seqAt = bam_seq_at(W.off, lname, ncig), qualAt = bam_qual_at(W.off, lname, ncig, W.lseq);       // all inside the record (checked above)
         // the read bases the walk would consume up to its end must exist: a record whose CIGAR outruns l_seq is rejected whole
         int64_t consumed = 0; bool stopped = false;
         for (uint32_t i = 0; i < ncig; i++) {
-            const uint32_t c = snv_ld32(rec, cigAt + 4ull * i), op = c & 15u;
+            const uint32_t c = bam_ld32(rec, cigAt + 4ull * i), op = c & 15u;
             if (op == 0u || op == 1u || op == 4u) consumed += (int64_t)(c >> 4);
             else if (op != 2u) { stopped = true; break; }
         }
@@ -95,15 +82,15 @@ __global__ void __launch_bounds__(SNV_BLOCK) k_snv_count(const uint8_t* __restri
             if (stopped) atomicAdd(&sStat[SNV_STOPPED], 1u);
             int64_t refPos = W.pos, baseIndex = 0; int s = W.k;
             for (uint32_t i = 0; i < ncig && s < nsites; i++) {
-                const uint32_t c = snv_ld32(rec, cigAt + 4ull * i), op = c & 15u; const int64_t len = (int64_t)(c >> 4);
+                const uint32_t c = bam_ld32(rec, cigAt + 4ull * i), op = c & 15u; const int64_t len = (int64_t)(c >> 4);
                 if (op == 0u) {
                     while (s < nsites && (int64_t)sitePos[s] - 1 < refPos) s++;
                     while (s < nsites) {
                         const int64_t x = (int64_t)sitePos[s] - 1;
                         if (x >= refPos + len) break;
                         const int64_t b = baseIndex + (x - refPos);             // < consumed <= l_seq
-                        if ((int32_t)snv_ld8(rec, qualAt + (uint64_t)b) >= minBaseQ) {
-                            const uint32_t two = snv_ld8(rec, seqAt + (uint64_t)(b >> 1)), nib = (b & 1) ? (two & 15u) : (two >> 4);
+                        if ((int32_t)bam_ld8(rec, qualAt + (uint64_t)b) >= minBaseQ) {
+                            const uint32_t two = bam_ld8(rec, seqAt + (uint64_t)(b >> 1)), nib = (b & 1) ? (two & 15u) : (two >> 4);
                             if (nib == (uint32_t)siteRef[s]) atomicAdd(&refCnt[s], 1);
                             if (nib == (uint32_t)siteAlt[s]) atomicAdd(&altCnt[s], 1);
                         }
@@ -118,14 +105,6 @@ __global__ void __launch_bounds__(SNV_BLOCK) k_snv_count(const uint8_t* __restri
     }
     __syncthreads();
     if (tid < SNV_NINFO && sStat[tid]) atomicAdd(&info[tid], (unsigned long long)sStat[tid]);
-}
-
-// the call's statistics travel through the context's pinned mailbox (common.hpp: payload, system fence, sequence word last)
-__global__ void k_snv_mail(const unsigned long long* __restrict__ info, long long* pin, unsigned* seqWord, unsigned seq) {
-    if (threadIdx.x < SNV_NINFO) pin[threadIdx.x] = (long long)info[threadIdx.x];
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) cvx_mail_publish(seqWord, seq);
 }
 
 extern "C" int32_t canvas_snv_count(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nbytes, const uint64_t* d_record_offsets, int64_t nrecords, int32_t ref_id, int32_t min_mapq,
@@ -148,13 +127,5 @@ extern "C" int32_t canvas_snv_count(canvas_ctx* ctx, const uint8_t* d_records, u
     }
     CANVAS_HIP_TRY(ctx, hipGetLastError());
     if (!h_info) return CANVAS_OK;                        // asynchronous: the counters are complete once the stream has been waited for
-    rc = canvas_pin_reserve(ctx, 64); if (rc) return rc;
-    long long* pin = (long long*)ctx->pin; unsigned* seqWord = (unsigned*)(pin + 6);
-    const unsigned seq = cvx_mail_arm(ctx, seqWord);
-    hipLaunchKernelGGL(k_snv_mail, dim3(1), dim3(64), 0, ctx->stream, dInfo, pin, seqWord, seq);
-    CANVAS_HIP_TRY(ctx, hipGetLastError());
-    CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    rc = cvx_mail_await(ctx, seqWord, seq, "canvas_snv_count"); if (rc) return rc;
-    for (int i = 0; i < SNV_NINFO; i++) h_info[i] = pin[i];
-    return CANVAS_OK;
+    return bam_mail_fetch(ctx, dInfo, SNV_NINFO, h_info, "canvas_snv_count");      // the call's statistics, through the pinned mailbox
 }

@@ -116,6 +116,8 @@ struct BamFixed {
         l_seq = (int32_t)le32(r + 16); next_refID = (int32_t)le32(r + 20); next_pos = (int32_t)le32(r + 24); tlen = (int32_t)le32(r + 28);
         return true;
     }
+    // the fixed fields, the name and the CIGAR lie inside block_size
+    bool name_and_cigar_fit(int32_t block_size) const { return 32 + (int64_t)l_read_name + 4 * (int64_t)n_cigar <= block_size; }
 };
 // the next record of the stream into rec, its fixed fields into a.  false: the stream's end, or, with z.bad set, a damaged block or a record whose block_size does not
 // hold its fixed fields, name and CIGAR
@@ -123,6 +125,6 @@ static bool read_bam_record(Bgzf& z, std::vector<uint8_t>& rec, BamFixed& a) {
     int32_t bs; if (!z.read(&bs, 4)) return false;
     rec.resize((size_t)std::max(bs, 0));
     if (bs >= 32 && !z.read(rec.data(), bs)) return false;
-    if (!a.decode(rec.data(), bs) || 32 + (int64_t)a.l_read_name + 4 * (int64_t)a.n_cigar > bs) z.bad = true;
+    if (!a.decode(rec.data(), bs) || !a.name_and_cigar_fit(bs)) z.bad = true;
     return !z.bad;
 }

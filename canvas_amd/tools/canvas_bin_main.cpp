@@ -61,6 +61,21 @@ static int open_bam_at(const std::string& bam, const std::string& chrom, BamAt& 
 // the read loop stopped at a BGZF block that does not parse or inflate, or at a record shorter than its fixed fields: nothing is written
 static int damaged_bam(const std::string& bam) { fprintf(stderr, "CanvasBin: %s is truncated or damaged: a BGZF block or an alignment record of it cannot be read\n", bam.c_str()); return 1; }
 
+// the read filters of LoadObservedAlignmentsBAM's loop (CanvasBin.cs:239-262), the ones in front of its comparison of reference ids.  r: the record behind its
+// block_size word; a: its fixed fields, with name and CIGAR inside block_size (name_and_cigar_fit)
+static bool passes_read_filters(const uint8_t* r, const BamFixed& a, bool pairedEnd) {
+    if (a.flag & 0x4) return false;                        // !IsMapped
+    if (a.flag & 0x200) return false;                      // IsFailedQC
+    if (a.flag & 0x400) return false;                      // IsDuplicate
+    if (a.flag & 0x10) return false;                       // IsReverseStrand
+    if (a.flag & 0x900) return false;                      // !IsMainAlignment
+    if (a.n_cigar == 0) return false;
+    const uint32_t c0 = le32(r + 32 + a.l_read_name);
+    if ((c0 & 0xF) != 0 || (c0 >> 4) < 35) return false;   // must start with 35 bases of 'M'
+    if (pairedEnd && !(a.flag & 0x2)) return false;        // IsProperPair
+    return true;
+}
+
 // LoadObservedAlignmentsBAM (CanvasBin.cs:207-275)
 static int load_bam(const std::string& bam, bool pairedEnd, const std::string& chrom, int mode, std::vector<uint8_t>& hits, std::vector<int16_t>& frag) {
     BamAt b; if (int rc = open_bam_at(bam, chrom, b)) return rc;
@@ -71,16 +86,8 @@ static int load_bam(const std::string& bam, bool pairedEnd, const std::string& c
     std::vector<uint8_t> rec;
     for (BamFixed a; read_bam_record(z, rec, a);) {
         readCount++;
-        const int32_t refID = a.refID, pos = a.pos, tlen = a.tlen; const uint16_t flag = a.flag;
-        if (flag & 0x4) continue;                          // !IsMapped
-        if (flag & 0x200) continue;                        // IsFailedQC
-        if (flag & 0x400) continue;                        // IsDuplicate
-        if (flag & 0x10) continue;                         // IsReverseStrand
-        if (flag & 0x900) continue;                        // !IsMainAlignment
-        if (a.n_cigar == 0) continue;
-        uint32_t c0; memcpy(&c0, &rec[32 + a.l_read_name], 4);
-        if ((c0 & 0xF) != 0 || (c0 >> 4) < 35) continue;   // must start with 35 bases of 'M'
-        if (pairedEnd && !(flag & 0x2)) continue;          // IsProperPair
+        const int32_t refID = a.refID, pos = a.pos, tlen = a.tlen;
+        if (!passes_read_filters(rec.data(), a, pairedEnd)) continue;
         if (refID != desired) break;
         if (refID == -1) continue;
         kept++;
@@ -112,11 +119,9 @@ static int load_bam_device(const std::string& bam, const BamAt& b, bool pairedEn
             return 0;
         },
         [&](const uint8_t* r, const BamFixed& a, int32_t bs) -> BamFrame {
-            if (32 + (int64_t)a.l_read_name + 4 * (int64_t)a.n_cigar > bs) return BamFrame::Fail;          // read_bam_record's check
+            if (!a.name_and_cigar_fit(bs)) return BamFrame::Fail;                                           // read_bam_record's check
             if (a.refID == desired && mode != CANVAS_MODE_GC_CONTENT_WEIGHTED) return BamFrame::Take;       // cannot stop, and its position does not matter
-            if ((a.flag & (0x4 | 0x200 | 0x400 | 0x10 | 0x900)) || a.n_cigar == 0) return BamFrame::Take;
-            const uint32_t c0 = le32(r + 32 + a.l_read_name);
-            if ((c0 & 0xF) != 0 || (c0 >> 4) < 35 || (pairedEnd && !(a.flag & 0x2))) return BamFrame::Take;
+            if (!passes_read_filters(r, a, pairedEnd)) return BamFrame::Take;
             if (a.refID != desired) return BamFrame::TakeAndStop;
             if (a.pos < lastKept) return BamFrame::Fail;
             lastKept = a.pos; return BamFrame::Take;
@@ -248,7 +253,7 @@ static int bin_fragments_device(const std::string& bam, const std::string& chrom
             return 0;
         },
         [&](const uint8_t*, const BamFixed& a, int32_t bs) -> BamFrame {
-            if (32 + (int64_t)a.l_read_name + 4 * (int64_t)a.n_cigar > bs) return BamFrame::Fail;          // read_bam_record's check
+            if (!a.name_and_cigar_fit(bs)) return BamFrame::Fail;                                           // read_bam_record's check
             return a.refID != desired ? BamFrame::TakeAndStop : BamFrame::Take;                            // (:221: every record of another reference ends the chromosome)
         },
         [&](void* dRec, uint64_t used, void* dOff, int64_t nrec) -> int32_t {

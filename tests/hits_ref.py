@@ -74,6 +74,25 @@ def chunk_of(reads, pad=0, extra_offsets=()):
     return buf, np.array(offs, np.int64), at
 
 
+def damaged_records(rd):
+    """[(what, record, last_only)]: records whose fixed fields do not describe bytes of the chunk, built with the caller's record builder `rd(pos, **fields)`.
+    last_only: damaged only as the LAST record of a chunk without padding (in front of other records its block_size stays inside the chunk)."""
+    past = rd(9)
+    past["block_size"] = len(encode_record(past)) - 4 + 1
+    return [
+        ("block_size 31", rd(9, block_size=31), False),
+        ("block_size past the chunk", past, True),
+        ("name and CIGAR past block_size", rd(9, n_cigar=60000), False),
+        ("name past block_size", rd(9, l_read_name=255, cigar=[], seq=""), False),
+        ("negative block_size", rd(9, block_size=-8), False),
+    ]
+
+
+def stray_offsets(nbytes):
+    """[(what, offset)]: offsets that leave no 36 bytes inside a chunk of `nbytes` (negative ones count from its end, as in chunk_of)"""
+    return [("nbytes - 20", -20), ("nbytes - 35", -35), ("nbytes", nbytes), ("nbytes + 1", nbytes + 1), ("2^63 - 1", 2 ** 63 - 1)]
+
+
 def new_state():
     return dict(stopped=0, seen=0, kept=0, out_of_range=0, malformed=0, last_pos=0)
 

@@ -347,18 +347,7 @@ def test_malformed(cv):
     good = F.pair("g1", 3, 40) + [F.rd(50, "g2", 0x63, 30, 90, 60)]
     good.sort(key=lambda r: r["pos"])
     stand_in = dict(malformed=True)
-    cases = {
-        "block_size 31": F.rd(9, block_size=31),
-        "block_size past the chunk": None,
-        "name and CIGAR past block_size": F.rd(9, n_cigar=60000),
-        "name past block_size": F.rd(9, l_read_name=255, cigar=[], seq=""),
-        "negative block_size": F.rd(9, block_size=-8),
-    }
-    for what, bad in cases.items():
-        past_chunk = bad is None
-        if past_chunk:
-            bad = F.rd(9)
-            bad["block_size"] = len(H.encode_record(bad)) - 4 + 1
+    for what, bad, past_chunk in H.damaged_records(F.rd):
         c, info, est = check(cv, [good + [bad]], bins, ref_chunks=[good + [stand_in]], what=what)
         assert info[4] == 1 and info[1] == 4 and info[3] == 2
         if past_chunk:
@@ -366,7 +355,7 @@ def test_malformed(cv):
         c, info, est = check(cv, [[bad] + good], bins, ref_chunks=[[stand_in] + good], what=what + " first")
         assert info[4] == 1 and info[3] == 2
     buf_len = sum(len(H.encode_record(r)) for r in good)
-    for where, off in (("nbytes - 20", -20), ("nbytes - 35", -35), ("nbytes", buf_len), ("nbytes + 1", buf_len + 1), ("2^63 - 1", 2 ** 63 - 1)):
+    for where, off in H.stray_offsets(buf_len):
         for idx in (0, 2, 3):
             ref = list(good)
             ref.insert(idx, stand_in)

@@ -282,19 +282,8 @@ def test_malformed(cv):
     """every damaged record is the LAST bytes of a buffer of exactly the records' size (pad 0): reading past a bound would leave it"""
     good = [rd(3, tlen=10), rd(4, tlen=20), rd(4, tlen=30)]
     stand_in = dict(malformed=True)
-    cases = {
-        "block_size 31": rd(9, block_size=31),
-        "block_size past the chunk": None,
-        "name and CIGAR past block_size": rd(9, n_cigar=60000),
-        "name past block_size": rd(9, l_read_name=255, cigar=[]),
-        "negative block_size": rd(9, block_size=-8),
-    }
     for mode in (H.MODE_TDR, H.MODE_GCW):
-        for what, bad in cases.items():
-            past_chunk = bad is None
-            if past_chunk:
-                bad = rd(9)
-                bad["block_size"] = len(H.encode_record(bad)) - 4 + 1
+        for what, bad, past_chunk in H.damaged_records(rd):
             _, _, info = check(cv, [good + [bad]], ref_chunks=[good + [stand_in]], mode=mode, what=what)
             assert info[4] == 1 and info[2] == 3 and info[1] == 4
             if past_chunk:                         # (in front of other records its block_size stays inside the chunk)
@@ -304,7 +293,7 @@ def test_malformed(cv):
             assert info[4] == 1 and info[2] == 3
         # an offset 20 bytes in front of the end, one exactly at the end, one behind it: no 36 bytes are left
         buf_len = sum(len(H.encode_record(r)) for r in good)
-        for where, off in (("nbytes - 20", -20), ("nbytes - 35", -35), ("nbytes", buf_len), ("nbytes + 1", buf_len + 1), ("2^63 - 1", 2 ** 63 - 1)):
+        for where, off in H.stray_offsets(buf_len):
             for idx in (0, 2, 3):
                 ref = list(good)
                 ref.insert(idx, stand_in)
