@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "canvas_segment_tables", "canvas_call_diploid_ids",
     "canvas_partition_states_cbs", "canvas_partition_states_breakpoints", "canvas_reference_copy_numbers", "canvas_call_somatic_ids",
     "canvas_hits_from_bam", "canvas_fragments_from_bam",
+    "canvas_bgzf_inflate", "canvas_bgzf_scan",
 ]
 
 
@@ -129,6 +130,30 @@ BACKBONE_PROBE_UNTOUCHED = 0x7FF8C0DEC0DEC0DE     # bits of the carries canvas_h
 
 class CanvasError(RuntimeError):
     pass
+
+
+# canvas_bgzf_block (24 bytes) and the block statuses of canvas_bgzf_inflate
+BGZF_BLOCK = np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"), ("src_bytes", "<u4"), ("out_bytes", "<u4")])
+INFLATE_OK, INFLATE_DESCRIPTOR, INFLATE_HEADER, INFLATE_INPUT, INFLATE_OVERRUN, INFLATE_SHORT, INFLATE_DISTANCE, INFLATE_CODE = range(8)
+BGZF_SCAN_LIMIT, BGZF_SCAN_END, BGZF_SCAN_DAMAGED = 0, 1, 2
+
+
+def bgzf_scan(buf, at=0, max_out_bytes=None):
+    """The descriptors of the consecutive BGZF blocks of `buf` (bytes-like or a uint8 array, host memory) from byte `at` on, until their inflated sizes reach
+    max_out_bytes (None: no bound).  Returns (blocks, info): a numpy array of BGZF_BLOCK, ready for Canvas.bgzf_inflate with `buf` as the source, and info[4] = blocks,
+    the file offset the walk stopped at, their inflated bytes, and why it stopped (BGZF_SCAN_LIMIT / _END / _DAMAGED).  Host code: no context, no device call."""
+    lib = load_library()
+    a = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    if not 0 <= int(at) <= a.size:
+        raise CanvasError("bgzf_scan: `at` lies outside the buffer")
+    cap = (a.size - int(at)) // 26 + 1            # the walk takes a block of 26 bytes (18 of header, no data, 8 of trailer)
+    blocks = np.zeros(cap, BGZF_BLOCK)
+    info = np.zeros(4, np.int64)
+    limit = (1 << 64) - 1 if max_out_bytes is None else int(max_out_bytes)
+    rc = lib.canvas_bgzf_scan(C.c_void_p(a.ctypes.data), C.c_uint64(a.size), C.c_uint64(int(at)), C.c_uint64(limit), _np_ptr(blocks), C.c_int64(cap), _np_ptr(info))
+    if rc != 0:
+        raise CanvasError("canvas_bgzf_scan failed (%d)" % rc)
+    return blocks[:int(info[0])].copy(), info
 
 
 _lib = None
@@ -329,6 +354,7 @@ class Canvas:
 
     def synchronize(self):
         self._check(self.lib.canvas_synchronize(self.ctx))
+        self.__dict__.pop("_queued_inputs", None)                 # (bgzf_inflate: what queued calls read has been read)
 
     def upload_genome_begin(self, lens, h_bases, d_bases, h_mask, d_mask, h_hits, d_hits):
         """queue the per-chromosome upload of host arrays (pinned torch tensors / numpy arrays; None = already resident) on the context's copy stream;
@@ -713,6 +739,36 @@ class Canvas:
                                               C.c_void_p(site_alt.data_ptr()), ns, C.c_void_p(ref_counts.data_ptr()), C.c_void_p(alt_counts.data_ptr()),
                                               _np_ptr(info) if want_info else None))
         return ref_counts, alt_counts, info
+
+    def bgzf_inflate(self, src, blocks, out=None, status=None, want_info=True):
+        """BGZF blocks inflated on the device.  src: uint8 tensor holding the compressed bytes; blocks: the descriptors as a numpy array of BGZF_BLOCK (bgzf_scan's), or a
+        device tensor of n x 24 uint8 (any dense shape of 24 n bytes).  out (uint8) is created to hold the farthest destination range when None, status (int32 per
+        block) likewise.  Returns (out, status, info): info[4] = blocks, failed blocks, bytes written by good blocks, first failed block or -1; want_info=False only
+        queues the work and returns None for it.  status[i] is 0 exactly where zlib's raw inflate accepts the block for its recorded size (INFLATE_* otherwise)."""
+        torch = self.torch
+        if isinstance(blocks, np.ndarray):
+            host = np.ascontiguousarray(blocks.astype(BGZF_BLOCK, copy=False))
+            n = int(host.size)
+            if out is None:
+                out = torch.empty(max(int((host["dst_offset"] + host["out_bytes"]).max()) if n else 0, 1), dtype=torch.uint8, device=self.device)
+            blocks = torch.from_numpy(host.view(np.uint8).reshape(-1).copy()).to(self.device)
+        else:
+            assert blocks.dtype == torch.uint8 and blocks.numel() % 24 == 0, "bgzf_inflate: blocks is n x 24 bytes"
+            n = int(blocks.numel()) // 24
+            assert out is not None, "bgzf_inflate: descriptors on the device need `out`"
+        if status is None:
+            status = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        assert src.dtype == torch.uint8 and out.dtype == torch.uint8 and status.dtype == torch.int32 and status.numel() >= n
+        for t in (src, blocks, out, status):
+            assert t.is_contiguous() and (t.numel() == 0 or t.device == self.device), "bgzf_inflate: tensors must be dense and on the context's device"
+        torch.cuda.current_stream(self.device).synchronize()      # torch fills and copies on its own stream; the kernel runs on the context's
+        info = np.zeros(4, np.int64) if want_info else None
+        self._check(self.lib.canvas_bgzf_inflate(self.ctx, C.c_void_p(src.data_ptr()), C.c_uint64(int(src.numel())), C.c_void_p(blocks.data_ptr()), C.c_int64(n),
+                                                 C.c_void_p(out.data_ptr()), C.c_uint64(int(out.numel())), C.c_void_p(status.data_ptr()),
+                                                 _np_ptr(info) if want_info else None))
+        if not want_info:
+            self.__dict__.setdefault("_queued_inputs", []).append((src, blocks))      # every queued call reads its own until synchronize() has waited for the stream
+        return out, status, info
 
     def hits_from_bam(self, records, offsets, ref_id, length, mode=MODE_TDR, paired_end=False, hits=None, frag=None, state=None, nbytes=None, want_info=True):
         """LoadObservedAlignmentsBAM (CanvasBin.cs:207-275) over one chunk of raw BAM records (the chunk format of snv_count: uint8 record bytes, int64 offsets).

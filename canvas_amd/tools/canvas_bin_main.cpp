@@ -134,8 +134,8 @@ static int load_bam_device(const std::string& bam, const BamAt& b, bool pairedEn
     int64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (rc == 0) TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, st, dState->p, 64));
     { const double tEnd = Phases::now(), rest = std::max(0.0, (tEnd - tLoop0) - loop.tInflate - loop.tDevice); ph.v.push_back({"inflate", tLoop0 + loop.tInflate + rest}); ph.v.push_back({"device_bam", tEnd}); }
-    if (getenv("CANVAS_TOOL_TIMING")) fprintf(stderr, "[bam] {\"records\": %lld, \"chunks\": %lld, \"record_bytes\": %lld, \"kernel_ms\": %.4f, \"inflate_s\": %.4f, \"device_wait_s\": %.4f, \"threads\": %d, \"host_path\": %d}\n",
-                                              loop.records, loop.chunks, loop.bytesUp, loop.kernelMs, loop.tInflate, loop.tDevice, io_threads(), rc != 0 || st[4] != 0 ? 1 : 0);
+    if (getenv("CANVAS_TOOL_TIMING")) fprintf(stderr, "[bam] {\"records\": %lld, \"chunks\": %lld, \"record_bytes\": %lld, \"kernel_ms\": %.4f, \"inflate_s\": %.4f, \"device_wait_s\": %.4f, \"threads\": %d, \"host_path\": %d%s}\n",
+                                              loop.records, loop.chunks, loop.bytesUp, loop.kernelMs, loop.tInflate, loop.tDevice, io_threads(), rc != 0 || st[4] != 0 ? 1 : 0, loop.timing_tail().c_str());
     if (rc != 0 || st[4] != 0) return 2;          // (a record the kernels call malformed passed the framing: not expected; load_bam decides)
     printf("Kept %ld of %ld total reads\n", (long)st[2], (long)st[1]);
     return 0;
@@ -279,9 +279,9 @@ static int bin_fragments_device(const std::string& bam, const std::string& chrom
     if (rc == 0) { TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, st, dState->p, 128)); if (nbins > 0) TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, counts.data(), dCount->p, nbins * 4)); }
     const bool handBack = rc != 0 || st[4] != 0 || st[6] != 0;
     if (getenv("CANVAS_TOOL_TIMING")) fprintf(stderr, "[frag] {\"chrom\": \"%s\", \"records\": %lld, \"chunks\": %lld, \"record_bytes\": %lld, \"kernel_ms\": %.4f, \"inflate_s\": %.4f, \"device_wait_s\": %.4f, \"threads\": %d, "
-                                              "\"carried_max\": %lld, \"carried_mean\": %.1f, \"longest_group\": %lld, \"carry_grown\": %lld, \"host_path\": %d}\n",
+                                              "\"carried_max\": %lld, \"carried_mean\": %.1f, \"longest_group\": %lld, \"carry_grown\": %lld, \"host_path\": %d%s}\n",
                                               chrom.c_str(), loop.records, loop.chunks, loop.bytesUp, loop.kernelMs, loop.tInflate, loop.tDevice, io_threads(), maxCarried,
-                                              loop.chunks ? (double)sumCarried / (double)loop.chunks : 0.0, longest, grown, handBack ? 1 : 0);
+                                              loop.chunks ? (double)sumCarried / (double)loop.chunks : 0.0, longest, grown, handBack ? 1 : 0, loop.timing_tail().c_str());
     if (handBack) return 2;
     for (int64_t i = 0; i < nbins; i++) bins[(size_t)i].count = (float)counts[(size_t)i];
     usableFragmentCount = (long)st[3];

@@ -168,7 +168,7 @@ int main(int argc, char** argv) {
     // (inflation and the device overlap: `inflate` is the time the main thread spent inflating and framing, `device` the time it spent queueing work and waiting for the
     // device — what of the device's work did not hide behind inflation.  Together they are the loop's wall time.)
     { const double tEnd = Phases::now(), rest = std::max(0.0, (tEnd - tLoop0) - tInflate - tDevice); ph.v.push_back({"inflate", tLoop0 + tInflate + rest}); ph.v.push_back({"device", tEnd}); }
-    if (getenv("CANVAS_TOOL_TIMING")) fprintf(stderr, "[snv] {\"records\": %lld, \"chunks\": %lld, \"record_bytes\": %lld, \"kernel_ms\": %.4f, \"inflate_s\": %.4f, \"device_wait_s\": %.4f, \"threads\": %d}\n", overall, chunks, bytesUp, kernelMs, tInflate, tDevice, io_threads());
+    if (getenv("CANVAS_TOOL_TIMING")) fprintf(stderr, "[snv] {\"records\": %lld, \"chunks\": %lld, \"record_bytes\": %lld, \"kernel_ms\": %.4f, \"inflate_s\": %.4f, \"device_wait_s\": %.4f, \"threads\": %d%s}\n", overall, chunks, bytesUp, kernelMs, tInflate, tDevice, io_threads(), loop.timing_tail().c_str());
 
     // ---- WriteResults (:276-316), filtered by IsVariantSite (:74-81)
     std::vector<int32_t> keep;

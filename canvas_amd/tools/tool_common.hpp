@@ -282,12 +282,19 @@ struct ExitStamp { const char* what; explicit ExitStamp(const char* w) : what(w)
 //   setup(ctx)                        once, when the staging buffers exist and before the first chunk is framed (the tool's own device arrays); 0 or the exit code
 //   frame(r, fx, block_size)          one record: r = its 32 fixed bytes (the whole record lies behind them), fx = the same decoded (block_size >= 32 is checked)
 //   consume(dRec, used, dOff, nrec)   queue the device work of a chunk of nrec taken records (nrec > 0); the library's return code
+// CANVAS_TOOL_DEVICE_INFLATE=1 (configuration of the executables, like the chunk size; off by default): the chunk's compressed bytes and a table of its blocks go up
+// instead, canvas_bgzf_inflate writes the record bytes straight into the buffer consume reads, and they are copied DOWN into the staging buffer for the framing, which
+// is the same code.  No host thread inflates and no inflated chunk is uploaded; only the carried tail (less than one record) goes up from the host copy.  A block the
+// device refuses is a block that "does not inflate to its recorded size".  The chunks are not overlapped in this form.
 enum class BamFrame { Take, Skip, TakeAndStop, Stop, Fail };      // TakeAndStop / Stop: nothing behind this record is read; Fail: the tool has said why (unless quiet)
 struct BamChunkLoop {
     const char* tool; std::string bam; uint64_t voff = 0; size_t chunkBytes = (size_t)32 << 20;
     bool quiet = false;               // no message for input the loop itself refuses (the caller has an answer of its own for such a file)
     const char* profile = nullptr;    // with CANVAS_TOOL_TIMING: the library scope whose device time goes to kernelMs
     double tInflate = 0, tDevice = 0, kernelMs = 0; long long records = 0, chunks = 0, bytesUp = 0;
+    bool deviceInflate = false; double inflateKernelMs = 0;      // CANVAS_TOOL_DEVICE_INFLATE; with CANVAS_TOOL_TIMING the device time of canvas_bgzf_inflate
+    // the end of the tool's timing line
+    std::string timing_tail() const { char b[96]; snprintf(b, sizeof b, ", \"device_inflate\": %d, \"inflate_kernel_ms\": %.4f", deviceInflate ? 1 : 0, inflateKernelMs); return b; }
     void chunk_bytes_from(const char* envName) { if (const char* e = getenv(envName)) { const long long v = atoll(e); if (v >= 65536) chunkBytes = (size_t)v; } }
     // 0: the file was read to its end or to the record that stopped it, everything is queued and waited for.  1: the device or the runtime failed (message printed).
     // 2: the input was refused (message printed unless quiet, or by frame).  Any other value: what setup returned.
@@ -322,6 +329,9 @@ struct BamChunkLoop {
         if (!dRec0.p || !dRec1.p || !dOff0.p || !dOff1.p) { fprintf(stderr, "%s: device allocation failed: %s\n", tool, canvas_last_error(ctx)); return 1; }
         void* dRec[2] = {dRec0.p, dRec1.p}; void* dOff[2] = {dOff0.p, dOff1.p};
         if (int rc = setup(ctx)) return rc;
+        { const char* e = getenv("CANVAS_TOOL_DEVICE_INFLATE"); deviceInflate = e && atoi(e) == 1; }
+        // device inflation: the chunk's stretch of the file, its block table and the statuses, grown as chunks need them (a level-0 block is larger than what it holds)
+        std::unique_ptr<Dev> dComp, dBlk, dStatus; size_t compCap = 0, blkCap = 0; std::vector<canvas_bgzf_block> table;
         tDevice += Phases::now() - tLoop0;
 
         size_t carry = 0; int cur = 0; bool done = false; std::vector<size_t> pre;
@@ -332,6 +342,27 @@ struct BamChunkLoop {
             pre.assign(blocks.size() + 1, carry);
             for (size_t i = 0; i < blocks.size(); i++) pre[i + 1] = pre[i] + blocks[i].isize;
             std::atomic<bool> ok(true);
+            if (deviceInflate) {
+                table.clear();                                                   // (a block of ISIZE 0 is not inflated here either)
+                const size_t compAt = blocks.empty() ? 0 : blocks.front().in, compBytes = blocks.empty() ? 0 : blocks.back().in + blocks.back().clen - compAt;
+                for (size_t i = 0; i < blocks.size(); i++) if (blocks[i].isize) table.push_back({(uint64_t)(blocks[i].in - compAt), (uint64_t)pre[i], (uint32_t)blocks[i].clen, blocks[i].isize});
+                if (!table.empty()) {
+                    if (!dComp || compBytes > compCap || table.size() > blkCap) {      // (!dComp: a first chunk whose blocks hold no deflate data at all)
+                        TOOL_TRY(ctx, canvas_synchronize(ctx));                  // chunk k - 1 may still read the buffers that go
+                        if (!dComp || compBytes > compCap) { compCap = compBytes + compBytes / 4; dComp.reset(); dComp.reset(new Dev(ctx, (int64_t)compCap)); }
+                        if (table.size() > blkCap) { blkCap = 2 * table.size(); dBlk.reset(); dStatus.reset(); dBlk.reset(new Dev(ctx, (int64_t)(blkCap * sizeof(canvas_bgzf_block)))); dStatus.reset(new Dev(ctx, (int64_t)(blkCap * 4))); }
+                        if (!dComp->p || !dBlk->p || !dStatus->p) { fprintf(stderr, "%s: device allocation failed: %s\n", tool, canvas_last_error(ctx)); return 1; }
+                    }
+                    TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dComp->p, F + compAt, (int64_t)compBytes));
+                    TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dBlk->p, table.data(), (int64_t)(table.size() * sizeof(canvas_bgzf_block))));
+                    if (carry) TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dRec[cur], buf, (int64_t)carry));
+                    int64_t info[4];
+                    TOOL_TRY(ctx, canvas_bgzf_inflate(ctx, dComp->as<uint8_t>(), compBytes, dBlk->as<canvas_bgzf_block>(), (int64_t)table.size(), (uint8_t*)dRec[cur], cap,
+                                                      dStatus->as<int32_t>(), info));
+                    if (info[1] != 0) ok = false;
+                    else TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, buf + carry, (uint8_t*)dRec[cur] + carry, (int64_t)total));
+                }
+            } else
             parallel_for((int64_t)blocks.size(), [&](int64_t i) {
                 const BgzfBlock& b = blocks[(size_t)i];
                 if (b.isize && !inflate_raw(F + b.in, b.clen, buf + pre[(size_t)i], b.isize)) ok = false;
@@ -361,7 +392,8 @@ struct BamChunkLoop {
             TOOL_TRY(ctx, canvas_synchronize(ctx));                            // chunk k - 1 ran while this one was inflated
             if (carry) memcpy(hRec[cur ^ 1].get(), buf + at, carry);          // only now: the other buffer was the source of chunk k - 1's upload until the wait above
             if (nrec > 0) {
-                TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dRec[cur], buf, (int64_t)used)); TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dOff[cur], offs, nrec * 8));
+                if (!deviceInflate) TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dRec[cur], buf, (int64_t)used));      // (inflated on the device: the bytes are there)
+                TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dOff[cur], offs, nrec * 8));
                 TOOL_TRY(ctx, consume(dRec[cur], (uint64_t)used, dOff[cur], nrec));
                 records += nrec; chunks++; bytesUp += (long long)used;
             }
@@ -375,6 +407,7 @@ struct BamChunkLoop {
         const double t3 = Phases::now();
         TOOL_TRY(ctx, canvas_synchronize(ctx));
         if (timing && profile) { int32_t launches = 0; (void)canvas_profile_get(ctx, profile, &kernelMs, &launches, 1); }
+        if (timing && deviceInflate) { int32_t launches = 0; (void)canvas_profile_get(ctx, "bgzf_inflate", &inflateKernelMs, &launches, 1); }
         tDevice += Phases::now() - t3;
         return 0;
     }

@@ -133,6 +133,12 @@ namespace CanvasHipInterop
         // library's own list of open read names (CANVAS_ERR_CAPACITY: info[8] bytes are needed; enlarge it, keep its contents, call again); info = long[16], the call waits
         [DllImport(Lib)] public static extern int canvas_fragments_from_bam(IntPtr ctx, IntPtr dRecords, ulong nbytes, IntPtr dRecordOffsets, long nrecords, int refId, IntPtr dBinStart,
             IntPtr dBinStop, long nbins, int qualityThreshold, IntPtr dCount, IntPtr dCarry, ulong carryCapacity, IntPtr dState, long[] info);
+        // BGZF: the blocks of a BAM inflated on the device, one BgzfBlock (24 bytes) per block; dStatus = int per block (0, or a CANVAS_INFLATE_* code: 1 descriptor, 2 header, 3 input, 4 overrun,
+        // 5 short, 6 distance, 7 code); info = long[4] (blocks, failed, bytes of the good blocks, first failed or -1) or null (queue only).  The CRC32 is not checked
+        [StructLayout(LayoutKind.Sequential)] public struct BgzfBlock { public ulong SrcOffset; public ulong DstOffset; public uint SrcBytes; public uint OutBytes; }
+        [DllImport(Lib)] public static extern int canvas_bgzf_inflate(IntPtr ctx, IntPtr dSrc, ulong srcNbytes, IntPtr dBlocks, long nblocks, IntPtr dDst, ulong dstNbytes, IntPtr dStatus, long[] info);
+        // the block table of a BGZF buffer in host memory from file offset `at` (no context): info = long[4] (blocks, next offset, inflated bytes, reason: 0 limit, 1 end, 2 damaged)
+        [DllImport(Lib)] public static extern int canvas_bgzf_scan(byte[] hBytes, ulong nbytes, ulong at, ulong maxOutBytes, [Out] BgzfBlock[] hBlocks, long capacity, long[] info);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d_async(IntPtr ctx, IntPtr dDst, IntPtr hSrc, long bytes);
         // Tools/FlagUniqueKmers (KmerChecker): unique-35-mer masks of all contigs at once (stats = long[8] or null), and the letter case of kmer.fa from a mask
         [DllImport(Lib)] public static extern int canvas_flag_unique_kmers(IntPtr ctx, int nchr, IntPtr[] dBases, long[] len, IntPtr[] dMask, long maxTableBytes, long[] stats);

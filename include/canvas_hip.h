@@ -942,6 +942,38 @@ int32_t canvas_call_somatic_ids(canvas_ctx* ctx, int64_t nbins, int32_t nchr, co
                                 int32_t* h_seg_ci4 /* 4*cap_seg */, float* d_count_f32, int32_t* h_seg_ref_cn /* cap_seg */, const canvas_somatic_call_out* out,
                                 canvas_somatic_call_scalars* h_scalars, canvas_somatic_result* h_fit);
 
+/* ---- BGZF: the blocks of a BAM inflated on the device (what the three readers above take as d_records) ------------------------------------------------- */
+/* A BGZF block is an independent raw-deflate stream of at most 64 KiB in and out.  Block i of d_blocks is the stream d_src[src_offset, src_offset + src_bytes) and has to
+ * give exactly out_bytes bytes at d_dst[dst_offset, ...): one wave per block, profile scope "bgzf_inflate".
+ *   d_status[i] 0, or why the block failed (CANVAS_INFLATE_*).  0 if and only if zlib's raw inflate (inflateInit2(-15), Z_FINISH) reaches Z_STREAM_END with exactly
+ *               out_bytes written, and the bytes are then zlib's.  Unused input behind the final deflate block is accepted; the CRC32 of the BGZF trailer is NOT checked.
+ *   ranges      src_bytes and out_bytes are at most 65536; a larger one, or a range outside src_nbytes / dst_nbytes, is CANVAS_INFLATE_DESCRIPTOR for that block and
+ *               nothing of it is read or written.  A block reads no byte outside its source range and writes none outside [dst_offset, dst_offset + out_bytes); the
+ *               destination bytes of a FAILED block are unspecified (this build leaves them alone).  Destination ranges of different blocks must not overlap.
+ *   h_info      NULL: the call only queues work on the context's stream.  Otherwise int64[4], and the call waits: [0] blocks, [1] failed blocks, [2] bytes written by
+ *               good blocks, [3] index of the first failed block (-1: none).
+ * CANVAS_ERR_INVALID: NULL context, negative nblocks, a NULL buffer with nblocks > 0.  nblocks == 0 launches nothing. */
+typedef struct { uint64_t src_offset; uint64_t dst_offset; uint32_t src_bytes; uint32_t out_bytes; } canvas_bgzf_block;   /* 24 bytes */
+#define CANVAS_INFLATE_OK 0
+#define CANVAS_INFLATE_DESCRIPTOR 1   /* a size above 65536 or a range outside its buffer */
+#define CANVAS_INFLATE_HEADER 2       /* BTYPE 3, stored LEN != ~NLEN, more than 286 literal/length or 30 distance codes */
+#define CANVAS_INFLATE_INPUT 3        /* the stream needs bits behind src_bytes */
+#define CANVAS_INFLATE_OVERRUN 4      /* the stream gives more than out_bytes */
+#define CANVAS_INFLATE_SHORT 5        /* the stream ends before out_bytes */
+#define CANVAS_INFLATE_DISTANCE 6     /* a match reaches before the block's first output byte */
+#define CANVAS_INFLATE_CODE 7         /* an invalid symbol or code set */
+int32_t canvas_bgzf_inflate(canvas_ctx* ctx, const uint8_t* d_src, uint64_t src_nbytes, const canvas_bgzf_block* d_blocks, int64_t nblocks,
+                            uint8_t* d_dst, uint64_t dst_nbytes, int32_t* d_status, int64_t* h_info);
+/* The descriptors of consecutive BGZF blocks of h_bytes[0, nbytes) from byte `at` on (host memory; no context, no device call): the gzip magic bytes, FEXTRA, a `BC`
+ * subfield with SLEN 2, BSIZE, ISIZE <= 65536.  src_offset is the deflate data's offset in h_bytes, dst_offset the running sum of out_bytes from 0.  The walk stops, in
+ * this order of precedence, at `capacity` blocks or once the inflated sizes have reached max_out_bytes (CANVAS_BGZF_SCAN_LIMIT), at nbytes (_END), or at bytes that
+ * are no whole block (_DAMAGED).  h_info int64[4]: [0] blocks, [1] the file offset the walk stopped at, [2] their inflated bytes, [3] the reason.
+ * CANVAS_ERR_INVALID: NULL h_info, NULL h_bytes with nbytes > 0, negative capacity, NULL h_blocks with capacity > 0, at > nbytes. */
+#define CANVAS_BGZF_SCAN_LIMIT 0
+#define CANVAS_BGZF_SCAN_END 1
+#define CANVAS_BGZF_SCAN_DAMAGED 2
+int32_t canvas_bgzf_scan(const uint8_t* h_bytes, uint64_t nbytes, uint64_t at, uint64_t max_out_bytes, canvas_bgzf_block* h_blocks, int64_t capacity, int64_t* h_info);
+
 /* ---- profiling hooks (hipEvent pairs recorded on the context's stream around the named kernels) --------------------- */
 /* on: 0 off; 1 every named scope; 2 only the scopes around the dominant (HBM-bound) kernel of CanvasBin — "bin_summary", "bin_summary_packed", "bin_pass",
    "bin_tile_stats" — so that a timed pass carries two event records instead of a dozen (each scope costs two barrier packets on the stream) */
