@@ -762,14 +762,12 @@ int32_t canvas_bin_rates(canvas_ctx* ctx, int32_t nchr, const uint8_t* const* d_
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     { int32_t rcf = canvas_upload_fence(ctx); if (rcf) return rcf; }
     BinPlan plan = make_plan(nchr, nullptr, d_mask, d_hits, h_len);
-    WsSizer sz; sz.take<BinChrom>(nchr); sz.take<unsigned long long>(nchr); sz.take<uint32_t>(plan.ntiles); sz.take<uint32_t>(plan.ntiles);
-    sz.take<int32_t>(plan.ntiles); sz.take<ChromOut>(nchr);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    BinChrom* dCh; unsigned long long* dPos0; uint32_t *tilePop, *tileObs; int32_t* rankBase; ChromOut* dOut;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) {
+        ws.take(dCh, nchr); ws.take(dPos0, nchr); ws.take(tilePop, plan.ntiles); ws.take(tileObs, plan.ntiles); ws.take(rankBase, plan.ntiles); ws.take(dOut, nchr);
+    });
+    if (rc) return rc;
     rc = canvas_pin_reserve(ctx, nchr * (sizeof(BinChrom) + sizeof(ChromOut))); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    BinChrom* dCh = ws.take<BinChrom>(nchr); unsigned long long* dPos0 = ws.take<unsigned long long>(nchr);
-    uint32_t* tilePop = ws.take<uint32_t>(plan.ntiles); uint32_t* tileObs = ws.take<uint32_t>(plan.ntiles);
-    int32_t* rankBase = ws.take<int32_t>(plan.ntiles); ChromOut* dOut = ws.take<ChromOut>(nchr);
     memcpy(ctx->pin, plan.chroms.data(), nchr * sizeof(BinChrom));
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dCh, ctx->pin, nchr * sizeof(BinChrom), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_init_pos0, dim3((nchr + 63) / 64), dim3(64), 0, ctx->stream, dCh, nchr, dPos0);   // pos0 = len: popBefore irrelevant here
@@ -825,10 +823,7 @@ static int32_t gcw_prepass_begin(canvas_ctx* ctx, int32_t nchr, const uint8_t* c
     int64_t totLen = 0;
     for (int c = 0; c < nchr; c++) totLen += (h_len[c] + 255) & ~255ll;
     size_t bytes = (size_t)totLen + 4096 + (size_t)nchr * (16 * NZ_REP + sizeof(GcwChrom) + sizeof(RgChrom)) + (size_t)RG_REP_ALL * 202 * 8 + 101 * 4 + (GCW_HMAX + 1) * 101 * 4 + 8192;
-    if (bytes > ctx->gc_arena_bytes) {
-        if (ctx->gc_arena) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->gc_arena)); ctx->gc_arena = nullptr; ctx->gc_arena_bytes = 0; }
-        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->gc_arena, bytes)); ctx->gc_arena_bytes = bytes;
-    }
+    { int32_t rcg = cvx_grow_device(ctx, &ctx->gc_arena, &ctx->gc_arena_bytes, bytes, bytes, ctx->stream); if (rcg) return rcg; }
     uint8_t* gcArena = (uint8_t*)ctx->gc_arena;
     uint8_t* p = gcArena;
     P.hGch.assign(nchr, GcwChrom{nullptr}); std::vector<GcwChrom>& gch = P.hGch;
@@ -934,11 +929,7 @@ static int32_t bin_genome_impl(canvas_ctx* ctx, int32_t nchr, const uint8_t* con
     }
     // the bin arrays are sized by the caller's capacity (the bin size may not be known yet)
     const int64_t ub = cap;
-    WsSizer sz;
     const size_t tabSlots = (size_t)nchr + ((size_t)nchr + sizeof(BinChrom) - 1) / sizeof(BinChrom);      // the chromosome table + one byte per chromosome (is autosome) behind it: one upload
-    sz.take<BinChrom>(tabSlots); sz.take<unsigned long long>(nchr); sz.take<uint32_t>(plan.ntiles); sz.take<uint32_t>(plan.ntiles); sz.take<int32_t>(plan.ntiles);
-    sz.take<ChromOut>(nchr); sz.take<long long>(nchr + 1); sz.take<uint32_t>(plan.ntiles); sz.take<uint32_t>(plan.ntiles);
-    sz.take<int32_t>(ub + 1); sz.take<uint32_t>(ub + 1); sz.take<uint32_t>(ub + 1);
     // bases/hits/mask streamed once (see k_tile_summary) when the rates are needed too; CANVAS_BIN_SINGLE_READ=1 takes that path for a given bin
     // size as well and CANVAS_BIN_TWO_PASS=1 never takes it (both are test hooks: the two paths must agree bit for bit)
     // a pending upload (canvas_upload_genome_begin) of exactly these arrays: every chromosome is swept as soon as it has arrived (single-read path only)
@@ -948,22 +939,20 @@ static int32_t bin_genome_impl(canvas_ctx* ctx, int32_t nchr, const uint8_t* con
     ctx->up_active = false;
     const bool singleRead = packed || streamed || (needRates && !cvx_hook("CANVAS_BIN_TWO_PASS")) || cvx_hook("CANVAS_BIN_SINGLE_READ");
     const int nchunks = (int)((plan.ntiles + TS_CHUNK - 1) / TS_CHUNK);
-    if (singleRead) { sz.take<uint32_t>(plan.ntiles * 64); sz.take<uint32_t>(plan.ntiles + 8); sz.take<TsPart>(nchunks + 1); sz.take<TsPart>(nchunks + 1); sz.take<unsigned long long>(nchr);
-                      sz.take<TsPart>(nchr + 1); sz.take<ChromDev>(nchr); sz.take<uint4>(ub + 1); }
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    BinChrom* dCh; unsigned long long* dPos0; uint32_t *tilePop, *tileObs, *tileTotC, *tileTotG, *locC, *locG; int32_t *rankBase, *stopTmp; ChromOut* dOut; long long* binOffset;
+    uint32_t* wordSum = nullptr; uint32_t* rankRaw = nullptr; TsPart* tsPart = nullptr; TsPart* tsPartEx = nullptr; unsigned long long* dPopBefore = nullptr; TsPart* chrPre = nullptr; ChromDev* chrDev = nullptr; uint4* binRec = nullptr;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) {
+        ws.take(dCh, tabSlots); ws.take(dPos0, nchr); ws.take(tilePop, plan.ntiles); ws.take(tileObs, plan.ntiles); ws.take(rankBase, plan.ntiles);
+        ws.take(dOut, nchr); ws.take(binOffset, nchr + 1); ws.take(tileTotC, plan.ntiles); ws.take(tileTotG, plan.ntiles);
+        ws.take(stopTmp, ub + 1); ws.take(locC, ub + 1); ws.take(locG, ub + 1);
+        if (singleRead) { ws.take(wordSum, plan.ntiles * 64); ws.take(rankRaw, plan.ntiles + 8); ws.take(tsPart, nchunks + 1); ws.take(tsPartEx, nchunks + 1); ws.take(dPopBefore, nchr);
+                          ws.take(chrPre, nchr + 1); ws.take(chrDev, nchr); ws.take(binRec, ub + 1); }
+    });
+    if (rc) return rc;
+    uint8_t* dIsAuto = (uint8_t*)(dCh + nchr);
     // pinned staging: [chromosome table | is-autosome bytes] (one H2D), then what comes back: per-chromosome totals, (packed: pos0 going up), the decisions
     const size_t oAuto = (size_t)nchr * sizeof(BinChrom), oOut = (oAuto + (size_t)nchr + 15) & ~size_t(15), oP0 = oOut + (size_t)nchr * sizeof(ChromOut), oBd = oP0 + (size_t)nchr * 8;
     rc = canvas_pin_reserve(ctx, oBd + sizeof(BinDev) + 64); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    BinChrom* dCh = ws.take<BinChrom>(tabSlots); unsigned long long* dPos0 = ws.take<unsigned long long>(nchr);
-    uint32_t* tilePop = ws.take<uint32_t>(plan.ntiles); uint32_t* tileObs = ws.take<uint32_t>(plan.ntiles); int32_t* rankBase = ws.take<int32_t>(plan.ntiles);
-    ChromOut* dOut = ws.take<ChromOut>(nchr); long long* binOffset = ws.take<long long>(nchr + 1);
-    uint32_t* tileTotC = ws.take<uint32_t>(plan.ntiles); uint32_t* tileTotG = ws.take<uint32_t>(plan.ntiles);
-    int32_t* stopTmp = ws.take<int32_t>(ub + 1); uint32_t* locC = ws.take<uint32_t>(ub + 1); uint32_t* locG = ws.take<uint32_t>(ub + 1);
-    uint32_t* wordSum = singleRead ? ws.take<uint32_t>(plan.ntiles * 64) : nullptr;
-    uint32_t* rankRaw = nullptr; TsPart* tsPart = nullptr; TsPart* tsPartEx = nullptr; unsigned long long* dPopBefore = nullptr; TsPart* chrPre = nullptr; ChromDev* chrDev = nullptr; uint4* binRec = nullptr; uint8_t* dIsAuto = (uint8_t*)(dCh + nchr);
-    if (singleRead) { rankRaw = ws.take<uint32_t>(plan.ntiles + 8); tsPart = ws.take<TsPart>(nchunks + 1); tsPartEx = ws.take<TsPart>(nchunks + 1); dPopBefore = ws.take<unsigned long long>(nchr);
-                      chrPre = ws.take<TsPart>(nchr + 1); chrDev = ws.take<ChromDev>(nchr); binRec = ws.take<uint4>(ub + 1); }
     if (singleRead && !ctx->bin_dev) {
         CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->bin_dev, 256)); CANVAS_HIP_TRY(ctx, hipMemsetAsync(ctx->bin_dev, 0, 256, ctx->stream));      // the tickets clean up after themselves
         CANVAS_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->bin_ev, hipEventDisableTiming));
@@ -1223,11 +1212,9 @@ int32_t canvas_pack_genome_device(canvas_ctx* ctx, int32_t nchr, const uint8_t* 
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     { int32_t rcf = canvas_upload_fence(ctx); if (rcf) return rcf; }
     for (int c = 0; c < nchr; c++) if (h_len[c] <= 0 || h_len[c] > 0x7FFFFFFFll) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "chromosome length must be in [1, 2^31)");
-    WsSizer sz; sz.take<BinChrom>(nchr); sz.take<unsigned long long>(nchr + 1);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    BinChrom* dCh; unsigned long long* dPos0;   // dPos0[nchr] = saturated positions
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) { ws.take(dCh, nchr); ws.take(dPos0, nchr + 1); }); if (rc) return rc;
     rc = canvas_pin_reserve(ctx, nchr * (sizeof(BinChrom) + 8) + 8); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    BinChrom* dCh = ws.take<BinChrom>(nchr); unsigned long long* dPos0 = ws.take<unsigned long long>(nchr + 1);   // [nchr] = saturated positions
     if (doRef) {
         BinPlan plan = make_plan(nchr, d_bases, d_mask, d_hits, h_len);
         memcpy(ctx->pin, plan.chroms.data(), nchr * sizeof(BinChrom));
@@ -1420,10 +1407,7 @@ int32_t canvas_upload_packed2_begin(canvas_ctx* ctx, int32_t nchr, const int64_t
         const size_t words = (size_t)((h_len[c] + TILE - 1) / TILE) * 64;
         need += al(words * 16) + al(words / 64 * 16) + al((size_t)h_n_extras[c] * 16 + 16);
     }
-    if (need > ctx->up2_stage_bytes) {
-        if (ctx->up2_stage) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->copy)); CANVAS_HIP_TRY(ctx, hipFree(ctx->up2_stage)); ctx->up2_stage = nullptr; ctx->up2_stage_bytes = 0; }
-        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->up2_stage, need + need / 8)); ctx->up2_stage_bytes = need + need / 8;
-    }
+    { int32_t rcg = cvx_grow_device(ctx, &ctx->up2_stage, &ctx->up2_stage_bytes, need, need + need / 8, ctx->copy); if (rcg) return rcg; }
     // the staging area and the destinations may still be read by work queued on the compute stream (the previous pass): the copies start after it
     CANVAS_HIP_TRY(ctx, hipEventRecord(ctx->up_fence, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy, ctx->up_fence, 0));
@@ -1531,11 +1515,8 @@ static int32_t bin_predefined_impl(canvas_ctx* ctx, int32_t nchr, const uint8_t*
         if (gcw) CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         return CANVAS_OK;
     }
-    WsSizer sz;
-    sz.take<PreChrom>(nchr); sz.take<int>(64); sz.take<BinChrom>(nchr); sz.take<int32_t>(nbins); sz.take<int32_t>(nbins);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver cv(ctx->ws);
-    PreChrom* dCh = cv.take<PreChrom>(nchr); int* dErr = cv.take<int>(64); BinChrom* dBc = cv.take<BinChrom>(nchr); int32_t* dChrIdx = cv.take<int32_t>(nbins); int32_t* dStartUsed = cv.take<int32_t>(nbins);
+    PreChrom* dCh; int* dErr; BinChrom* dBc; int32_t *dChrIdx, *dStartUsed;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& cv) { cv.take(dCh, nchr); cv.take(dErr, 64); cv.take(dBc, nchr); cv.take(dChrIdx, nbins); cv.take(dStartUsed, nbins); }); if (rc) return rc;
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dCh, pc.data(), (size_t)nchr * sizeof(PreChrom), hipMemcpyHostToDevice, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dErr, 0, 4, ctx->stream));
     BinPlan plan;

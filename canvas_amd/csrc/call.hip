@@ -194,31 +194,26 @@ static int32_t cl_segment_select_enqueue(canvas_ctx* ctx, const float* d_values,
     const size_t nq = ranks.size(), histWords = nq * 256 * SEL_REP;
     // the flag and every list travel as ONE pinned blob with the layout of the device workspace (one asynchronous copy, no wait, whatever S is); the blob is reused by the
     // next select, which first waits for the event behind this copy — the copy only, not the kernels
-    WsSizer sz; sz.take<unsigned long long>(1); sz.take<ClItem>(wave.size()); sz.take<ClItem>(lds.size()); sz.take<ClBig>(big.size()); sz.take<SelTile>(tiles.size());
-    sz.take<SelSegQ>(segq.size()); sz.take<unsigned long long>(nq);
-    const size_t blobBytes = sz.off;
-    sz.take<unsigned long long>(nq); sz.take<uint32_t>(histWords);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-    if (!ctx->call_pin_ev) CANVAS_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->call_pin_ev, hipEventDisableTiming));
-    else CANVAS_HIP_TRY(ctx, hipEventSynchronize(ctx->call_pin_ev));
-    if (blobBytes + 256 > ctx->call_pin_bytes) {
-        if (ctx->call_pin) { CANVAS_HIP_TRY(ctx, hipHostFree(ctx->call_pin)); ctx->call_pin = nullptr; ctx->call_pin_bytes = 0; }
-        const size_t want = blobBytes + blobBytes / 4 + (64u << 10);
-        CANVAS_HIP_TRY(ctx, hipHostMalloc(&ctx->call_pin, want, hipHostMallocDefault)); ctx->call_pin_bytes = want;
-    }
-    WsCarver cv(ctx->ws), hv(ctx->call_pin);
-    unsigned long long* dBad = cv.take<unsigned long long>(1);
-    ClItem* dWave = cv.take<ClItem>(wave.size()); ClItem* dLds = cv.take<ClItem>(lds.size()); ClBig* dBig = cv.take<ClBig>(big.size()); SelTile* dTiles = cv.take<SelTile>(tiles.size());
-    SelSegQ* dSegq = cv.take<SelSegQ>(segq.size()); unsigned long long* dK = cv.take<unsigned long long>(nq); unsigned long long* dPrefix = cv.take<unsigned long long>(nq);
-    uint32_t* dHist = cv.take<uint32_t>(histWords);
-    *hv.take<unsigned long long>(1) = ~0ull;
-    if (!wave.empty()) memcpy(hv.take<ClItem>(wave.size()), wave.data(), wave.size() * sizeof(ClItem)); else hv.take<ClItem>(0);
-    if (!lds.empty()) memcpy(hv.take<ClItem>(lds.size()), lds.data(), lds.size() * sizeof(ClItem)); else hv.take<ClItem>(0);
-    if (!big.empty()) memcpy(hv.take<ClBig>(big.size()), big.data(), big.size() * sizeof(ClBig)); else hv.take<ClBig>(0);
-    if (!tiles.empty()) memcpy(hv.take<SelTile>(tiles.size()), tiles.data(), tiles.size() * sizeof(SelTile)); else hv.take<SelTile>(0);
-    if (!segq.empty()) memcpy(hv.take<SelSegQ>(segq.size()), segq.data(), segq.size() * sizeof(SelSegQ)); else hv.take<SelSegQ>(0);
-    if (nq) memcpy(hv.take<unsigned long long>(nq), ranks.data(), nq * sizeof(unsigned long long)); else hv.take<unsigned long long>(0);
-    if (hv.off != blobBytes || (size_t)((char*)dPrefix - (char*)ctx->ws) < blobBytes) CANVAS_FAIL(ctx, CANVAS_ERR_HIP, "canvas_segment_select: staging layout");
+    unsigned long long *dBad, *dK, *dPrefix, *hBad, *hK; ClItem *dWave, *dLds, *hWave, *hLds; ClBig *dBig, *hBig; SelTile *dTiles, *hTiles; SelSegQ *dSegq, *hSegq; uint32_t* dHist;
+    auto blob = [&](WsCarver& c, unsigned long long*& bad, ClItem*& w, ClItem*& l, ClBig*& b, SelTile*& t, SelSegQ*& q, unsigned long long*& k) {
+        c.take(bad, 1); c.take(w, wave.size()); c.take(l, lds.size()); c.take(b, big.size()); c.take(t, tiles.size()); c.take(q, segq.size()); c.take(k, nq);
+    };
+    int32_t rc = cvx_ws_carve(ctx, 256, [&](WsCarver& cv) { blob(cv, dBad, dWave, dLds, dBig, dTiles, dSegq, dK); cv.take(dPrefix, nq); cv.take(dHist, histWords); }); if (rc) return rc;
+    size_t blobBytes = 0;
+    rc = ws_layout_carve("canvas_segment_select: staging layout", 256, CANVAS_ERR_HIP, &ctx->err, [&](size_t need, void** base) -> int32_t {
+        if (!ctx->call_pin_ev) CANVAS_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->call_pin_ev, hipEventDisableTiming));
+        else CANVAS_HIP_TRY(ctx, hipEventSynchronize(ctx->call_pin_ev));
+        const size_t b = need - 256;
+        const int32_t rcg = cvx_grow_pinned(ctx, &ctx->call_pin, &ctx->call_pin_bytes, need, b + b / 4 + (64u << 10)); *base = ctx->call_pin; return rcg;
+    }, [&](WsCarver& hv) { blob(hv, hBad, hWave, hLds, hBig, hTiles, hSegq, hK); }, &blobBytes);
+    if (rc) return rc;
+    *hBad = ~0ull;
+    if (!wave.empty()) memcpy(hWave, wave.data(), wave.size() * sizeof(ClItem));
+    if (!lds.empty()) memcpy(hLds, lds.data(), lds.size() * sizeof(ClItem));
+    if (!big.empty()) memcpy(hBig, big.data(), big.size() * sizeof(ClBig));
+    if (!tiles.empty()) memcpy(hTiles, tiles.data(), tiles.size() * sizeof(SelTile));
+    if (!segq.empty()) memcpy(hSegq, segq.data(), segq.size() * sizeof(SelSegQ));
+    if (nq) memcpy(hK, ranks.data(), nq * sizeof(unsigned long long));
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(ctx->ws, ctx->call_pin, blobBytes, hipMemcpyHostToDevice, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipEventRecord(ctx->call_pin_ev, ctx->stream));
     if (!wave.empty()) {
@@ -243,6 +238,14 @@ static int32_t cl_segment_select_enqueue(canvas_ctx* ctx, const float* d_values,
     CANVAS_HIP_TRY(ctx, hipGetLastError());
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(h_bad, dBad, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     return CANVAS_OK;
+}
+
+// cvx_ws_carve for ctx->call_ws: what a caller keeps across the selects it enqueues (they carve ctx->ws); grow-only, by a quarter and 1 MB
+template <class Layout> static int32_t cl_call_ws_carve(canvas_ctx* ctx, Layout&& layout, const char* site = __builtin_FUNCTION()) {
+    return ws_layout_carve(site, 256, CANVAS_ERR_HIP, &ctx->err, [&](size_t need, void** base) {
+        const size_t b = need - 256;
+        const int32_t rc = cvx_grow_device(ctx, &ctx->call_ws, &ctx->call_ws_bytes, need, b + b / 4 + (1u << 20), ctx->stream); *base = ctx->call_ws; return rc;
+    }, layout);
 }
 
 extern "C" int32_t canvas_segment_select(canvas_ctx* ctx, const float* d_values, int64_t nseg, const int64_t* h_seg_offset, int32_t mode, double* d_out, int64_t* h_nempty) {
@@ -448,22 +451,17 @@ static int32_t cl_call_diploid(canvas_ctx* ctx, int64_t nbins, const float* d_co
 
     // ---- buffers that live across the selects
     const long long nb = (nsites + CL_BLOCK - 1) / CL_BLOCK;
-    WsSizer sz; sz.take<ClSiteStat>(1); sz.take<ClModel>(1); sz.take<long long>((size_t)nchr + 1); sz.take<long long>((size_t)nchr + 1); sz.take<int>((size_t)nseg); sz.take<int>((size_t)nseg);
-    sz.take<int>((size_t)nsites); sz.take<unsigned>((size_t)nb); sz.take<unsigned long long>((size_t)nb + 1); sz.take<float>((size_t)nsites); sz.take<int>((size_t)nsites);
-    sz.take<long long>((size_t)nseg + 1); for (int k = 0; k < 5; k++) sz.take<double>((size_t)nseg); for (int k = 0; k < 3; k++) sz.take<int>((size_t)nseg);
-    if (sz.off + 256 > ctx->call_ws_bytes) {
-        if (ctx->call_ws) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->call_ws)); ctx->call_ws = nullptr; ctx->call_ws_bytes = 0; }
-        const size_t want = sz.off + sz.off / 4 + (1u << 20);
-        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->call_ws, want)); ctx->call_ws_bytes = want;
-    }
-    WsCarver cv(ctx->call_ws);
-    ClSiteStat* dSt = cv.take<ClSiteStat>(1); ClModel* dModel = cv.take<ClModel>(1); long long* dChrSite = cv.take<long long>((size_t)nchr + 1); long long* dChrSeg = cv.take<long long>((size_t)nchr + 1);
-    int* dBegin = cv.take<int>((size_t)nseg); int* dEnd = cv.take<int>((size_t)nseg); int* dSiteSeg = cv.take<int>((size_t)nsites); unsigned* dBlockCnt = cv.take<unsigned>((size_t)nb);
-    unsigned long long* dBlockOff = cv.take<unsigned long long>((size_t)nb + 1); float* dMaf = cv.take<float>((size_t)nsites); int* dCseg = cv.take<int>((size_t)nsites);
-    long long* dSegOff = cv.take<long long>((size_t)nseg + 1);
-    double* dMedCount = cv.take<double>((size_t)nseg); double* dMedMafIn = cv.take<double>((size_t)nseg); double* dMedMaf = cv.take<double>((size_t)nseg); double* dDist = cv.take<double>((size_t)nseg);
-    double* dDist2 = cv.take<double>((size_t)nseg); int* dInf = cv.take<int>((size_t)nseg); int* dCn = cv.take<int>((size_t)nseg); int* dMcc = cv.take<int>((size_t)nseg);
-    int32_t rc = canvas_pin_reserve(ctx, 256); if (rc) return rc;
+    ClSiteStat* dSt; ClModel* dModel; long long *dChrSite, *dChrSeg, *dSegOff; int *dBegin, *dEnd, *dSiteSeg, *dCseg, *dInf, *dCn, *dMcc; unsigned* dBlockCnt; unsigned long long* dBlockOff; float* dMaf;
+    double *dMedCount, *dMedMafIn, *dMedMaf, *dDist, *dDist2;
+    int32_t rc = cl_call_ws_carve(ctx, [&](WsCarver& cv) {
+        const size_t S = (size_t)nseg;
+        cv.take(dSt, 1); cv.take(dModel, 1); cv.take(dChrSite, (size_t)nchr + 1); cv.take(dChrSeg, (size_t)nchr + 1); cv.take(dBegin, S); cv.take(dEnd, S);
+        cv.take(dSiteSeg, (size_t)nsites); cv.take(dBlockCnt, (size_t)nb); cv.take(dBlockOff, (size_t)nb + 1); cv.take(dMaf, (size_t)nsites); cv.take(dCseg, (size_t)nsites);
+        cv.take(dSegOff, S + 1);
+        cv.take(dMedCount, S); cv.take(dMedMafIn, S); cv.take(dMedMaf, S); cv.take(dDist, S); cv.take(dDist2, S); cv.take(dInf, S); cv.take(dCn, S); cv.take(dMcc, S);
+    });
+    if (rc) return rc;
+    rc = canvas_pin_reserve(ctx, 256); if (rc) return rc;
     unsigned long long* hBad = (unsigned long long*)ctx->pin;     // [0..2] the selects' flags, [4..8] ClSiteStat
     ClSiteStat* hSt = (ClSiteStat*)(hBad + 4);
     const unsigned long long none = ~0ull;
@@ -768,27 +766,18 @@ static int32_t sc_call_somatic(canvas_ctx* ctx, int64_t nbins, const float* d_co
     // ---- buffers that live across the selects and the fit (which carve ctx->ws)
     const long long nb = (nsites + CL_BLOCK - 1) / CL_BLOCK;
     const size_t S = (size_t)nseg;
-    WsSizer sz; sz.take<ClSiteStat>(1); sz.take<ScModel>(1); sz.take<long long>((size_t)nchr + 1); sz.take<long long>((size_t)nchr + 1); sz.take<int>(S); sz.take<int>(S);
-    sz.take<int>((size_t)nsites); sz.take<unsigned>((size_t)nb); sz.take<unsigned long long>((size_t)nb + 1); sz.take<float>((size_t)nsites); sz.take<int>((size_t)nsites);
-    sz.take<long long>(S + 1); sz.take<long long>(S + 1); sz.take<long long>(S); for (int k = 0; k < 11; k++) sz.take<double>(S); for (int k = 0; k < 7; k++) sz.take<int>(S);
-    sz.take<float>(S); sz.take<float>((size_t)nbins); sz.take<double>(4);
-    if (sz.off + 256 > ctx->call_ws_bytes) {
-        if (ctx->call_ws) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->call_ws)); ctx->call_ws = nullptr; ctx->call_ws_bytes = 0; }
-        const size_t want = sz.off + sz.off / 4 + (1u << 20);
-        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->call_ws, want)); ctx->call_ws_bytes = want;
-    }
-    WsCarver cv(ctx->call_ws);
-    ClSiteStat* dSt = cv.take<ClSiteStat>(1); ScModel* dModel = cv.take<ScModel>(1); long long* dChrSite = cv.take<long long>((size_t)nchr + 1); long long* dChrSeg = cv.take<long long>((size_t)nchr + 1);
-    int* dBegin = cv.take<int>(S); int* dEnd = cv.take<int>(S); int* dSiteSeg = cv.take<int>((size_t)nsites); unsigned* dBlockCnt = cv.take<unsigned>((size_t)nb);
-    unsigned long long* dBlockOff = cv.take<unsigned long long>((size_t)nb + 1); float* dMaf = cv.take<float>((size_t)nsites); int* dCseg = cv.take<int>((size_t)nsites);
-    long long* dSegOff = cv.take<long long>(S + 1); long long* dBinOff = cv.take<long long>(S + 1); long long* dDst = cv.take<long long>(S);
-    double* dMedCount = cv.take<double>(S); double* dMafUp = cv.take<double>(S); double* dCov = cv.take<double>(S); double* dMafU = cv.take<double>(S); double* dW = cv.take<double>(S);
-    double* dUCov = cv.take<double>(S); double* dUMaf = cv.take<double>(S); double* dUW = cv.take<double>(S); double* dDist = cv.take<double>(S); double* dDist2 = cv.take<double>(S);
-    double* dMean = cv.take<double>(S);                         // (11 arrays of doubles, then 7 of ints: the sizer's two loops)
-    int* dULen = cv.take<int>(S); int* dDense = cv.take<int>(S); int* dRefCn = cv.take<int>(S); int* dCn = cv.take<int>(S); int* dCn2 = cv.take<int>(S); int* dMcc = cv.take<int>(S);
-    int* dRoute = cv.take<int>(S);
-    float* dMedF = cv.take<float>(S); float* dCompact = cv.take<float>((size_t)nbins); double* dQ = cv.take<double>(4);
-    int32_t rc = canvas_pin_reserve(ctx, 256); if (rc) return rc;
+    ClSiteStat* dSt; ScModel* dModel; long long *dChrSite, *dChrSeg, *dSegOff, *dBinOff, *dDst; int *dBegin, *dEnd, *dSiteSeg, *dCseg; unsigned* dBlockCnt; unsigned long long* dBlockOff; float *dMaf, *dMedF, *dCompact;
+    double *dMedCount, *dMafUp, *dCov, *dMafU, *dW, *dUCov, *dUMaf, *dUW, *dDist, *dDist2, *dMean, *dQ; int *dULen, *dDense, *dRefCn, *dCn, *dCn2, *dMcc, *dRoute;
+    int32_t rc = cl_call_ws_carve(ctx, [&](WsCarver& cv) {
+        cv.take(dSt, 1); cv.take(dModel, 1); cv.take(dChrSite, (size_t)nchr + 1); cv.take(dChrSeg, (size_t)nchr + 1); cv.take(dBegin, S); cv.take(dEnd, S);
+        cv.take(dSiteSeg, (size_t)nsites); cv.take(dBlockCnt, (size_t)nb); cv.take(dBlockOff, (size_t)nb + 1); cv.take(dMaf, (size_t)nsites); cv.take(dCseg, (size_t)nsites);
+        cv.take(dSegOff, S + 1); cv.take(dBinOff, S + 1); cv.take(dDst, S);
+        cv.take(dMedCount, S); cv.take(dMafUp, S); cv.take(dCov, S); cv.take(dMafU, S); cv.take(dW, S); cv.take(dUCov, S); cv.take(dUMaf, S); cv.take(dUW, S); cv.take(dDist, S); cv.take(dDist2, S); cv.take(dMean, S);
+        cv.take(dULen, S); cv.take(dDense, S); cv.take(dRefCn, S); cv.take(dCn, S); cv.take(dCn2, S); cv.take(dMcc, S); cv.take(dRoute, S);
+        cv.take(dMedF, S); cv.take(dCompact, (size_t)nbins); cv.take(dQ, 4);
+    });
+    if (rc) return rc;
+    rc = canvas_pin_reserve(ctx, 256); if (rc) return rc;
     unsigned long long* hBad = (unsigned long long*)ctx->pin;     // [0..3] the selects' flags, [4..8] ClSiteStat, [10..11] the two quartile medians
     // (hBad[1] and hBad[3], the flags of the two selects over whole arrays, are not looked at: the per-segment select behind hBad[0] has read every one of those counts)
     ClSiteStat* hSt = (ClSiteStat*)(hBad + 4);

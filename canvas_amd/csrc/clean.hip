@@ -697,29 +697,20 @@ extern "C" int32_t canvas_clean2(canvas_ctx* ctx, int64_t n, int32_t* d_chr, int
     }
     // workspace
     const int64_t nW0 = n / 20 + 2;
-    WsSizer sz;
-    sz.take<int32_t>(n); sz.take<int32_t>(n); sz.take<int32_t>(n); sz.take<int32_t>(n); sz.take<float>(n); sz.take<double>(n); sz.take<double>(n);
-    sz.take<int32_t>(n); sz.take<int32_t>(n); sz.take<int32_t>(n); sz.take<int32_t>(n); sz.take<float>(n); sz.take<double>(n);
-    sz.take<uint8_t>(n); sz.take<uint32_t>(n / CBLK + 2); sz.take<unsigned long long>(2); sz.take<uint32_t>(n); sz.take<unsigned long long>(nW0); sz.take<uint32_t>(n);
-    sz.take<uint8_t>(nchr); sz.take<uint32_t>(2 * NGC); sz.take<uint32_t>(NGC + 1); sz.take<uint32_t>(NGC); sz.take<double>(NGC); sz.take<VarTab>(1);
-    sz.take<uint8_t>(NGC); sz.take<double>(nW0); sz.take<double>(65536); sz.take<int64_t>(65536 + 1); sz.take<unsigned int>(1); sz.take<long long>(65536); sz.take<unsigned int>(1);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 8192); if (rc) return rc;
-    WsCarver ws(ctx->ws);
     CleanState st; st.ctx = ctx; st.n = n;
     st.cur = Soa{d_chr, d_start, d_stop, d_gc, d_count, nullptr};
-    st.alt.chr = ws.take<int32_t>(n); st.alt.start = ws.take<int32_t>(n); st.alt.stop = ws.take<int32_t>(n); st.alt.gc = ws.take<int32_t>(n);
-    st.alt.count = ws.take<float>(n); st.alt.dev = ws.take<double>(n); st.cur.dev = ws.take<double>(n);
+    uint32_t *dHist, *dSegOff, *dCursor; double *dMedians, *dSd, *dRunMedian; VarTab* dTab; uint8_t* dKeepGc; int64_t* dRunStart; unsigned int *dCnt, *dBad; long long* dPos;
+    int32_t rc = cvx_ws_carve(ctx, 8192, [&](WsCarver& ws) {
+        ws.take(st.alt.chr, n); ws.take(st.alt.start, n); ws.take(st.alt.stop, n); ws.take(st.alt.gc, n); ws.take(st.alt.count, n); ws.take(st.alt.dev, n); ws.take(st.cur.dev, n);
+        Soa& b2 = st.bufs[2];
+        ws.take(b2.chr, n); ws.take(b2.start, n); ws.take(b2.stop, n); ws.take(b2.gc, n); ws.take(b2.count, n); ws.take(b2.dev, n);
+        ws.take(st.flags, n); ws.take(st.blockCnt, n / CBLK + 2); ws.take(st.dTotal, 2); ws.take(st.keys32, n); ws.take(st.keys64, nW0); ws.take(st.gidx, n);
+        ws.take(st.dIsAuto, nchr);
+        ws.take(dHist, 2 * NGC); ws.take(dSegOff, NGC + 1); ws.take(dCursor, NGC); ws.take(dMedians, NGC); ws.take(dTab, 1); ws.take(dKeepGc, NGC);
+        ws.take(dSd, nW0); ws.take(dRunMedian, 65536); ws.take(dRunStart, 65536 + 1); ws.take(dCnt, 1); ws.take(dPos, 65536); ws.take(dBad, 1);
+    });
+    if (rc) return rc;
     st.bufs[0] = st.cur; st.bufs[1] = st.alt;
-    st.bufs[2].chr = ws.take<int32_t>(n); st.bufs[2].start = ws.take<int32_t>(n); st.bufs[2].stop = ws.take<int32_t>(n); st.bufs[2].gc = ws.take<int32_t>(n);
-    st.bufs[2].count = ws.take<float>(n); st.bufs[2].dev = ws.take<double>(n);
-    st.flags = ws.take<uint8_t>(n); st.blockCnt = ws.take<uint32_t>(n / CBLK + 2); st.dTotal = ws.take<unsigned long long>(2);
-    st.keys32 = ws.take<uint32_t>(n); st.keys64 = ws.take<unsigned long long>(nW0); st.gidx = ws.take<uint32_t>(n);
-    st.dIsAuto = ws.take<uint8_t>(nchr);
-    uint32_t* dHist = ws.take<uint32_t>(2 * NGC); uint32_t* dSegOff = ws.take<uint32_t>(NGC + 1); uint32_t* dCursor = ws.take<uint32_t>(NGC);
-    double* dMedians = ws.take<double>(NGC); VarTab* dTab = ws.take<VarTab>(1); uint8_t* dKeepGc = ws.take<uint8_t>(NGC);
-    double* dSd = ws.take<double>(nW0); double* dRunMedian = ws.take<double>(65536); int64_t* dRunStart = ws.take<int64_t>(65536 + 1);
-    unsigned int* dCnt = ws.take<unsigned int>(1); long long* dPos = ws.take<long long>(65536);
-    unsigned int* dBad = ws.take<unsigned int>(1);
     ProfScope psTotal(ctx, "clean_total");       // whole CanvasClean on the device timeline (kernels + the gaps of the host decisions)
     rc = canvas_h2d_small(ctx, st.dIsAuto, h_chr_is_autosome, nchr); if (rc) return rc;
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dBad, 0, 4, ctx->stream));
@@ -914,11 +905,8 @@ extern "C" int32_t canvas_merge_cleaned(canvas_ctx* ctx, int32_t nsamples, const
     *h_n_out = 0;
     if (n0 == 0) return CANVAS_OK;
     const int nb = (int)nblk(n0, CBLK);
-    WsSizer sz; sz.take<uint8_t>(n0); sz.take<int32_t>((size_t)nsamples * n0); sz.take<uint32_t>(nb + 2); sz.take<unsigned long long>(1); sz.take<int>(1);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    uint8_t* flags = ws.take<uint8_t>(n0); int32_t* where = ws.take<int32_t>((size_t)nsamples * n0); uint32_t* blockCnt = ws.take<uint32_t>(nb + 2);
-    unsigned long long* dTotal = ws.take<unsigned long long>(1); int* dBad = ws.take<int>(1);
+    uint8_t* flags; int32_t* where; uint32_t* blockCnt; unsigned long long* dTotal; int* dBad;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) { ws.take(flags, n0); ws.take(where, (size_t)nsamples * n0); ws.take(blockCnt, nb + 2); ws.take(dTotal, 1); ws.take(dBad, 1); }); if (rc) return rc;
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dBad, 0, 4, ctx->stream));
     hipLaunchKernelGGL(k_merge_check_sorted, dim3(nblk(nmax, 256), nsamples), dim3(256), 0, ctx->stream, P, nsamples, dBad);
     hipLaunchKernelGGL(k_merge_find, dim3(nblk(n0, 256)), dim3(256), 0, ctx->stream, P, nsamples, flags, where);
@@ -998,7 +986,7 @@ int32_t cvx_clean_f2_offsets(canvas_ctx* ctx, int64_t n, int32_t* d_chr, int32_t
         // (measured and dropped: the F2 hand-off written by the last compaction itself + a counting sweep over its integer keys — the compaction grows from 39 to 61 us, the
         //  counting sweep takes 16: 10 us less per pass than k_quant_covq, at the price of a CanvasClean stage that is 21 us slower by its own account)
         rc = cvx_quant_covq_enqueue(ctx, d_count, n, dN, d_cov, &hq); if (rc) return rc;
-        long long* dFirst = (long long*)((char*)ctx->ws + ctx->clean_ws_end);
+        long long* dFirst = q.dChrFirst;
         CANVAS_HIP_TRY(ctx, hipMemsetAsync(dFirst, 0x7F, (size_t)nchr * 8, ctx->stream));     // "not seen"
         hipLaunchKernelGGL(k_chr_first, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, d_chr, n, nchr, dFirst, dN);
         CANVAS_HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->pin + oFirst, dFirst, (size_t)nchr * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1111,10 +1099,8 @@ extern "C" int32_t canvas_select_probe(canvas_ctx* ctx, int32_t variant, int32_t
     if (nq == 0) return CANVAS_OK;
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (variant == 2) {
-        WsSizer sz; sz.take<int64_t>(nseg + 1); sz.take<int32_t>(nq); sz.take<unsigned long long>(2 * (size_t)nq); sz.take<unsigned long long>(2 * (size_t)nq);
-        int32_t rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-        WsCarver ws(ctx->ws);
-        int64_t* dOff = ws.take<int64_t>(nseg + 1); int32_t* dSeg = ws.take<int32_t>(nq); unsigned long long* dRank = ws.take<unsigned long long>(2 * (size_t)nq); unsigned long long* dOut = ws.take<unsigned long long>(2 * (size_t)nq);
+        int64_t* dOff; int32_t* dSeg; unsigned long long *dRank, *dOut;
+        int32_t rc = cvx_ws_carve(ctx, 256, [&](WsCarver& ws) { ws.take(dOff, nseg + 1); ws.take(dSeg, nq); ws.take(dRank, 2 * (size_t)nq); ws.take(dOut, 2 * (size_t)nq); }); if (rc) return rc;
         rc = canvas_h2d_small(ctx, dOff, h_seg_off, (size_t)(nseg + 1) * 8); if (rc) return rc;
         rc = canvas_h2d_small(ctx, dSeg, h_seg_lo, (size_t)nq * 4); if (rc) return rc;
         rc = canvas_h2d_small(ctx, dRank, h_k, (size_t)nq * 16); if (rc) return rc;

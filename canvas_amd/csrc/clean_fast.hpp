@@ -1494,7 +1494,7 @@ __global__ void __launch_bounds__(256) k_cf_scatter_final(const CfArgs* __restri
 }
 
 // ---------------------------------------------------------------- host side
-struct CleanPending { int B; unsigned gxN, gxB, gxT; bool anyLsd, anyVar, anyGc, useCq; CfArgs* dArgs; CleanDev* dD; std::vector<CfArgs> h; };
+struct CleanPending { int B; unsigned gxN, gxB, gxT; bool anyLsd, anyVar, anyGc, useCq; CfArgs* dArgs; CleanDev* dD; long long* dChrFirst; std::vector<CfArgs> h; };
 
 static void cf_select_passes(canvas_ctx* ctx, const CfArgs* dArgs, int B, unsigned gxT, int which) {
     for (int shift = 24; shift >= 0; shift -= 8) {
@@ -1518,50 +1518,45 @@ static int32_t clean_batch_enqueue(canvas_ctx* ctx, int B, const int64_t* h_n, i
                                    int32_t nchr, const uint8_t* h_chr_is_autosome, uint32_t flags, int32_t min_bins_per_gc, bool useCq) {
     useCq = useCq && (flags & CANVAS_CLEAN_GCNORM);
     const size_t cqWords = useCq ? (size_t)B * CQ_ROWS * CQW : 0;
-    WsSizer sz;
-    sz.take<CfArgs>(B); sz.take<uint8_t>(nchr); sz.take<CleanDev>(B); sz.take<uint32_t>((size_t)B * CF_SZ_BINS); sz.take<uint32_t>((size_t)B * CF_HREP * 3 * NGC); sz.take<CfCq>(B); sz.take<uint32_t>((size_t)B * 8 * CF_TICK_WORDS); sz.take<uint32_t>(cqWords + 4);
     int64_t nMax = 0; bool anyLsd = false, anyVar = false;
-    for (int s = 0; s < B; s++) {
-        const int64_t n = h_n[s], nW0 = n / 20 + 2, nb = nblk(n, CBLK); const size_t tilesUpper = (size_t)(n / SEL_TILE + NGC + 1);
-        nMax = std::max(nMax, n);
-        sz.take<int32_t>(n); sz.take<int32_t>(n); sz.take<int32_t>(n); sz.take<float>(n); sz.take<uint8_t>(n + 16);
-        sz.take<uint8_t>(n + 16); sz.take<unsigned long long>(nb + 2); sz.take<uint32_t>(nb + 2); sz.take<uint32_t>(n); sz.take<uint32_t>(n / 8 + 1024); sz.take<double>(nW0); sz.take<double>(CF_MAXRUN + 8);
-        sz.take<int64_t>(CF_MAXRUN + 8); sz.take<long long>(65536); sz.take<CfSel>(CF_NPROB); sz.take<SelTile>(tilesUpper * CF_NPROB); sz.take<SelTile>((size_t)(n / CQ_TILE + NGC + 1)); sz.take<unsigned long long>(64);
-    }
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 8192 + (size_t)nchr * 8 + 1024); if (rc) return rc;      // (+ the chromosome-offset table cvx_clean_f2_offsets enqueues behind the stage)
-    const size_t histPer = (size_t)CF_MAXQ * 1024 * SEL_REP, histBytes = histPer * (size_t)B;
-    if (histBytes > ctx->sel_hist_bytes) {
-        if (ctx->sel_hist) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->sel_hist)); ctx->sel_hist = nullptr; ctx->sel_hist_bytes = 0; }
-        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->sel_hist, histBytes)); ctx->sel_hist_bytes = histBytes;
-        CANVAS_HIP_TRY(ctx, hipMemsetAsync(ctx->sel_hist, 0, ctx->sel_hist_bytes, ctx->stream));       // zero once: k_select_pick clears every row it has read
-    }
-    WsCarver ws(ctx->ws);
-    // two adjacent groups: what the host sends (the argument table) and what starts as zero (k_cf_init)
-    CfArgs* dArgs = ws.take<CfArgs>(B); uint8_t* dIsAuto = ws.take<uint8_t>(nchr);
-    CleanDev* dD = ws.take<CleanDev>(B); uint32_t* dSz = ws.take<uint32_t>((size_t)B * CF_SZ_BINS); uint32_t* dRepl = ws.take<uint32_t>((size_t)B * CF_HREP * 3 * NGC); CfCq* dCq = ws.take<CfCq>(B);
-    uint32_t* dTick = ws.take<uint32_t>((size_t)B * 8 * CF_TICK_WORDS); uint32_t* dCqHist = ws.take<uint32_t>(cqWords + 4);
-    CleanPending pend; pend.useCq = useCq; pend.B = B; pend.dArgs = dArgs; pend.dD = dD; pend.h.resize(B);
+    CfArgs* dArgs; uint8_t* dIsAuto; CleanDev* dD; uint32_t *dSz, *dRepl, *dTick, *dCqHist; CfCq* dCq;
+    CleanPending pend; pend.useCq = useCq; pend.B = B; pend.h.resize(B);
     unsigned gxT = 1, gxTcq = 1;
-    for (int s = 0; s < B; s++) {
-        const int64_t n = h_n[s], nW0 = n / 20 + 2; const int nb = (int)nblk(n, CBLK); const unsigned tilesUpper = (unsigned)(n / SEL_TILE + NGC + 1);
-        CfArgs& A = pend.h[s];
-        memset(&A, 0, sizeof A);
-        A.n = n; A.nb = nb; A.nchr = nchr; A.minBinsPerGc = min_bins_per_gc; A.flags = flags; A.tilesUpper = tilesUpper; A.useCq = useCq ? 1 : 0;
-        A.wantLsd = ((flags & CANVAS_CLEAN_LOCALSD) && n >= 50000) ? 1 : 0;
-        A.doSize = (flags & CANVAS_CLEAN_FILTSIZE) ? 1 : 0; A.doOutlier = (flags & CANVAS_CLEAN_OUTLIERS) ? 1 : 0;
-        A.caller = Soa{d_chr[s], d_start[s], d_stop[s], d_gc[s], d_count[s], nullptr};
-        A.S1.chr = ws.take<int32_t>(n); A.S1.start = ws.take<int32_t>(n); A.S1.stop = ws.take<int32_t>(n); A.S1.count = ws.take<float>(n); A.S1.gc = ws.take<uint8_t>(n + 16);
-        A.dFlags = ws.take<uint8_t>(n + 16); A.dBlk = ws.take<unsigned long long>(nb + 2); A.dBlkF = ws.take<uint32_t>(nb + 2); A.keysG = ws.take<uint32_t>(n); A.szOverCap = (uint32_t)(n / 8 + 1024); A.szOver = ws.take<uint32_t>(A.szOverCap);
-        A.dSd = ws.take<double>(nW0); A.dRunMad = ws.take<double>(CF_MAXRUN + 8); A.dRunStart = ws.take<int64_t>(CF_MAXRUN + 8); A.dPos = ws.take<long long>(65536);
-        A.P = ws.take<CfSel>(CF_NPROB); A.tiles = ws.take<SelTile>((size_t)tilesUpper * CF_NPROB);
-        A.cqTiles = ws.take<SelTile>((size_t)(n / CQ_TILE + NGC + 1)); A.cq = dCq + s; A.cqHist = dCqHist + (size_t)s * CQ_ROWS * CQW;
-        gxTcq = std::max(gxTcq, (unsigned)(n / CQ_TILE + NGC + 1));
-        A.isAuto = dIsAuto; A.repl = dRepl + (size_t)s * CF_HREP * 3 * NGC; A.szHist = dSz + (size_t)s * CF_SZ_BINS; A.D = dD + s; A.hist = (uint32_t*)((char*)ctx->sel_hist + histPer * (size_t)s);
-        A.tick = dTick + (size_t)s * 8 * CF_TICK_WORDS;
-        { unsigned long long* dbg = ws.take<unsigned long long>(64); A.dbg = cvx_hook("CANVAS_CLEAN_DEBUG_CLOCKS") ? dbg : nullptr; }
-        gxT = std::max(gxT, tilesUpper);
-        anyLsd = anyLsd || A.wantLsd; anyVar = anyVar || (A.wantLsd && n > 500000);
-    }
+    // the layout also fills the argument table pend.h (pointers into the workspace and plain values: it runs twice)
+    int32_t rc = cvx_ws_carve(ctx, 8192, [&](WsCarver& ws) {
+        // two adjacent groups: what the host sends (the argument table) and what starts as zero (k_cf_init)
+        ws.take(dArgs, B); ws.take(dIsAuto, nchr);
+        ws.take(dD, B); ws.take(dSz, (size_t)B * CF_SZ_BINS); ws.take(dRepl, (size_t)B * CF_HREP * 3 * NGC); ws.take(dCq, B);
+        ws.take(dTick, (size_t)B * 8 * CF_TICK_WORDS); ws.take(dCqHist, cqWords + 4);
+        for (int s = 0; s < B; s++) {
+            const int64_t n = h_n[s], nW0 = n / 20 + 2; const int nb = (int)nblk(n, CBLK); const unsigned tilesUpper = (unsigned)(n / SEL_TILE + NGC + 1);
+            CfArgs& A = pend.h[s];
+            memset(&A, 0, sizeof A);
+            A.n = n; A.nb = nb; A.nchr = nchr; A.minBinsPerGc = min_bins_per_gc; A.flags = flags; A.tilesUpper = tilesUpper; A.useCq = useCq ? 1 : 0;
+            A.wantLsd = ((flags & CANVAS_CLEAN_LOCALSD) && n >= 50000) ? 1 : 0;
+            A.doSize = (flags & CANVAS_CLEAN_FILTSIZE) ? 1 : 0; A.doOutlier = (flags & CANVAS_CLEAN_OUTLIERS) ? 1 : 0;
+            A.caller = Soa{d_chr[s], d_start[s], d_stop[s], d_gc[s], d_count[s], nullptr};
+            ws.take(A.S1.chr, n); ws.take(A.S1.start, n); ws.take(A.S1.stop, n); ws.take(A.S1.count, n); ws.take(A.S1.gc, n + 16);
+            ws.take(A.dFlags, n + 16); ws.take(A.dBlk, nb + 2); ws.take(A.dBlkF, nb + 2); ws.take(A.keysG, n); A.szOverCap = (uint32_t)(n / 8 + 1024); ws.take(A.szOver, A.szOverCap);
+            ws.take(A.dSd, nW0); ws.take(A.dRunMad, CF_MAXRUN + 8); ws.take(A.dRunStart, CF_MAXRUN + 8); ws.take(A.dPos, 65536);
+            ws.take(A.P, CF_NPROB); ws.take(A.tiles, (size_t)tilesUpper * CF_NPROB);
+            ws.take(A.cqTiles, (size_t)(n / CQ_TILE + NGC + 1)); A.cq = dCq + s; A.cqHist = dCqHist + (size_t)s * CQ_ROWS * CQW;
+            gxTcq = std::max(gxTcq, (unsigned)(n / CQ_TILE + NGC + 1));
+            A.isAuto = dIsAuto; A.repl = dRepl + (size_t)s * CF_HREP * 3 * NGC; A.szHist = dSz + (size_t)s * CF_SZ_BINS; A.D = dD + s;
+            A.tick = dTick + (size_t)s * 8 * CF_TICK_WORDS;
+            ws.take(A.dbg, 64); if (!cvx_hook("CANVAS_CLEAN_DEBUG_CLOCKS")) A.dbg = nullptr;
+            nMax = std::max(nMax, n); gxT = std::max(gxT, tilesUpper);
+            anyLsd = anyLsd || A.wantLsd; anyVar = anyVar || (A.wantLsd && n > 500000);
+        }
+        ws.take(pend.dChrFirst, nchr);      // the chromosome table cvx_clean_f2_offsets enqueues behind the stage (a second phase may follow: it must not alias the rest)
+    });
+    if (rc) return rc;
+    pend.dArgs = dArgs; pend.dD = dD;
+    const size_t histPer = (size_t)CF_MAXQ * 1024 * SEL_REP, histBytes = histPer * (size_t)B;
+    const bool histGrows = histBytes > ctx->sel_hist_bytes;
+    rc = cvx_grow_device(ctx, &ctx->sel_hist, &ctx->sel_hist_bytes, histBytes, histBytes, ctx->stream); if (rc) return rc;
+    if (histGrows) CANVAS_HIP_TRY(ctx, hipMemsetAsync(ctx->sel_hist, 0, ctx->sel_hist_bytes, ctx->stream));       // zero once: k_select_pick clears every row it has read
+    for (int s = 0; s < B; s++) pend.h[s].hist = (uint32_t*)((char*)ctx->sel_hist + histPer * (size_t)s);
     const unsigned gxN = (unsigned)nblk(nMax, 256), gxB = (unsigned)nblk(nMax, CBLK);
     pend.gxN = gxN; pend.gxB = gxB; pend.gxT = gxT; pend.anyLsd = anyLsd; pend.anyVar = anyVar; pend.anyGc = (flags & CANVAS_CLEAN_GCNORM) != 0;
     ProfScope psTotal(ctx, "clean_total");
@@ -1617,7 +1612,6 @@ static int32_t clean_batch_enqueue(canvas_ctx* ctx, int B, const int64_t* h_n, i
     hipLaunchKernelGGL(k_cf_scatter_final, dim3(gxB, B), dim3(256), 0, ctx->stream, dArgs, 0);
     rc = canvas_pin_reserve(ctx, (size_t)B * sizeof(CleanDev)); if (rc) return rc;
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(ctx->pin, dD, (size_t)B * sizeof(CleanDev), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->clean_ws_end = (ws.off + 255) & ~size_t(255);
     ctx->clean_batch = std::make_shared<CleanPending>(std::move(pend));
     return CANVAS_OK;
 }

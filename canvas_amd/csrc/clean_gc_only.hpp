@@ -482,7 +482,6 @@ static int32_t clean_gc_only(canvas_ctx* ctx, int B, const int64_t* h_n, int32_t
     CgPack pack; memset(&pack, 0, sizeof pack);
     memcpy(pack.isAuto, h_chr_is_autosome, (size_t)nchr); pack.minBinsPerGc = min_bins_per_gc;
     { const char* cut = cvx_hook("CANVAS_CG_CUT"); pack.cut = cut ? atoi(cut) : 0; }
-    WsSizer sz; sz.take<CgDev>(B);
     int Gmax = 1;
     for (int s = 0; s < B; s++) {
         const int64_t n = h_n[s];
@@ -492,25 +491,27 @@ static int32_t clean_gc_only(canvas_ctx* ctx, int B, const int64_t* h_n, int32_t
         CgArgs& a = pack.a[s];
         a.n = n; a.nchr = nchr; a.G = G; a.chunk = (int32_t)chunk; a.bpt = (int32_t)((chunk + CG_T - 1) / CG_T);
         a.chr = d_chr[s]; a.start = d_start[s]; a.stop = d_stop[s]; a.gc = d_gc[s]; a.count = d_count[s];
-        sz.take<uint32_t>((size_t)G * CG_SLAB); sz.take<uint32_t>((size_t)G * CG_TABW);
-        for (int k = 0; k < 5; k++) sz.take<uint32_t>((size_t)n); sz.take<uint32_t>((size_t)G);      // the spill columns and the deferral flags (touched only when a workgroup defers)
         Gmax = std::max(Gmax, G);
     }
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) cus = 0;
     pack.ticket = ((long long)Gmax * B > (long long)cus || cvx_hook("CANVAS_CG_TICKET")) ? 1 : 0;       // (the hook forces the ticket for the tests)
     pack.spin = cvx_hook("CANVAS_CG_SPIN_LIMIT") ? (uint32_t)atoi(cvx_hook("CANVAS_CG_SPIN_LIMIT")) : CG_SPIN_LIMIT;      // (test hook: 0 = every workgroup that finds a chunk in front unread defers at once)
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    CgDev* dD = ws.take<CgDev>(B);
+    CgDev* dD;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) {
+        ws.take(dD, B);
+        for (int s = 0; s < B; s++) {
+            CgArgs& a = pack.a[s];
+            ws.take(a.slab, (size_t)a.G * CG_SLAB); ws.take(a.tab, (size_t)a.G * CG_TABW);
+            // the spill columns and the deferral flags (touched only when a workgroup defers)
+            ws.take(a.spChr, (size_t)a.n); ws.take(a.spStart, (size_t)a.n); ws.take(a.spStop, (size_t)a.n); ws.take(a.spGc, (size_t)a.n);
+            ws.take(a.spCount, (size_t)a.n); ws.take(a.defer, (size_t)a.G);
+            a.D = dD + s;
+        }
+    });
+    if (rc) return rc;
     unsigned epoch = ++ctx->cg_epoch; if (epoch == 0) epoch = ++ctx->cg_epoch;
-    for (int s = 0; s < B; s++) {
-        CgArgs& a = pack.a[s];
-        a.slab = ws.take<uint32_t>((size_t)a.G * CG_SLAB); a.tab = ws.take<uint32_t>((size_t)a.G * CG_TABW);
-        a.spChr = (int32_t*)ws.take<uint32_t>((size_t)a.n); a.spStart = (int32_t*)ws.take<uint32_t>((size_t)a.n); a.spStop = (int32_t*)ws.take<uint32_t>((size_t)a.n); a.spGc = (int32_t*)ws.take<uint32_t>((size_t)a.n);
-        a.spCount = (float*)ws.take<uint32_t>((size_t)a.n); a.defer = ws.take<uint32_t>((size_t)a.G);
-        a.D = dD + s; a.S = (CgState*)ctx->cg_state + s; a.epoch = epoch;
-    }
+    for (int s = 0; s < B; s++) { pack.a[s].S = (CgState*)ctx->cg_state + s; pack.a[s].epoch = epoch; }
     const size_t head = sizeof(CgDev);
     rc = canvas_pin_reserve(ctx, (size_t)B * head); if (rc) return rc;
     {

@@ -26,10 +26,7 @@ int32_t cvx_allgather(canvas_ctx* ctx, const void* d_send, void* d_recv, size_t 
     if (ctx->comm) { CANVAS_NCCL_TRY(ctx, ncclAllGather(d_send, d_recv, bytes, ncclUint8, (ncclComm_t)ctx->comm, ctx->stream)); return CANVAS_OK; }
     if (!ctx->host_allgather) CANVAS_FAIL(ctx, CANVAS_ERR_COMM, "no communicator: call canvas_comm_init or canvas_comm_init_host first");
     const size_t need = bytes * (size_t)(ctx->nranks + 1);
-    if (need * 2 > ctx->comm_pin_bytes) {      // (two areas of `need` bytes each)
-        if (ctx->comm_pin) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipHostFree(ctx->comm_pin)); ctx->comm_pin = nullptr; ctx->comm_pin_bytes = 0; }
-        CANVAS_HIP_TRY(ctx, hipHostMalloc(&ctx->comm_pin, need * 4, hipHostMallocDefault)); ctx->comm_pin_bytes = need * 4;
-    }
+    { int32_t rcg = cvx_grow_pinned(ctx, &ctx->comm_pin, &ctx->comm_pin_bytes, need * 2, need * 4, &ctx->stream); if (rcg) return rcg; }      // (two areas of `need` bytes each)
     // two staging areas, used in turn: the upload of this exchange may still be running when the next exchange fills the OTHER area, and that exchange's own
     // synchronisation (below, same stream) has passed it by the time this area comes round again — one synchronisation per exchange instead of two
     ctx->comm_pin_flip ^= 1;

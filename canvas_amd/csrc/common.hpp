@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 #include "../../include/canvas_hip.h"
+#include "ws_layout.hpp"
 
 struct canvas_ctx {
     int device = 0;
@@ -48,7 +49,6 @@ struct canvas_ctx {
     void* bin_dev = nullptr; hipEvent_t bin_ev = nullptr;      // bin_tail.hpp: arrival tickets + the sample's decisions (BinDev) in device memory; event behind their D2H copy
     long long gcw_total = 0; void* gcw_stats_dev = nullptr;     // last GCContentWeighted binning: {bins whose weighted count was decided from the exact sum's interval, bins replayed in the reference's order} (in gc_arena)
     void* gc_arena = nullptr; size_t gc_arena_bytes = 0;   // GCContentWeighted binning: read-GC profile of every position + GC prefix array (grow-only)
-    size_t clean_ws_end = 0;          // clean_fast.hpp: bytes of ctx->ws the last clean_batch_enqueue carved (what is enqueued behind it must not alias them: a second phase may follow)
     bool clean_cq_failed = false, clean_cq_skip = false;   // clean_fast.hpp: a sample's counting selects gave up (it is redone with the radix selects)
     int one_shot = 0;                   // canvas_set_one_shot: the host makes one call per method and exits — staging through pinned host memory is not worth its pinning
     std::shared_ptr<void> cbs_cache;     // cbs.hip: device / pinned buffers of the arc-search and permutation engines, kept between calls (a call used to spend tens of ms in hipMalloc / hipHostMalloc)
@@ -171,14 +171,28 @@ static inline int32_t cvx_mail_await(canvas_ctx* ctx, const volatile unsigned* s
     return CANVAS_OK;
 }
 
-// ensure ctx->ws has at least `bytes`
-static inline int32_t canvas_ws_reserve(canvas_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->ws_bytes) return CANVAS_OK;
-    if (ctx->ws) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->ws)); ctx->ws = nullptr; ctx->ws_bytes = 0; }
-    size_t want = bytes + bytes / 4 + (1u << 20);
-    CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->ws, want));
-    ctx->ws_bytes = want;
+// grow-only buffers kept by the context: when *p holds fewer than `need` bytes the old block is freed (after `sync` has drained: work queued there may
+// still use it) and `want` bytes are allocated; the call site chooses `want` (its growth rule).  The pinned form synchronises only when given a stream.
+static inline int32_t cvx_grow_device(canvas_ctx* ctx, void** p, size_t* bytes, size_t need, size_t want, hipStream_t sync) {
+    if (need <= *bytes) return CANVAS_OK;
+    if (*p) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(sync)); CANVAS_HIP_TRY(ctx, hipFree(*p)); *p = nullptr; *bytes = 0; }
+    CANVAS_HIP_TRY(ctx, hipMalloc(p, want));
+    *bytes = want;
     return CANVAS_OK;
+}
+static inline int32_t cvx_grow_pinned(canvas_ctx* ctx, void** p, size_t* bytes, size_t need, size_t want, const hipStream_t* sync = nullptr) {
+    if (need <= *bytes) return CANVAS_OK;
+    if (*p) { if (sync) CANVAS_HIP_TRY(ctx, hipStreamSynchronize(*sync)); CANVAS_HIP_TRY(ctx, hipHostFree(*p)); *p = nullptr; *bytes = 0; }
+    CANVAS_HIP_TRY(ctx, hipHostMalloc(p, want, hipHostMallocDefault));
+    *bytes = want;
+    return CANVAS_OK;
+}
+// ensure ctx->ws has at least `bytes`
+static inline int32_t canvas_ws_reserve(canvas_ctx* ctx, size_t bytes) { return cvx_grow_device(ctx, &ctx->ws, &ctx->ws_bytes, bytes, bytes + bytes / 4 + (1u << 20), ctx->stream); }
+// the buffers of one call in ctx->ws: `layout` (ws_layout.hpp) declares them once; it is measured, `slack` more bytes are reserved, and it is carved
+template <class Layout>
+static inline int32_t cvx_ws_carve(canvas_ctx* ctx, size_t slack, Layout&& layout, const char* site = __builtin_FUNCTION()) {
+    return ws_layout_carve(site, slack, CANVAS_ERR_HIP, &ctx->err, [&](size_t bytes, void** base) { const int32_t rc = canvas_ws_reserve(ctx, bytes); *base = ctx->ws; return rc; }, layout);
 }
 #define CANVAS_MISC_PIN_BYTES (256u << 10)
 // copy `bytes` from host memory to the device through the pinned staging area: fully asynchronous, `src` may be a stack buffer
@@ -200,14 +214,7 @@ static inline int32_t canvas_side_init(canvas_ctx* ctx) {
     CANVAS_HIP_TRY(ctx, hipHostMalloc((void**)&ctx->side_pin, (65536 + 65544) * sizeof(double), hipHostMallocDefault));
     return CANVAS_OK;
 }
-static inline int32_t canvas_pin_reserve(canvas_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->pin_bytes) return CANVAS_OK;
-    if (ctx->pin) { CANVAS_HIP_TRY(ctx, hipHostFree(ctx->pin)); ctx->pin = nullptr; ctx->pin_bytes = 0; }
-    size_t want = bytes + 4096;
-    CANVAS_HIP_TRY(ctx, hipHostMalloc(&ctx->pin, want, hipHostMallocDefault));
-    ctx->pin_bytes = want;
-    return CANVAS_OK;
-}
+static inline int32_t canvas_pin_reserve(canvas_ctx* ctx, size_t bytes) { return cvx_grow_pinned(ctx, &ctx->pin, &ctx->pin_bytes, bytes, bytes + 4096); }
 
 // ---- internal cross-file entry points (hidden: not part of the C ABI)
 #define CVX_INTERNAL __attribute__((visibility("hidden")))
@@ -250,17 +257,6 @@ static inline int32_t canvas_upload_fence(canvas_ctx* ctx) {
     if (ctx->up_active) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->copy)); ctx->up_active = false; }
     return CANVAS_OK;
 }
-
-// bump allocator over the workspace
-struct WsCarver {
-    char* base; size_t off = 0;
-    explicit WsCarver(void* p) : base((char*)p) {}
-    template <class T> T* take(size_t n) { off = (off + 255) & ~size_t(255); T* r = (T*)(base + off); off += n * sizeof(T); return r; }
-};
-struct WsSizer {
-    size_t off = 0;
-    template <class T> void take(size_t n) { off = (off + 255) & ~size_t(255); off += n * sizeof(T); }
-};
 
 // ---- device helpers ------------------------------------------------------------------------------------------
 #define WAVE 64

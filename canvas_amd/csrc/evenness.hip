@@ -100,10 +100,8 @@ extern "C" int32_t canvas_evenness_score(canvas_ctx* ctx, int32_t nchr, const do
     if (nIqr < 2 || wins.size() == nIqr) return CANVAS_OK;            // Quartiles / Median throw in the reference: no score (WaveletsRunner.cs:58-67)
     if (!d_cov) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_evenness_score: no coverage");
     const size_t nw = wins.size();
-    WsSizer sz; sz.take<EvWindow>(nw); sz.take<double>(nw); sz.take<int>(1);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    EvWindow* dWins = ws.take<EvWindow>(nw); double* dScore = ws.take<double>(nw); int* dStatus = ws.take<int>(1);
+    EvWindow* dWins; double* dScore; int* dStatus;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) { ws.take(dWins, nw); ws.take(dScore, nw); ws.take(dStatus, 1); }); if (rc) return rc;
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dWins, wins.data(), nw * sizeof(EvWindow), hipMemcpyHostToDevice, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dStatus, 0, 4, ctx->stream));
     hipLaunchKernelGGL(k_evenness_windows, dim3((unsigned)nw), dim3(256), 0, ctx->stream, d_cov, dWins, dScore, dStatus);

@@ -295,16 +295,15 @@ extern "C" int32_t canvas_fragments_from_bam(canvas_ctx* ctx, const uint8_t* d_r
     uint64_t slots = 1024; while (slots < 2ull * (uint64_t)nitems) slots <<= 1;
     // the new carry: at most one entry per item, its name no longer than the item's — the old carry's name bytes, and 254 per record at the most (bounded by the chunk)
     const uint64_t nameCap = ((uint64_t)carryUsed - (uint64_t)ncarry * FRAG_HDR_BYTES) + std::min<uint64_t>(nbytes, 254ull * (uint64_t)nrecords) + 8;
-    WsSizer sz; sz.take<unsigned long long>(FK_WORDS); sz.take<int32_t>((size_t)nbins); sz.take<FragRec>((size_t)nrecords); sz.take<int32_t>((size_t)slots); sz.take<int32_t>((size_t)nitems);
-    sz.take<int32_t>((size_t)nitems); sz.take<uint32_t>((size_t)nrecords); sz.take<FragHdr>((size_t)nitems); sz.take<uint8_t>((size_t)nameCap);
-    rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-    WsCarver cv(ctx->ws);
     FragArgs a;
     a.rec = d_records; a.nbytes = nbytes; a.offs = d_record_offsets; a.nrec = nrecords; a.refId = ref_id; a.binStart = d_bin_start; a.binStop = d_bin_stop; a.nbins = nbins; a.quality = quality_threshold;
     a.carry = d_carry; a.ncarry = ncarry; a.carryUsed = (uint64_t)carryUsed; a.state = (const long long*)d_state; a.hashMask = hashMask;
-    a.ctl = cv.take<unsigned long long>(FK_WORDS); a.prefMax = cv.take<int32_t>((size_t)nbins); a.summary = cv.take<FragRec>((size_t)nrecords); a.head = cv.take<int32_t>((size_t)slots);
-    a.slotMask = (uint32_t)(slots - 1); a.next = cv.take<int32_t>((size_t)nitems); a.leader = cv.take<int32_t>((size_t)nitems); a.ev = cv.take<uint32_t>((size_t)nrecords);
-    a.newHdr = cv.take<FragHdr>((size_t)nitems); a.newNames = cv.take<uint8_t>((size_t)nameCap); a.nameCap = nameCap;
+    a.slotMask = (uint32_t)(slots - 1); a.nameCap = nameCap;
+    rc = cvx_ws_carve(ctx, 256, [&](WsCarver& cv) {
+        cv.take(a.ctl, FK_WORDS); cv.take(a.prefMax, (size_t)nbins); cv.take(a.summary, (size_t)nrecords); cv.take(a.head, (size_t)slots);
+        cv.take(a.next, (size_t)nitems); cv.take(a.leader, (size_t)nitems); cv.take(a.ev, (size_t)nrecords); cv.take(a.newHdr, (size_t)nitems); cv.take(a.newNames, (size_t)nameCap);
+    });
+    if (rc) return rc;
     {
         ProfScope ps(ctx, "fragments_from_bam", true);
         CANVAS_HIP_TRY(ctx, hipMemsetAsync(a.ctl, 0, FK_WORDS * 8, ctx->stream));

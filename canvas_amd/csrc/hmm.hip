@@ -1552,17 +1552,10 @@ static HmmLists hmm_lists(int32_t nchr, const int64_t* h_chr_offset) {
 enum { BB_MODE_CHAIN = 0, BB_MODE_SCAN = 1, BB_MODE_PIECES = 2 };
 struct BbWork { double* chunkSum; double* chunkBase; BbChunkOut* chunkOut; BbCross* cross; ParFn* at64Fn; uint8_t* at64Rank; unsigned long long* chunkBits; BbPost* post; };
 // (a chunk keeps BB_MAXC crossings: one with more sets the fail word, and k_bb_emit clamps the rank it reads to the records that exist)
-static void bb_work_size(WsSizer& sz, int nchunks) {
-    sz.take<double>(nchunks + 1); sz.take<double>(nchunks + 1); sz.take<BbChunkOut>(nchunks + 1);
-    sz.take<BbCross>((size_t)nchunks * BB_MAXC + 1); sz.take<ParFn>((size_t)nchunks * 16 + 1); sz.take<uint8_t>((size_t)nchunks * 16 + 8);
-    sz.take<unsigned long long>(nchunks + 1); sz.take<BbPost>((size_t)nchunks * BB_MAXC + 1);
-}
-static BbWork bb_work_carve(WsCarver& ws, int nchunks) {
-    BbWork W;
-    W.chunkSum = ws.take<double>(nchunks + 1); W.chunkBase = ws.take<double>(nchunks + 1); W.chunkOut = ws.take<BbChunkOut>(nchunks + 1);
-    W.cross = ws.take<BbCross>((size_t)nchunks * BB_MAXC + 1); W.at64Fn = ws.take<ParFn>((size_t)nchunks * 16 + 1); W.at64Rank = ws.take<uint8_t>((size_t)nchunks * 16 + 8);
-    W.chunkBits = ws.take<unsigned long long>(nchunks + 1); W.post = ws.take<BbPost>((size_t)nchunks * BB_MAXC + 1);
-    return W;
+static void bb_work_layout(WsCarver& ws, BbWork& W, int nchunks) {
+    ws.take(W.chunkSum, nchunks + 1); ws.take(W.chunkBase, nchunks + 1); ws.take(W.chunkOut, nchunks + 1);
+    ws.take(W.cross, (size_t)nchunks * BB_MAXC + 1); ws.take(W.at64Fn, (size_t)nchunks * 16 + 1); ws.take(W.at64Rank, (size_t)nchunks * 16 + 8);
+    ws.take(W.chunkBits, nchunks + 1); ws.take(W.post, (size_t)nchunks * BB_MAXC + 1);
 }
 static void enqueue_backbone(canvas_ctx* ctx, int mode, int nchr, int nchunks, const HmmChrom* dChroms, const BbChunk* dBChunks, const int32_t* dFirstChunk, const double* dV,
                              double* dCarry, int32_t* dFail, const int32_t* dTodo, const BbWork& W) {
@@ -1622,8 +1615,8 @@ struct HmmEmis { int32_t* idx = nullptr; double* dTab = nullptr;
 struct SegPost { const int32_t* d_start; const int32_t* d_stop; int32_t maxDist; int32_t* d_segment_id; int64_t nseg = 0; bool valid = false; };
 static void enqueue_segment_ids(canvas_ctx* ctx, const int64_t* dOff, int nchr, const int32_t* d_state, const int32_t* d_start, const int32_t* d_stop, int64_t N, int32_t maxDist,
                                 uint8_t* flags, uint32_t* blockCnt, unsigned long long* dTot, int32_t* d_segment_id, unsigned* totSeq = nullptr, unsigned seq = 0);
-template <class PrepareA, class PrepareB>
-static int32_t hmm_pipeline(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_offset, size_t extraBytes, PrepareA prepareA, PrepareB prepareB, int32_t* d_state, SegPost* seg = nullptr,
+template <class ModeLayout, class PrepareA, class PrepareB>
+static int32_t hmm_pipeline(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_offset, ModeLayout modeLayout /* the mode's own buffers, carved behind the common ones */, PrepareA prepareA, PrepareB prepareB, int32_t* d_state, SegPost* seg = nullptr,
                             bool descByValue = false /* prepareA launches nothing that reads the descriptor tables: they may arrive with the set-up kernel */) {
     const int64_t N = h_chr_offset[nchr];
     VitCorrupt corrupt;                  // (test hook, refused before anything is launched when it does not name a back-pointer of this call)
@@ -1633,40 +1626,32 @@ static int32_t hmm_pipeline(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_
     const std::vector<int32_t>&firstBlock = L.firstBlock, &firstGroup = L.firstGroup, &firstS = L.firstS, &firstChunk = L.firstChunk;
     const int nblocks = L.nblocks, ngroups = L.ngroups, nblocksS = L.nblocksS, nchunks = L.nchunks;
     const int nbSeg = (int)nblk2(N, 2048);
-    WsSizer sz;
-    sz.take<BbChunk>(nchunks + 1); sz.take<int32_t>(nchr + 1); bb_work_size(sz, nchunks);
-    sz.take<uint16_t>(N + 8); sz.take<HmmChrom>(nchr); sz.take<int32_t>(nchr);
-    sz.take<int32_t>(nchr + 1); sz.take<uint16_t>(nblocks + 8); sz.take<int8_t>(nblocks + 8);
-    sz.take<int64_t>(nchr + 1); sz.take<VitBlock>(nblocks + 1); sz.take<double>(N); sz.take<double>(N + 64); sz.take<int32_t>(nchr); sz.take<int32_t>(nchr);
-    sz.take<VitBlock>(nblocksS + 1); sz.take<uint16_t>(nblocksS + 8); sz.take<int32_t>(nchr + 1);
-    sz.take<int32_t>(nchr + 1); sz.take<uint16_t>(nblocks + 8); sz.take<uint16_t>(ngroups + 8); sz.take<int8_t>(ngroups + 8);
-    sz.take<char>(8 * 256 + (size_t)nchr * 64 + 64);
-    if (seg) { sz.take<uint8_t>(N + 16); sz.take<uint32_t>(nbSeg + 1); sz.take<unsigned long long>(1); }
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + extraBytes + 65536); if (rc) return rc;
-    rc = canvas_pin_reserve(ctx, (size_t)nchr * 4 + 64); if (rc) return rc;         // verification flags (+ the segment count and its mailbox stamp) come back here
-    WsCarver ws(ctx->ws);
-    uint16_t* psi = ws.take<uint16_t>(N + 8);
-    HmmChrom* dChroms = ws.take<HmmChrom>(nchr); int32_t* dLast = ws.take<int32_t>(nchr);
-    int32_t* dFirst = ws.take<int32_t>(nchr + 1);
-    uint16_t* dMaps = ws.take<uint16_t>(nblocks + 8); (void)ws.take<int8_t>(nblocks + 8);
-    int64_t* dOffDev = ws.take<int64_t>(nchr + 1);
-    VitBlock* dVBlocks = ws.take<VitBlock>(nblocks + 1); double* dD = ws.take<double>(N); double* dCarry = ws.take<double>(N + 64); int32_t* dFail = ws.take<int32_t>(nchr); int32_t* dRedo = ws.take<int32_t>(nchr);
-    int32_t* dFirstGroup = ws.take<int32_t>(nchr + 1); uint16_t* dPre = ws.take<uint16_t>(nblocks + 8); uint16_t* dGmap = ws.take<uint16_t>(ngroups + 8);
-    int8_t* dGentry = ws.take<int8_t>(ngroups + 8);
-    VitBlock* dSBlocks = ws.take<VitBlock>(nblocksS + 1); uint16_t* dMapsS = ws.take<uint16_t>(nblocksS + 8); int32_t* dFirstS = ws.take<int32_t>(nchr + 1);
-    BbChunk* dBChunks = ws.take<BbChunk>(nchunks + 1); int32_t* dFirstChunk = ws.take<int32_t>(nchr + 1);
-    const BbWork bbWork = bb_work_carve(ws, nchunks);
+    // static descriptors: six small tables in one blob, by value with the set-up kernel (<= HMM_BYVAL chromosomes) or in ONE packed upload
+    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t oCh = 0, oFirst = al((size_t)nchr * sizeof(HmmChrom)), oOff = oFirst + al((size_t)(nchr + 1) * 4), oChunk = oOff + al((size_t)(nchr + 1) * 8),
+                 oS = oChunk + al((size_t)(nchr + 1) * 4), oG = oS + al((size_t)(nchr + 1) * 4), total = oG + al((size_t)(nchr + 1) * 4);
+    uint16_t *psi, *dMaps, *dPre, *dGmap, *dMapsS; int32_t *dLast, *dFail, *dRedo; VitBlock *dVBlocks, *dSBlocks; double *dD, *dCarry; int8_t* dGentry; BbChunk* dBChunks; BbWork bbWork; char* dBlob;
     uint8_t* segFlags = nullptr; uint32_t* segBlockCnt = nullptr; unsigned long long* segTot = nullptr;
-    if (seg) { segFlags = ws.take<uint8_t>(N + 16); segBlockCnt = ws.take<uint32_t>(nbSeg + 1); segTot = ws.take<unsigned long long>(1); seg->valid = false; }
-
-    // static descriptors: six small tables, by value with the set-up kernel (<= HMM_BYVAL chromosomes) or in ONE packed upload
+    int32_t rc = cvx_ws_carve(ctx, 65536, [&](WsCarver& ws) {
+        // (the takes without a name are room that earlier forms of the descriptor tables used: kept, so that every buffer stays where it was)
+        ws.take(psi, N + 8); ws.take<HmmChrom>(nchr); ws.take(dLast, nchr); ws.take<int32_t>(nchr + 1); ws.take(dMaps, nblocks + 8); ws.take<int8_t>(nblocks + 8); ws.take<int64_t>(nchr + 1);
+        ws.take(dVBlocks, nblocks + 1); ws.take(dD, N); ws.take(dCarry, N + 64); ws.take(dFail, nchr); ws.take(dRedo, nchr);
+        ws.take<int32_t>(nchr + 1); ws.take(dPre, nblocks + 8); ws.take(dGmap, ngroups + 8); ws.take(dGentry, ngroups + 8);
+        ws.take(dSBlocks, nblocksS + 1); ws.take(dMapsS, nblocksS + 8); ws.take<int32_t>(nchr + 1);
+        ws.take(dBChunks, nchunks + 1); ws.take<int32_t>(nchr + 1);
+        bb_work_layout(ws, bbWork, nchunks);
+        if (seg) { ws.take(segFlags, N + 16); ws.take(segBlockCnt, nbSeg + 1); ws.take(segTot, 1); }
+        ws.take(dBlob, total);
+        modeLayout(ws);
+    });
+    if (rc) return rc;
+    rc = canvas_pin_reserve(ctx, (size_t)nchr * 4 + 64); if (rc) return rc;         // verification flags (+ the segment count and its mailbox stamp) come back here
+    if (seg) seg->valid = false;
+    HmmChrom* dChroms = (HmmChrom*)(dBlob + oCh); int32_t* dFirst = (int32_t*)(dBlob + oFirst); int64_t* dOffDev = (int64_t*)(dBlob + oOff); int32_t* dFirstChunk = (int32_t*)(dBlob + oChunk);
+    int32_t* dFirstS = (int32_t*)(dBlob + oS); int32_t* dFirstGroup = (int32_t*)(dBlob + oG);
     const bool byVal = descByValue && nchr <= HMM_BYVAL;
     HmmDescPack pack;
     {
-        auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-        const size_t oCh = 0, oFirst = al((size_t)nchr * sizeof(HmmChrom)), oOff = oFirst + al((size_t)(nchr + 1) * 4), oChunk = oOff + al((size_t)(nchr + 1) * 8),
-                     oS = oChunk + al((size_t)(nchr + 1) * 4), oG = oS + al((size_t)(nchr + 1) * 4), total = oG + al((size_t)(nchr + 1) * 4);
-        char* dBlob = ws.take<char>(total);
         if (byVal) {
             memset(&pack, 0, sizeof pack);
             memcpy(pack.chroms, chroms.data(), (size_t)nchr * sizeof(HmmChrom)); memcpy(pack.off, h_chr_offset, (size_t)(nchr + 1) * 8); memcpy(pack.first, firstBlock.data(), (size_t)(nchr + 1) * 4);
@@ -1678,20 +1663,18 @@ static int32_t hmm_pipeline(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_
             memcpy(blob.data() + oS, firstS.data(), (size_t)(nchr + 1) * 4); memcpy(blob.data() + oG, firstGroup.data(), (size_t)(nchr + 1) * 4);
             rc = canvas_h2d_small(ctx, dBlob, blob.data(), total); if (rc) return rc;
         }
-        dChroms = (HmmChrom*)(dBlob + oCh); dFirst = (int32_t*)(dBlob + oFirst); dOffDev = (int64_t*)(dBlob + oOff); dFirstChunk = (int32_t*)(dBlob + oChunk);
-        dFirstS = (int32_t*)(dBlob + oS); dFirstGroup = (int32_t*)(dBlob + oG);
     }
     // phase A of the mode: everything the set-up kernel needs (PerSampleHMM: the threshold); phase B: the emission tables, computed on the host while the set-up kernel runs
     HmmParams P; HmmEmis E;
     ctx->hmm_dispersion = 1e9;          // (prepareA of the per-sample model sets it; the joint model keeps the long first lead-in)
-    rc = prepareA(ws, P, E, (const HmmChrom*)dChroms, (const int64_t*)dOffDev); if (rc) return rc;
+    rc = prepareA(P, E, (const HmmChrom*)dChroms, (const int64_t*)dOffDev); if (rc) return rc;
     {
         const int64_t most = std::max<int64_t>(std::max<int64_t>(E.indexCov ? N : 0, nblocks), std::max<int64_t>(std::max(nblocksS, nchunks), nchr));
         HmmDescDev DD{dChroms, dOffDev, dFirst, dFirstChunk, dFirstS, dFirstGroup};
         hipLaunchKernelGGL((k_hmm_setup<VitBlock, BbChunk>), dim3(nblk2(most, 256)), dim3(256), 0, ctx->stream, pack, byVal ? 1 : 0, DD, nchr, nblocks, nblocksS, nchunks, VB, VBS, BB_CHUNK,
                            dVBlocks, dSBlocks, dBChunks, E.indexCov, N, P.maxThreshold, E.idx, dLast, dFail);
     }
-    rc = prepareB(ws, P, E); if (rc) return rc;
+    rc = prepareB(P, E); if (rc) return rc;
     int32_t* idx = E.idx; double* dTab = E.dTab;
     size_t tabBytes = (size_t)NSTATE * P.tableLen * 8;
     size_t lds = tabBytes <= 48 * 1024 ? tabBytes : 0;
@@ -1810,13 +1793,13 @@ static int32_t hmm_per_sample_impl(canvas_ctx* ctx, int32_t nchr, const double* 
     const int64_t N = h_chr_offset[nchr];
     // nAll / d_cov_all: the genome the quartiles are taken over (the whole sample; == the chromosomes handled here unless the sample is sharded)
     if (nAll < 5) CANVAS_FAIL(ctx, CANVAS_ERR_UNSUPPORTED, "HMM: fewer than 5 bins genome-wide (Quartiles would throw in the reference)");
-    WsSizer ex; ex.take<uint32_t>(nAll); ex.take<int32_t>(N + 256); ex.take<double>(NSTATE * 70000); ex.take<CovQ>(1); ex.take<uint32_t>(CQ_WIN);
+    uint32_t *keys, *dWin; int32_t* idx; double* dTab; CovQ* dQ;   // idx: padded for the group loads of k_vit_spec
+    auto modeLayout = [&](WsCarver& ws) { ws.take(keys, nAll); ws.take(idx, N + 256); ws.take(dTab, NSTATE * 70000); ws.take(dQ, 1); ws.take(dWin, CQ_WIN); };
     double haploidMean = 0, pseudoVariance = 0;
     std::vector<double> tab;
     struct Joiner { NbPool* p = nullptr; ~Joiner() { if (p) p->finish(); } } joiner;      // (an early return must not leave helpers writing into `tab`)
-    auto prepareA = [&](WsCarver& ws, HmmParams& P, HmmEmis& E, const HmmChrom*, const int64_t*) -> int32_t {
+    auto prepareA = [&](HmmParams& P, HmmEmis& E, const HmmChrom*, const int64_t*) -> int32_t {
         int32_t rc;
-        uint32_t* keys = ws.take<uint32_t>(nAll); int32_t* idx = ws.take<int32_t>(N + 256); double* dTab = ws.take<double>(NSTATE * 70000);   // idx: padded for the group loads of k_vit_spec
     // 1. genome-wide quartiles of (float)coverage (HiddenMarkovModelsRunner.cs:36-50): by counting when the coverage is F2 text (k_covq_hist), by the radix select otherwise
     //    (CANVAS_HMM_RADIX_SELECT=1 forces the latter: test hook, both must agree)
     int64_t qidx[6]; int nq;
@@ -1829,7 +1812,6 @@ static int32_t hmm_per_sample_impl(canvas_ctx* ctx, int32_t nchr, const double* 
         if (same && !preQ->bad && !preQ->fail) for (int k = 0; k < nq; k++) v[k] = (float)((double)preQ->resultK[k] / 100.0);
         else radix = true;
     } else if (!radix) {
-        CovQ* dQ = ws.take<CovQ>(1); uint32_t* dWin = ws.take<uint32_t>(CQ_WIN);
         CovQ hQ; memset(&hQ, 0, sizeof hQ); hQ.nq = (uint32_t)nq;
         for (int k = 0; k < nq; k++) hQ.rank[k] = (unsigned long long)qidx[k];
         rc = canvas_h2d_small(ctx, dQ, &hQ, sizeof hQ); if (rc) return rc;
@@ -1873,7 +1855,7 @@ static int32_t hmm_per_sample_impl(canvas_ctx* ctx, int32_t nchr, const double* 
         joiner.p->submit(jobs, NSTATE);
         return CANVAS_OK;
     };
-    auto prepareB = [&](WsCarver&, HmmParams& P, HmmEmis& E) -> int32_t {
+    auto prepareB = [&](HmmParams& P, HmmEmis& E) -> int32_t {
     std::static_pointer_cast<NbPool>(ctx->hmm_pool)->finish();
     const double selfTransition = 0.99;
     for (int i = 0; i < NSTATE; i++) {
@@ -1883,7 +1865,7 @@ static int32_t hmm_per_sample_impl(canvas_ctx* ctx, int32_t nchr, const double* 
     // 3. Viterbi and backtrack: hmm_pipeline
         return canvas_h2d_small(ctx, E.dTab, tab.data(), tab.size() * 8);          // (through the pinned staging area: `tab` is a local)
     };
-    return hmm_pipeline(ctx, nchr, h_chr_offset, ex.off, prepareA, prepareB, d_state, seg, true);
+    return hmm_pipeline(ctx, nchr, h_chr_offset, modeLayout, prepareA, prepareB, d_state, seg, true);
 }
 int32_t canvas_hmm_per_sample(canvas_ctx* ctx, int32_t nchr, const double* d_cov, const int64_t* h_chr_offset, int32_t* d_state) {
     if (!ctx) return CANVAS_ERR_INVALID;
@@ -2018,10 +2000,9 @@ extern "C" int32_t canvas_hmm_joint(canvas_ctx* ctx, int32_t nsamples, int32_t n
     }
     JointCombos K; genotype_combinations(S, K);
     // ---- phase 2 inside the shared pipeline: indices, tables, per-bin maxima, host log, then Viterbi
-    WsSizer ex; ex.take<int32_t>(N + 256); ex.take<int32_t>((size_t)S * N); ex.take<double>((size_t)NSTATE * N); ex.take<double>(nCS * NSTATE * strideUb); ex.take<double>(nchr); ex.take<int32_t>(nchr);
-    auto prepare = [&](WsCarver& ws, HmmParams& P, HmmEmis& E, const HmmChrom* dChroms, const int64_t* dOffDev) -> int32_t {
-        int32_t* idx = ws.take<int32_t>(N + 256); int32_t* idxS = ws.take<int32_t>((size_t)S * N); double* dL = ws.take<double>((size_t)NSTATE * N);
-        double* dPmf = ws.take<double>(nCS * NSTATE * strideUb); double* dThr = ws.take<double>(nchr); int32_t* dMaxIdx = ws.take<int32_t>(nchr);
+    int32_t *idx, *idxS, *dMaxIdx; double *dL, *dPmf, *dThr;
+    auto modeLayout = [&](WsCarver& ws) { ws.take(idx, N + 256); ws.take(idxS, (size_t)S * N); ws.take(dL, (size_t)NSTATE * N); ws.take(dPmf, nCS * NSTATE * strideUb); ws.take(dThr, nchr); ws.take(dMaxIdx, nchr); };
+    auto prepare = [&](HmmParams& P, HmmEmis& E, const HmmChrom* dChroms, const int64_t* dOffDev) -> int32_t {
         int32_t rc = canvas_h2d_small(ctx, dThr, thr.data(), nchr * 8); if (rc) return rc;
         CANVAS_HIP_TRY(ctx, hipMemsetAsync(dMaxIdx, 0, nchr * 4, ctx->stream));
         hipLaunchKernelGGL(k_joint_index, dim3(nblk2(N, 256)), dim3(256), 0, ctx->stream, ptrs, S, dOffDev, nchr, dThr, N, idxS, dMaxIdx);
@@ -2058,7 +2039,7 @@ extern "C" int32_t canvas_hmm_joint(canvas_ctx* ctx, int32_t nsamples, int32_t n
         E.idx = idx; E.dTab = dL;
         return CANVAS_OK;
     };
-    return hmm_pipeline(ctx, nchr, h_chr_offset, ex.off, prepare, [](WsCarver&, HmmParams&, HmmEmis&) -> int32_t { return CANVAS_OK; }, d_state);
+    return hmm_pipeline(ctx, nchr, h_chr_offset, modeLayout, prepare, [](HmmParams&, HmmEmis&) -> int32_t { return CANVAS_OK; }, d_state);
 }
 
 // ---------------------------------------------------------------- canvas_hmm_backbone_probe: the exact backbone on caller-supplied increments (tests/test_hmm_backbone_gpu.py)
@@ -2075,11 +2056,8 @@ extern "C" int32_t canvas_hmm_backbone_probe(canvas_ctx* ctx, int32_t mode, int3
     const int nchunks = L.nchunks;
     if (nchunks == 0) return CANVAS_OK;                // every chromosome is skipped (at most ten steps)
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    WsSizer sz; sz.take<HmmChrom>(nchr); sz.take<int32_t>(nchr + 1); sz.take<BbChunk>(nchunks + 1); sz.take<int32_t>(nchr); bb_work_size(sz, nchunks);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 65536); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    HmmChrom* dChroms = ws.take<HmmChrom>(nchr); int32_t* dFirstChunk = ws.take<int32_t>(nchr + 1); BbChunk* dBChunks = ws.take<BbChunk>(nchunks + 1); int32_t* dFail = ws.take<int32_t>(nchr);
-    const BbWork W = bb_work_carve(ws, nchunks);
+    HmmChrom* dChroms; int32_t *dFirstChunk, *dFail; BbChunk* dBChunks; BbWork W;
+    int32_t rc = cvx_ws_carve(ctx, 65536, [&](WsCarver& ws) { ws.take(dChroms, nchr); ws.take(dFirstChunk, nchr + 1); ws.take(dBChunks, nchunks + 1); ws.take(dFail, nchr); bb_work_layout(ws, W, nchunks); }); if (rc) return rc;
     rc = canvas_h2d_small(ctx, dChroms, L.chroms.data(), (size_t)nchr * sizeof(HmmChrom)); if (rc) return rc;
     rc = canvas_h2d_small(ctx, dFirstChunk, L.firstChunk.data(), (size_t)(nchr + 1) * 4); if (rc) return rc;
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dFail, 0, (size_t)nchr * 4, ctx->stream));
@@ -2119,14 +2097,13 @@ int32_t canvas_segment_ids_ploidy(canvas_ctx* ctx, int32_t nchr, const int64_t* 
     if (h_ploidy_offset && npl > 0 && (!h_ploidy_start || !h_ploidy_end || !h_ploidy_cn)) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_segment_ids_ploidy: missing ploidy arrays");
     for (int64_t k = 0; k < npl; k++) if (h_ploidy_cn[k] < 0 || h_ploidy_cn[k] > 4)
         CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "reference ploidy outside 0..4 (PloidyInfo.getPloidyCounts indexes a 5-element array: the reference throws)");
-    WsSizer sz; sz.take<int64_t>(nchr + 1); sz.take<uint8_t>(N); sz.take<uint32_t>(nb + 1); sz.take<unsigned long long>(1);
-    sz.take<int64_t>(nchr + 1); sz.take<int32_t>(nex + 1); sz.take<int32_t>(nex + 1);
-    sz.take<int64_t>(nchr + 1); sz.take<int32_t>(npl + 1); sz.take<int32_t>(npl + 1); sz.take<int32_t>(npl + 1);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    int64_t* dOff = ws.take<int64_t>(nchr + 1); uint8_t* flags = ws.take<uint8_t>(N); uint32_t* blockCnt = ws.take<uint32_t>(nb + 1); unsigned long long* dTot = ws.take<unsigned long long>(1);
-    int64_t* dExOff = ws.take<int64_t>(nchr + 1); int32_t* dExStart = ws.take<int32_t>(nex + 1); int32_t* dExStop = ws.take<int32_t>(nex + 1);
-    int64_t* dPlOff = ws.take<int64_t>(nchr + 1); int32_t* dPlStart = ws.take<int32_t>(npl + 1); int32_t* dPlEnd = ws.take<int32_t>(npl + 1); int32_t* dPlCn = ws.take<int32_t>(npl + 1);
+    int64_t *dOff, *dExOff, *dPlOff; uint8_t* flags; uint32_t* blockCnt; unsigned long long* dTot; int32_t *dExStart, *dExStop, *dPlStart, *dPlEnd, *dPlCn;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) {
+        ws.take(dOff, nchr + 1); ws.take(flags, N); ws.take(blockCnt, nb + 1); ws.take(dTot, 1);
+        ws.take(dExOff, nchr + 1); ws.take(dExStart, nex + 1); ws.take(dExStop, nex + 1);
+        ws.take(dPlOff, nchr + 1); ws.take(dPlStart, npl + 1); ws.take(dPlEnd, npl + 1); ws.take(dPlCn, npl + 1);
+    });
+    if (rc) return rc;
     if (h_ploidy_offset) {
         CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dPlOff, h_ploidy_offset, (nchr + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         if (npl > 0) { CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dPlStart, h_ploidy_start, npl * 4, hipMemcpyHostToDevice, ctx->stream));

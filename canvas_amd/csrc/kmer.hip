@@ -240,14 +240,12 @@ extern "C" int32_t canvas_flag_unique_kmers(canvas_ctx* ctx, int32_t nchr, const
     { int32_t rcf = canvas_upload_fence(ctx); if (rcf) return rcf; }
 
     // ---- device tables: contigs, class histogram, counters, one pass's class table
-    WsSizer sz; sz.take<int64_t>((size_t)nchr + 1); sz.take<int64_t>((size_t)nchr); sz.take<const uint8_t*>((size_t)nchr); sz.take<uint64_t*>((size_t)nchr);
-    sz.take<unsigned long long>(KMER_CLASSES); sz.take<unsigned long long>(KMER_ST_N); sz.take<KmerClassSlot>(KMER_CLASSES);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-    WsCarver cv(ctx->ws);
-    int64_t* dWordOff = cv.take<int64_t>((size_t)nchr + 1); int64_t* dLen = cv.take<int64_t>((size_t)nchr);
-    const uint8_t** dBases = cv.take<const uint8_t*>((size_t)nchr); uint64_t** dMask = cv.take<uint64_t*>((size_t)nchr);
-    unsigned long long* dHist = cv.take<unsigned long long>(KMER_CLASSES); unsigned long long* dStats = cv.take<unsigned long long>(KMER_ST_N);
-    KmerClassSlot* dClasses = cv.take<KmerClassSlot>(KMER_CLASSES);
+    int64_t *dWordOff, *dLen; const uint8_t** dBases; uint64_t** dMask; unsigned long long *dHist, *dStats; KmerClassSlot* dClasses;
+    int32_t rc = cvx_ws_carve(ctx, 256, [&](WsCarver& cv) {
+        cv.take(dWordOff, (size_t)nchr + 1); cv.take(dLen, (size_t)nchr); cv.take(dBases, (size_t)nchr); cv.take(dMask, (size_t)nchr);
+        cv.take(dHist, KMER_CLASSES); cv.take(dStats, KMER_ST_N); cv.take(dClasses, KMER_CLASSES);
+    });
+    if (rc) return rc;
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dWordOff, wordOff.data(), ((size_t)nchr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dLen, h_len, (size_t)nchr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dBases, d_bases, (size_t)nchr * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));

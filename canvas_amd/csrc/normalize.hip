@@ -123,10 +123,8 @@ int32_t canvas_normalize_ratio(canvas_ctx* ctx, int64_t n, const float* d_sample
         CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_normalize_ratio: bad arguments");
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t nk = d_on_target_idx ? n_on_target : n, nblocks = (n + 255) / 256;
-    WsSizer sz; sz.take<unsigned long long>((size_t)nk); sz.take<uint32_t>((size_t)nblocks); sz.take<long long>(1);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    unsigned long long* dKeys = ws.take<unsigned long long>((size_t)nk); uint32_t* dBlock = ws.take<uint32_t>((size_t)nblocks); long long* dTotal = ws.take<long long>(1);
+    unsigned long long* dKeys; uint32_t* dBlock; long long* dTotal;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) { ws.take(dKeys, (size_t)nk); ws.take(dBlock, (size_t)nblocks); ws.take(dTotal, 1); }); if (rc) return rc;
     double lsf = 1;
     if (mode == 0) {                                  // LSNormRatioCalculator.cs:29-31
         double sm, rm;
@@ -310,11 +308,8 @@ int32_t canvas_normalize_best_normal(canvas_ctx* ctx, const double* d_tumor, int
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t nk = d_on_target_idx ? n_on_target : n;
     const int nb = (int)std::min<int64_t>(BLR2_BLOCKS, (nk + 255) / 256);
-    WsSizer sz; sz.take<unsigned long long>((size_t)nk); for (int a = 0; a < 3; a++) sz.take<double>((size_t)nb * nnormals);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    unsigned long long* dKeys = ws.take<unsigned long long>((size_t)nk);
-    double* dSum = ws.take<double>((size_t)nb * nnormals); double* dKept = ws.take<double>((size_t)nb * nnormals); double* dIgn = ws.take<double>((size_t)nb * nnormals);
+    unsigned long long* dKeys; double *dSum, *dKept, *dIgn; const size_t nPart = (size_t)nb * nnormals;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) { ws.take(dKeys, (size_t)nk); ws.take(dSum, nPart); ws.take(dKept, nPart); ws.take(dIgn, nPart); }); if (rc) return rc;
     // weight = 1 / OnTargetMedianBinCount, 0 when the median is not positive (BestLR2ReferenceGenerator.cs:41-58)
     auto weight_of = [&](const double* d, double& w) -> int32_t {
         hipLaunchKernelGGL(k_norm_keys_f64, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, d, d_on_target_idx, nk, dKeys);
@@ -383,17 +378,14 @@ int32_t canvas_normalize_pca_reference(canvas_ctx* ctx, int64_t n, const float* 
     const int npairs = naxes * (naxes - 1) / 2;
     const int64_t nblocks = (n + 255) / 256;
     const int nb = (int)std::min<int64_t>(256, nblocks);
-    WsSizer sz; sz.take<PcaTab>(1); sz.take<double>(PCA_MAX_AXES); sz.take<int2>((size_t)npairs + 1); sz.take<double>((size_t)npairs + 1);
-    sz.take<double>((size_t)nb * npairs + 1); sz.take<double>((size_t)nb * npairs + 1);
-    sz.take<double>((size_t)n); sz.take<float>((size_t)n); sz.take<int32_t>((size_t)n); sz.take<float>((size_t)n); sz.take<float>((size_t)n);
-    sz.take<unsigned long long>((size_t)n); sz.take<uint32_t>((size_t)nblocks); sz.take<long long>(1);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    PcaTab* dTab = ws.take<PcaTab>(1); double* dChain = ws.take<double>(PCA_MAX_AXES); int2* dPairs = ws.take<int2>((size_t)npairs + 1); double* dPairChain = ws.take<double>((size_t)npairs + 1);
-    double* dDot = ws.take<double>((size_t)nb * npairs + 1); double* dAbs = ws.take<double>((size_t)nb * npairs + 1);
-    double* dRef = ws.take<double>((size_t)n); float* dRefQ = ws.take<float>((size_t)n);
-    int32_t* dKeep = ws.take<int32_t>((size_t)n); float* dRatio = ws.take<float>((size_t)n); float* dCount = ws.take<float>((size_t)n);
-    unsigned long long* dKeys = ws.take<unsigned long long>((size_t)n); uint32_t* dBlock = ws.take<uint32_t>((size_t)nblocks); long long* dTotal = ws.take<long long>(1);
+    PcaTab* dTab; double *dChain, *dPairChain, *dDot, *dAbs, *dRef; int2* dPairs; float *dRefQ, *dRatio, *dCount; int32_t* dKeep; unsigned long long* dKeys; uint32_t* dBlock; long long* dTotal;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) {
+        ws.take(dTab, 1); ws.take(dChain, PCA_MAX_AXES); ws.take(dPairs, (size_t)npairs + 1); ws.take(dPairChain, (size_t)npairs + 1);
+        ws.take(dDot, (size_t)nb * npairs + 1); ws.take(dAbs, (size_t)nb * npairs + 1);
+        ws.take(dRef, (size_t)n); ws.take(dRefQ, (size_t)n); ws.take(dKeep, (size_t)n); ws.take(dRatio, (size_t)n); ws.take(dCount, (size_t)n);
+        ws.take(dKeys, (size_t)n); ws.take(dBlock, (size_t)nblocks); ws.take(dTotal, 1);
+    });
+    if (rc) return rc;
 
     PcaTab T; memset(&T, 0, sizeof T);
     for (int k = 0; k < naxes; k++) T.a[k] = h_d_axes[k];

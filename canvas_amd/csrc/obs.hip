@@ -144,10 +144,8 @@ extern "C" int32_t canvas_hits_from_bam(canvas_ctx* ctx, const uint8_t* d_record
     unsigned long long* dState = (unsigned long long*)d_state;
     if (nrecords > 0) {
         const int64_t ntiles = (nrecords + OBS_BLOCK - 1) / OBS_BLOCK;
-        WsSizer sz; sz.take<uint2>((size_t)nrecords); sz.take<int2>((size_t)ntiles);
-        int32_t rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-        WsCarver cv(ctx->ws);
-        uint2* summary = cv.take<uint2>((size_t)nrecords); int2* tiles = cv.take<int2>((size_t)ntiles);
+        uint2* summary; int2* tiles;
+        int32_t rc = cvx_ws_carve(ctx, 256, [&](WsCarver& cv) { cv.take(summary, (size_t)nrecords); cv.take(tiles, (size_t)ntiles); }); if (rc) return rc;
         uint32_t epoch = ++g_obs_epoch; if (epoch == 0) epoch = ++g_obs_epoch;
         ProfScope ps(ctx, "hits_from_bam", true);
         hipLaunchKernelGGL(k_obs_classify, dim3((unsigned)ntiles), dim3(OBS_BLOCK), 0, ctx->stream, d_records, nbytes, d_record_offsets, nrecords, ref_id, paired_end, epoch,

@@ -168,12 +168,11 @@ static int32_t ps_wait(canvas_ctx* ctx, const PsBuffers& B, unsigned long long* 
 template <class Extra> static int32_t ps_begin(canvas_ctx* ctx, int32_t nchr, const int64_t* h_chr_offset, long long n, PsBuffers& B, Extra&& extra) {
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     B.nb = (n + PS_BLOCK - 1) / PS_BLOCK;
-    WsSizer sz; sz.take<unsigned long long>(1); sz.take<long long>((size_t)nchr + 1); sz.take<unsigned char>((size_t)n); sz.take<unsigned>((size_t)B.nb); sz.take<unsigned>((size_t)B.nb + 1);
-    sz.take<unsigned>((size_t)nchr); extra(&sz, nullptr);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-    WsCarver cv(ctx->ws);
-    B.err = cv.take<unsigned long long>(1); B.chrOff = cv.take<long long>((size_t)nchr + 1); B.flags = cv.take<unsigned char>((size_t)n); B.blockCnt = cv.take<unsigned>((size_t)B.nb);
-    B.blockOff = cv.take<unsigned>((size_t)B.nb + 1); B.chrBase = cv.take<unsigned>((size_t)nchr); extra(nullptr, &cv);
+    int32_t rc = cvx_ws_carve(ctx, 256, [&](WsCarver& cv) {
+        cv.take(B.err, 1); cv.take(B.chrOff, (size_t)nchr + 1); cv.take(B.flags, (size_t)n); cv.take(B.blockCnt, (size_t)B.nb);
+        cv.take(B.blockOff, (size_t)B.nb + 1); cv.take(B.chrBase, (size_t)nchr); extra(cv);
+    });
+    if (rc) return rc;
     const unsigned long long none = PS_NONE;
     rc = canvas_h2d_small(ctx, B.err, &none, sizeof(none)); if (rc) return rc;
     { std::vector<long long> t(h_chr_offset, h_chr_offset + nchr + 1); rc = canvas_h2d_small(ctx, B.chrOff, t.data(), t.size() * sizeof(long long)); if (rc) return rc; }
@@ -193,7 +192,7 @@ extern "C" int32_t canvas_partition_states_cbs(canvas_ctx* ctx, int32_t nchr, co
     }
     if (!d_seg_len || !d_state) PS_REFUSE("bad arguments (null array)");
     PsBuffers B; int* dNseg = nullptr;
-    rc = ps_begin(ctx, nchr, h_chr_offset, n, B, [&](WsSizer* s, WsCarver* c) { if (s) s->take<int>((size_t)nchr); else dNseg = c->take<int>((size_t)nchr); }); if (rc) return rc;
+    rc = ps_begin(ctx, nchr, h_chr_offset, n, B, [&](WsCarver& cv) { cv.take(dNseg, (size_t)nchr); }); if (rc) return rc;
     rc = canvas_h2d_small(ctx, dNseg, h_nseg, (size_t)nchr * sizeof(int)); if (rc) return rc;
     unsigned long long err = PS_NONE;
     {
@@ -233,9 +232,7 @@ extern "C" int32_t canvas_partition_states_breakpoints(canvas_ctx* ctx, int32_t 
     if (n == 0) return CANVAS_OK;
     if (!d_state) PS_REFUSE("bad arguments (null array)");
     PsBuffers B; int* dBp = nullptr; long long* dBpOff = nullptr;
-    rc = ps_begin(ctx, nchr, h_chr_offset, n, B, [&](WsSizer* s, WsCarver* c) {
-        if (s) { s->take<int>((size_t)nbp + 1); s->take<long long>((size_t)nchr + 1); } else { dBp = c->take<int>((size_t)nbp + 1); dBpOff = c->take<long long>((size_t)nchr + 1); } });
-    if (rc) return rc;
+    rc = ps_begin(ctx, nchr, h_chr_offset, n, B, [&](WsCarver& cv) { cv.take(dBp, (size_t)nbp + 1); cv.take(dBpOff, (size_t)nchr + 1); }); if (rc) return rc;
     if (nbp > 0) { rc = canvas_h2d_small(ctx, dBp, h_breakpoints, (size_t)nbp * sizeof(int)); if (rc) return rc; }
     { std::vector<long long> t(h_bp_offset, h_bp_offset + nchr + 1); rc = canvas_h2d_small(ctx, dBpOff, t.data(), t.size() * sizeof(long long)); if (rc) return rc; }
     unsigned long long err = PS_NONE;

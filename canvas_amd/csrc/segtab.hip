@@ -126,13 +126,12 @@ extern "C" int32_t canvas_segment_tables(canvas_ctx* ctx, int64_t nbins, int32_t
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // there are at most nbins segments, and 2^31 and more are refused: the tables never hold more than that
     const size_t cap = (size_t)std::min<long long>(std::min<long long>(cap_seg, nbins), 0x7FFFFFFFll);
-    WsSizer sz; sz.take<StStat>(1); sz.take<long long>((size_t)nchr + 1); sz.take<unsigned char>((size_t)nbins); sz.take<unsigned>((size_t)nb); sz.take<unsigned long long>((size_t)nb + 1);
-    sz.take<long long>((size_t)nchr + 1); sz.take<int>(cap); sz.take<int>(cap); sz.take<long long>(cap + 1); sz.take<int>(4 * cap);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-    WsCarver cv(ctx->ws);
-    StStat* dSt = cv.take<StStat>(1); long long* dChrOff = cv.take<long long>((size_t)nchr + 1); unsigned char* dFlags = cv.take<unsigned char>((size_t)nbins);
-    unsigned* dBlockCnt = cv.take<unsigned>((size_t)nb); unsigned long long* dBlockOff = cv.take<unsigned long long>((size_t)nb + 1);
-    long long* dChrSeg = cv.take<long long>((size_t)nchr + 1); int* dBegin = cv.take<int>(cap); int* dEnd = cv.take<int>(cap); long long* dBinOff = cv.take<long long>(cap + 1); int* dCi = cv.take<int>(4 * cap);
+    StStat* dSt; long long *dChrOff, *dChrSeg, *dBinOff; unsigned char* dFlags; unsigned* dBlockCnt; unsigned long long* dBlockOff; int *dBegin, *dEnd, *dCi;
+    int32_t rc = cvx_ws_carve(ctx, 256, [&](WsCarver& cv) {
+        cv.take(dSt, 1); cv.take(dChrOff, (size_t)nchr + 1); cv.take(dFlags, (size_t)nbins); cv.take(dBlockCnt, (size_t)nb); cv.take(dBlockOff, (size_t)nb + 1);
+        cv.take(dChrSeg, (size_t)nchr + 1); cv.take(dBegin, cap); cv.take(dEnd, cap); cv.take(dBinOff, cap + 1); cv.take(dCi, 4 * cap);
+    });
+    if (rc) return rc;
     // the tables lie behind one another in the workspace (dChrSeg first): ONE copy brings them into a pinned image with the same layout, a second the flags
     const size_t outBytes = (size_t)((char*)(dCi + 4 * cap) - (char*)dChrSeg);
     rc = canvas_pin_reserve(ctx, 256 + outBytes); if (rc) return rc;

@@ -248,21 +248,13 @@ static int32_t radix_select(canvas_ctx* ctx, const K* d_keys, int nseg, const st
     auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
     const size_t oTiles = 0, oSegq = al(tiles.size() * sizeof(SelTile)), oK = oSegq + al(segq.size() * sizeof(SelSegQ)), oPrefix = oK + al((size_t)nq * 8),
                  devBytes = oPrefix + al((size_t)nq * 8), histBytes = (size_t)nq * 1024 * SEL_REP, pinBytes = oPrefix + al((size_t)nq * 8);
-    if (devBytes > ctx->sel_ws_bytes) {
-        if (ctx->sel_ws) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->sel_ws)); ctx->sel_ws = nullptr; ctx->sel_ws_bytes = 0; }
-        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->sel_ws, devBytes * 2)); ctx->sel_ws_bytes = devBytes * 2;
-    }
-    if (histBytes > ctx->sel_hist_bytes) {
-        // the histograms live in their own buffer and are zero at the start of every call: cleared here once, and k_select_pick clears every
-        // row it has read (all replicas, after the last pass too), so there is no per-call memset
-        if (ctx->sel_hist) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->sel_hist)); ctx->sel_hist = nullptr; ctx->sel_hist_bytes = 0; }
-        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->sel_hist, histBytes * 2)); ctx->sel_hist_bytes = histBytes * 2;
-        CANVAS_HIP_TRY(ctx, hipMemsetAsync(ctx->sel_hist, 0, ctx->sel_hist_bytes, ctx->stream));
-    }
-    if (pinBytes > ctx->sel_pin_bytes) {
-        if (ctx->sel_pin) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipHostFree(ctx->sel_pin)); ctx->sel_pin = nullptr; ctx->sel_pin_bytes = 0; }
-        CANVAS_HIP_TRY(ctx, hipHostMalloc(&ctx->sel_pin, pinBytes * 2, hipHostMallocDefault)); ctx->sel_pin_bytes = pinBytes * 2;
-    }
+    int32_t rcg = cvx_grow_device(ctx, &ctx->sel_ws, &ctx->sel_ws_bytes, devBytes, devBytes * 2, ctx->stream); if (rcg) return rcg;
+    // the histograms live in their own buffer and are zero at the start of every call: cleared once when the buffer grows, and k_select_pick clears every
+    // row it has read (all replicas, after the last pass too), so there is no per-call memset
+    const bool histGrows = histBytes > ctx->sel_hist_bytes;
+    rcg = cvx_grow_device(ctx, &ctx->sel_hist, &ctx->sel_hist_bytes, histBytes, histBytes * 2, ctx->stream); if (rcg) return rcg;
+    if (histGrows) CANVAS_HIP_TRY(ctx, hipMemsetAsync(ctx->sel_hist, 0, ctx->sel_hist_bytes, ctx->stream));
+    rcg = cvx_grow_pinned(ctx, &ctx->sel_pin, &ctx->sel_pin_bytes, pinBytes, pinBytes * 2, &ctx->stream); if (rcg) return rcg;
     char* d = (char*)ctx->sel_ws; char* h = (char*)ctx->sel_pin;
     SelTile* dTiles = (SelTile*)(d + oTiles); SelSegQ* dSegq = (SelSegQ*)(d + oSegq);
     unsigned long long* dK = (unsigned long long*)(d + oK); unsigned long long* dPrefix = (unsigned long long*)(d + oPrefix);

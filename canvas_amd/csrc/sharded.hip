@@ -169,6 +169,8 @@ int32_t shard_bin_size_hook(void* user, int nl, const long long* obs, const long
 }
 }  // namespace
 
+static int32_t shard_ws_reserve(canvas_ctx* ctx, size_t need) { return cvx_grow_device(ctx, &ctx->shard_ws, &ctx->shard_ws_bytes, need, need, ctx->stream); }
+
 // h_pos0 != NULL: d_bases / d_hits are the packed reference / hit planes of the owned chromosomes (canvas_bin_sample_packed), d_mask is not read
 static int32_t pipeline_sharded_impl(canvas_ctx* ctx, int32_t nchr, const int32_t* h_chr_owner, const uint8_t* const* d_bases, const uint64_t* const* d_mask,
                                      const uint8_t* const* d_hits, const int64_t* h_pos0, const int64_t* h_len, const uint8_t* h_chr_is_autosome, const uint8_t* h_chr_is_y,
@@ -209,10 +211,7 @@ static int32_t pipeline_sharded_impl(canvas_ctx* ctx, int32_t nchr, const int32_
     const size_t oFlags = need; need += al((size_t)capLocal);
     const size_t oBlk = need; need += al((size_t)nbLocal * 4);
     const size_t oCnt = need; need += 256;
-    if (need > ctx->shard_ws_bytes) {
-        if (ctx->shard_ws) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->shard_ws)); ctx->shard_ws = nullptr; ctx->shard_ws_bytes = 0; }
-        CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->shard_ws, need)); ctx->shard_ws_bytes = need;
-    }
+    { int32_t rcg = shard_ws_reserve(ctx, need); if (rcg) return rcg; }
     char* S = (char*)ctx->shard_ws;
     int32_t* lChr = (int32_t*)(S + oBins); int32_t* lStart = (int32_t*)(S + oBins + al((size_t)capLocal * 4)); int32_t* lStop = (int32_t*)(S + oBins + 2 * al((size_t)capLocal * 4));
     int32_t* lGc = (int32_t*)(S + oBins + 3 * al((size_t)capLocal * 4)); float* lCount = (float*)(S + oBins + 4 * al((size_t)capLocal * 4));
@@ -681,12 +680,6 @@ extern "C" int32_t canvas_wavelets_sharded(canvas_ctx* ctx, int32_t nchr, const 
 //                                  everybody's and runs the same intersection as canvas_merge_cleaned with the samples in rank order: the merged bin list (first sample's
 //                                  order, stop from the last sample) comes out identical on every rank, together with THIS rank's counts of the surviving bins.
 // The count exchange in front of the columns carries the status word: a rank that failed sends a negative count and every rank returns an error.
-static int32_t shard_ws_reserve(canvas_ctx* ctx, size_t need) {
-    if (need <= ctx->shard_ws_bytes) return CANVAS_OK;
-    if (ctx->shard_ws) { CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); CANVAS_HIP_TRY(ctx, hipFree(ctx->shard_ws)); ctx->shard_ws = nullptr; ctx->shard_ws_bytes = 0; }
-    CANVAS_HIP_TRY(ctx, hipMalloc(&ctx->shard_ws, need)); ctx->shard_ws_bytes = need;
-    return CANVAS_OK;
-}
 extern "C" int32_t canvas_allgather_host(canvas_ctx* ctx, const void* h_send, int64_t bytes_per_rank, void* h_recv) {
     if (!ctx) return CANVAS_ERR_INVALID;
     if (!h_send || !h_recv || bytes_per_rank <= 0 || bytes_per_rank > (1 << 24)) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_allgather_host: 1 .. 16 MiB per rank");

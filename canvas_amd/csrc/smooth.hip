@@ -178,9 +178,8 @@ extern "C" int32_t canvas_smooth(canvas_ctx* ctx, int32_t nchr, const int64_t* h
             }
         }
         if (items.size() > 0x7FFFFFFFull) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_smooth: too many tiles in one call");
-        WsSizer sz; sz.take<unsigned long long>(1); sz.take<SmItem>(items.size());
-        rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-        WsCarver cv(ctx->ws); unsigned long long* dBad = cv.take<unsigned long long>(1); SmItem* dItems = cv.take<SmItem>(items.size());
+        unsigned long long* dBad; SmItem* dItems;
+        rc = cvx_ws_carve(ctx, 256, [&](WsCarver& cv) { cv.take(dBad, 1); cv.take(dItems, items.size()); }); if (rc) return rc;
         CANVAS_HIP_TRY(ctx, hipMemsetAsync(dBad, 0xFF, sizeof(unsigned long long), ctx->stream));
         rc = canvas_h2d_small(ctx, dItems, items.data(), items.size() * sizeof(SmItem)); if (rc) return rc;
         {
@@ -192,13 +191,12 @@ extern "C" int32_t canvas_smooth(canvas_ctx* ctx, int32_t nchr, const int64_t* h
     }
 
     // ---- W = 0 (a copy) and the per-pass path
-    WsSizer sz; sz.take<unsigned long long>(1); sz.take<long long>((size_t)nchr + 1); sz.take<long long>((size_t)nchr); sz.take<long long>((size_t)nchr);
-    if (W > 1) { sz.take<float>((size_t)total); sz.take<float>((size_t)total); }
-    rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-    WsCarver cv(ctx->ws); unsigned long long* dBad = cv.take<unsigned long long>(1);
-    long long* dOff = cv.take<long long>((size_t)nchr + 1); long long* dCur = cv.take<long long>((size_t)nchr); long long* dNew = cv.take<long long>((size_t)nchr);
-    float* buf[2] = {nullptr, nullptr};
-    if (W > 1) { buf[0] = cv.take<float>((size_t)total); buf[1] = cv.take<float>((size_t)total); }
+    unsigned long long* dBad; long long *dOff, *dCur, *dNew; float* buf[2] = {nullptr, nullptr};
+    rc = cvx_ws_carve(ctx, 256, [&](WsCarver& cv) {
+        cv.take(dBad, 1); cv.take(dOff, (size_t)nchr + 1); cv.take(dCur, (size_t)nchr); cv.take(dNew, (size_t)nchr);
+        if (W > 1) { cv.take(buf[0], (size_t)total); cv.take(buf[1], (size_t)total); }
+    });
+    if (rc) return rc;
     const unsigned nblk = (unsigned)((total + SM_BLOCK - 1) / SM_BLOCK);
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dBad, 0xFF, sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_smooth_check, dim3(nblk), dim3(SM_BLOCK), 0, ctx->stream, d_count + off0, total, off0, dBad);

@@ -262,19 +262,16 @@ extern "C" int32_t canvas_somatic_model_fit(canvas_ctx* ctx, int64_t nseg, const
     // ---- upload
     t0 = std::chrono::steady_clock::now();
     const int K = pr.maximum_related_models;
-    WsSizer sz;
-    sz.take<double>((size_t)M * 2 * P); sz.take<double>((size_t)M * SOM_OUT); sz.take<int32_t>(K); sz.take<double>((size_t)K * SOM_OUT); sz.take<unsigned char>((size_t)K * S);
-    sz.take<int32_t>(S); sz.take<double>(S);
-    if (!inputs_on_device) { sz.take<double>(S); sz.take<double>(S); sz.take<double>(S); sz.take<int32_t>(S); }
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 256); if (rc) return rc;
-    WsCarver cv(ctx->ws);
-    double* dTable = cv.take<double>((size_t)M * 2 * P); double* dOut = cv.take<double>((size_t)M * SOM_OUT); int32_t* dList = cv.take<int32_t>(K);
-    double* dOutTop = cv.take<double>((size_t)K * SOM_OUT); unsigned char* dProfile = cv.take<unsigned char>((size_t)K * S);
-    int32_t* dSegPoint = cv.take<int32_t>(S); double* dSegDist = cv.take<double>(S);
+    double *dTable, *dOut, *dOutTop, *dSegDist, *dc, *dm, *dw; int32_t *dList, *dSegPoint, *dl; unsigned char* dProfile;
+    int32_t rc = cvx_ws_carve(ctx, 256, [&](WsCarver& cv) {
+        cv.take(dTable, (size_t)M * 2 * P); cv.take(dOut, (size_t)M * SOM_OUT); cv.take(dList, K); cv.take(dOutTop, (size_t)K * SOM_OUT); cv.take(dProfile, (size_t)K * S);
+        cv.take(dSegPoint, S); cv.take(dSegDist, S);
+        if (!inputs_on_device) { cv.take(dc, S); cv.take(dm, S); cv.take(dw, S); cv.take(dl, S); }
+    });
+    if (rc) return rc;
     SomArgs a{};
     a.cov = coverage; a.maf = maf; a.w = weight; a.len = length;
     if (!inputs_on_device) {
-        double* dc = cv.take<double>(S); double* dm = cv.take<double>(S); double* dw = cv.take<double>(S); int32_t* dl = cv.take<int32_t>(S);
         CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dc, coverage, S * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dm, maf, S * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dw, weight, S * sizeof(double), hipMemcpyHostToDevice, ctx->stream));

@@ -1241,47 +1241,34 @@ int32_t cvx_wavelets_masked(canvas_ctx* ctx, int32_t nchr, const double* d_cov, 
     const size_t maxLong = caps.maxLong, maxChunks = caps.maxChunks, maxRoots = caps.maxRoots, listCap = caps.listCap, chCap = caps.chCap, rootCap = caps.rootCap, nCn = (size_t)(WV_LB + 3) * WV_REP;
     if (maxRoots + WV_REP * rootCap > 0x7FFFFFF0ull || WV_REP * chCap > 0x7FFFFFF0ull) CANVAS_FAIL(ctx, CANVAS_ERR_INVALID, "canvas_wavelets: bin count out of range");      // (the replicas' stretches are addressed with 32-bit numbers)
     const unsigned long long capCand = (unsigned long long)N + 16;
-    WsSizer sz;
     const size_t opsCap = 5 * (size_t)N;                                  // the exact chains of nodes of several levels (which overlap in position) run side by side: [N, 5 N); the first N belong to the level loop's own passes
-    sz.take<WvOps>(opsCap); sz.take<WvNode>(maxLong); sz.take<WvOut>(maxLong); sz.take<int32_t>(maxLong);
-    sz.take<int32_t>(maxLong + 1); sz.take<int32_t>(maxLong); sz.take<WvHead>(maxLong); sz.take<WvCk>(maxChunks); sz.take<WvBest>(maxChunks);
-    sz.take<WvRoot>(maxRoots + WV_REP * rootCap); sz.take<uint32_t>((size_t)N); sz.take<int32_t>((size_t)N); sz.take<WvCand>((size_t)capCand); sz.take<double>(nchr); sz.take<unsigned long long>(2);
     const size_t maxList2 = caps.maxList2;
-    sz.take<long long>((size_t)N); sz.take<long long>((size_t)N); sz.take<long long>(nchr + 1); sz.take<int>(4); sz.take<WvSlot>(WV_REP * listCap); sz.take<WvSlot>(WV_REP * listCap); sz.take<WvCn>(nCn); sz.take<WvDNode>(maxList2); sz.take<int32_t>(maxList2);
-    sz.take<int32_t>(WV_REP * chCap); sz.take<int32_t>(WV_REP * chCap); sz.take<WvPart>(WV_REP * chCap); sz.take<WvDNode>(maxLong);
-    sz.take<WvDNode>(maxList2); sz.take<WvDev>(1); sz.take<long long>(maxLong); sz.take<int32_t>(maxLong);
-    sz.take<WvNode>(maxLong); sz.take<WvOut>(maxLong); sz.take<int32_t>(maxLong); sz.take<int32_t>(maxLong + WV_EB); sz.take<int32_t>(maxLong); sz.take<WvHead>(maxLong); sz.take<WvCk>(maxChunks); sz.take<WvBest>(maxChunks);
-    sz.take<long long>(maxLong); sz.take<int32_t>(maxLong);
     const size_t f3Cap = (size_t)N / 3 + 16;
     const size_t varCap = (size_t)N / (size_t)std::max(1, std::min(variability_window, 10000)) + (size_t)nchr + 16;
-    sz.take<long long>(varCap); sz.take<float>(varCap); sz.take<double>(nchr + 1); sz.take<uint8_t>(nchr + 1); sz.take<double>(varCap);
-    sz.take<double>(f3Cap); sz.take<double>(f3Cap); sz.take<unsigned long long>(f3Cap); sz.take<WvF3Sel>(1);
     // the integers of the coverage, the prefix tiles' sums, and the state of the multi-stretch medians (up to WV_MED_MAXR stretches per launch set)
     const size_t prefTiles = (size_t)N / WV_PT + (size_t)nchr + 1, medR = WV_MED_MAXR;
-    sz.take<uint32_t>((size_t)N); sz.take<long long>(2 * prefTiles); sz.take<int32_t>(nchr + 2); sz.take<long long>(medR); sz.take<long long>(medR); sz.take<int32_t>(medR + 2); sz.take<WvMedState>(medR);
-    sz.take<uint32_t>(medR * 2 * WV_MD); sz.take<uint32_t>(medR);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
+    WvOps* dOps; WvNode* dNodes; WvOut* dOut; int32_t *dLong, *dBase, *dFlag, *dCounts, *dExactInd, *dChA, *dChB, *dLim, *dLimE, *dTile0P, *dMedTile0; WvHead* dHead; WvCk* dCk; WvBest* dBest; WvRoot* dRoots;
+    uint32_t *dStack, *dK32, *dMedHist, *dMedTick; WvCand* dCands; double *dKeep, *dChromMed, *dSegMed, *dF3Med[2]; unsigned long long *dNcand, *dF3Key; long long *dP1, *dP2, *dOff, *dOpsOff, *dOpsOffE, *dVarStart, *dAgg, *dMedStart, *dMedLen;
+    int* dBad; WvSlot *dListA, *dListB; WvCn* dCn; WvDNode *dExact, *dListIn, *dUndec; WvPart* dParts; WvDev* dDev; WvF3Sel* dF3Sel; float* dVarOut; uint8_t* dIsRoot; WvMedState* dMedState;
+    LongBufs E;      // a second set for the exact chains that start while the level loop is still running (side stream; slices handed out by running offsets, see exact_launch below)
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) {
+        ws.take(dOps, opsCap); ws.take(dNodes, maxLong); ws.take(dOut, maxLong); ws.take(dLong, maxLong); ws.take(dBase, maxLong + 1);
+        ws.take(dFlag, maxLong); ws.take(dHead, maxLong); ws.take(dCk, maxChunks); ws.take(dBest, maxChunks);
+        ws.take(dRoots, maxRoots + WV_REP * rootCap); ws.take(dStack, (size_t)N); ws.take(dCounts, (size_t)N); ws.take(dCands, (size_t)capCand); ws.take(dKeep, nchr); ws.take(dNcand, 2);
+        ws.take(dP1, (size_t)N); ws.take(dP2, (size_t)N); ws.take(dOff, nchr + 1); ws.take(dBad, 4);
+        ws.take(dListA, WV_REP * listCap); ws.take(dListB, WV_REP * listCap); ws.take(dCn, nCn); ws.take(dExact, maxList2); ws.take(dExactInd, maxList2);
+        ws.take(dChA, WV_REP * chCap); ws.take(dChB, WV_REP * chCap); ws.take(dParts, WV_REP * chCap); ws.take(dListIn, maxLong);
+        ws.take(dUndec, maxList2); ws.take(dDev, 1); ws.take(dOpsOff, maxLong); ws.take(dLim, maxLong);
+        ws.take(E.nodes, maxLong); ws.take(E.out, maxLong); ws.take(E.list, maxLong); ws.take(E.base, maxLong + WV_EB); ws.take(E.flag, maxLong); ws.take(E.head, maxLong); ws.take(E.ck, maxChunks); ws.take(E.best, maxChunks);
+        ws.take(dOpsOffE, maxLong); ws.take(dLimE, maxLong);
+        ws.take(dF3Med[0], f3Cap); ws.take(dF3Med[1], f3Cap); ws.take(dF3Key, f3Cap); ws.take(dF3Sel, 1);
+        ws.take(dVarStart, varCap); ws.take(dVarOut, varCap); ws.take(dChromMed, nchr + 1); ws.take(dIsRoot, nchr + 1); ws.take(dSegMed, varCap);
+        ws.take(dK32, (size_t)N); ws.take(dAgg, 2 * prefTiles); ws.take(dTile0P, nchr + 2);
+        ws.take(dMedStart, medR); ws.take(dMedLen, medR); ws.take(dMedTile0, medR + 2); ws.take(dMedState, medR); ws.take(dMedHist, medR * 2 * WV_MD); ws.take(dMedTick, medR);
+    });
+    if (rc) return rc;
     rc = canvas_side_init(ctx); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    WvOps* dOps = ws.take<WvOps>(opsCap); WvNode* dNodes = ws.take<WvNode>(maxLong); WvOut* dOut = ws.take<WvOut>(maxLong);
-    int32_t* dLong = ws.take<int32_t>(maxLong); int32_t* dBase = ws.take<int32_t>(maxLong + 1);
-    int32_t* dFlag = ws.take<int32_t>(maxLong); WvHead* dHead = ws.take<WvHead>(maxLong); WvCk* dCk = ws.take<WvCk>(maxChunks); WvBest* dBest = ws.take<WvBest>(maxChunks);
-    WvRoot* dRoots = ws.take<WvRoot>(maxRoots + WV_REP * rootCap); uint32_t* dStack = ws.take<uint32_t>((size_t)N); int32_t* dCounts = ws.take<int32_t>((size_t)N);
-    WvCand* dCands = ws.take<WvCand>((size_t)capCand); double* dKeep = ws.take<double>(nchr); unsigned long long* dNcand = ws.take<unsigned long long>(2);
-    int32_t* dOverflow = (int32_t*)(dNcand + 1);
-    long long* dP1 = ws.take<long long>((size_t)N); long long* dP2 = ws.take<long long>((size_t)N); long long* dOff = ws.take<long long>(nchr + 1); int* dBad = ws.take<int>(4);
-    WvSlot* dListA = ws.take<WvSlot>(WV_REP * listCap); WvSlot* dListB = ws.take<WvSlot>(WV_REP * listCap); WvCn* dCn = ws.take<WvCn>(nCn); WvCn* dRootCn = dCn + (size_t)(WV_LB + 2) * WV_REP; WvDNode* dExact = ws.take<WvDNode>(maxList2); int32_t* dExactInd = ws.take<int32_t>(maxList2);
-    int32_t* dChA = ws.take<int32_t>(WV_REP * chCap); int32_t* dChB = ws.take<int32_t>(WV_REP * chCap); WvPart* dParts = ws.take<WvPart>(WV_REP * chCap); WvDNode* dListIn = ws.take<WvDNode>(maxLong);
-    WvDNode* dUndec = ws.take<WvDNode>(maxList2); WvDev* dDev = ws.take<WvDev>(1); long long* dOpsOff = ws.take<long long>(maxLong); int32_t* dLim = ws.take<int32_t>(maxLong);
-    // a second set for the exact chains that start while the level loop is still running (side stream; slices handed out by running offsets, see exact_launch below)
-    LongBufs E; E.nodes = ws.take<WvNode>(maxLong); E.out = ws.take<WvOut>(maxLong); E.list = ws.take<int32_t>(maxLong); E.base = ws.take<int32_t>(maxLong + WV_EB); E.flag = ws.take<int32_t>(maxLong);
-    E.head = ws.take<WvHead>(maxLong); E.ck = ws.take<WvCk>(maxChunks); E.best = ws.take<WvBest>(maxChunks);
-    long long* dOpsOffE = ws.take<long long>(maxLong); int32_t* dLimE = ws.take<int32_t>(maxLong);
-    double* dF3Med[2] = {ws.take<double>(f3Cap), nullptr}; dF3Med[1] = ws.take<double>(f3Cap); unsigned long long* dF3Key = ws.take<unsigned long long>(f3Cap); WvF3Sel* dF3Sel = ws.take<WvF3Sel>(1);
-    long long* dVarStart = ws.take<long long>(varCap); float* dVarOut = ws.take<float>(varCap); double* dChromMed = ws.take<double>(nchr + 1); uint8_t* dIsRoot = ws.take<uint8_t>(nchr + 1); double* dSegMed = ws.take<double>(varCap);
-    uint32_t* dK32 = ws.take<uint32_t>((size_t)N); long long* dAgg = ws.take<long long>(2 * prefTiles); int32_t* dTile0P = ws.take<int32_t>(nchr + 2);
-    long long* dMedStart = ws.take<long long>(medR); long long* dMedLen = ws.take<long long>(medR); int32_t* dMedTile0 = ws.take<int32_t>(medR + 2); WvMedState* dMedState = ws.take<WvMedState>(medR);
-    uint32_t* dMedHist = ws.take<uint32_t>(medR * 2 * WV_MD); uint32_t* dMedTick = ws.take<uint32_t>(medR);
+    int32_t* dOverflow = (int32_t*)(dNcand + 1); WvCn* dRootCn = dCn + (size_t)(WV_LB + 2) * WV_REP;
     const WvMedBufs medBufs{dK32, dMedStart, dMedLen, dMedTile0, dMedState, dMedHist, dMedTick};
     auto medians_enqueue = [&](const std::vector<long long>& st, const std::vector<long long>& ln, double* out) -> int32_t { return wv_medians_enqueue(ctx, medBufs, st, ln, out); };
     // what does not depend on the thresholds starts now, next to the host's order statistics: counters cleared, the exact prefix sums of the closed-form decisions
@@ -2027,14 +2014,10 @@ bool probe_disjoint(std::vector<std::pair<int64_t, int64_t>> v) {
     return true;
 }
 struct PrefixBufs { long long* off; int32_t* tile0; uint32_t* K32; long long* agg; long long *P1, *P2; int* bad; };
-void prefix_size(WsSizer& sz, int64_t N, int nchr, bool sums) {
-    sz.take<long long>(nchr + 1); sz.take<int32_t>(nchr + 2); sz.take<uint32_t>((size_t)N); sz.take<long long>(2 * ((size_t)N / WV_PT + (size_t)nchr + 1)); sz.take<int>(4);
-    if (sums) { sz.take<long long>((size_t)N); sz.take<long long>((size_t)N); }
-}
-PrefixBufs prefix_carve(WsCarver& ws, int64_t N, int nchr, bool sums) {
-    PrefixBufs p; p.off = ws.take<long long>(nchr + 1); p.tile0 = ws.take<int32_t>(nchr + 2); p.K32 = ws.take<uint32_t>((size_t)N); p.agg = ws.take<long long>(2 * ((size_t)N / WV_PT + (size_t)nchr + 1)); p.bad = ws.take<int>(4);
-    p.P1 = sums ? ws.take<long long>((size_t)N) : nullptr; p.P2 = sums ? ws.take<long long>((size_t)N) : nullptr;
-    return p;
+void prefix_layout(WsCarver& ws, PrefixBufs& p, int64_t N, int nchr, bool sums) {
+    ws.take(p.off, nchr + 1); ws.take(p.tile0, nchr + 2); ws.take(p.K32, (size_t)N); ws.take(p.agg, 2 * ((size_t)N / WV_PT + (size_t)nchr + 1)); ws.take(p.bad, 4);
+    p.P1 = p.P2 = nullptr;
+    if (sums) { ws.take(p.P1, (size_t)N); ws.take(p.P2, (size_t)N); }
 }
 }  // namespace
 
@@ -2045,10 +2028,8 @@ extern "C" int32_t canvas_wavelets_prefix_probe(canvas_ctx* ctx, int32_t nchr, c
     int32_t rc = probe_offsets(ctx, who, nchr, d_cov, h_chr_offset, N); if (rc) return rc;
     if (!h_p1 || !h_p2 || !h_bad2) WV_PROBE_FAIL(ctx, who, "no room for the results");
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    WsSizer sz; prefix_size(sz, N, nchr, true);
-    rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    const PrefixBufs P = prefix_carve(ws, N, nchr, true);
+    PrefixBufs P;
+    rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) { prefix_layout(ws, P, N, nchr, true); }); if (rc) return rc;
     rc = wv_prefix_enqueue(ctx, nchr, h_chr_offset, d_cov, P.off, P.tile0, P.K32, P.agg, P.P1, P.P2, P.bad); if (rc) return rc;
     CANVAS_HIP_TRY(ctx, hipGetLastError());
     CANVAS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2074,11 +2055,8 @@ extern "C" int32_t canvas_wavelets_bound_probe(canvas_ctx* ctx, int32_t nchr, co
     }
     const size_t total = (size_t)outOff[(size_t)nnodes];
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    WsSizer sz; prefix_size(sz, N, nchr, true); sz.take<WvDNode>(nnodes); sz.take<long long>(nnodes + 1); sz.take<double>(total); sz.take<double>(total);
-    rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    const PrefixBufs P = prefix_carve(ws, N, nchr, true);
-    WvDNode* dNodes = ws.take<WvDNode>(nnodes); long long* dOutOff = ws.take<long long>(nnodes + 1); double* dT = ws.take<double>(total); double* dB = ws.take<double>(total);
+    PrefixBufs P; WvDNode* dNodes; long long* dOutOff; double *dT, *dB;
+    rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) { prefix_layout(ws, P, N, nchr, true); ws.take(dNodes, nnodes); ws.take(dOutOff, nnodes + 1); ws.take(dT, total); ws.take(dB, total); }); if (rc) return rc;
     rc = wv_prefix_enqueue(ctx, nchr, h_chr_offset, d_cov, P.off, P.tile0, P.K32, P.agg, P.P1, P.P2, P.bad); if (rc) return rc;
     int bad[2] = {1, 1};
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(bad, P.bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
@@ -2126,18 +2104,15 @@ extern "C" int32_t canvas_wavelets_level_probe(canvas_ctx* ctx, int32_t nchr, co
         WV_PROBE_FAIL(ctx, who, "the node list (or what it can append) does not fit the capacities canvas_wavelets allocates for this coverage");
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t nCn = (size_t)(WV_LB + 3) * WV_REP;
-    WsSizer sz; prefix_size(sz, N, nchr, true);
-    sz.take<WvSlot>(WV_REP * caps.listCap); sz.take<WvSlot>(WV_REP * caps.listCap); sz.take<int32_t>(WV_REP * caps.chCap); sz.take<int32_t>(WV_REP * caps.chCap); sz.take<WvPart>(WV_REP * caps.chCap);
-    sz.take<WvCn>(nCn); sz.take<WvDev>(1); sz.take<WvDNode>(caps.maxList2); sz.take<int32_t>(caps.maxList2); sz.take<WvDNode>(caps.maxList2); sz.take<WvRoot>(WV_REP * caps.rootCap);
-    sz.take<int32_t>((size_t)N); sz.take<double>(nchr); sz.take<WvDNode>(nnodes);
-    rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    const PrefixBufs P = prefix_carve(ws, N, nchr, true);
-    WvLevelBufs L;
-    L.listA = ws.take<WvSlot>(WV_REP * caps.listCap); L.listB = ws.take<WvSlot>(WV_REP * caps.listCap); L.chA = ws.take<int32_t>(WV_REP * caps.chCap); L.chB = ws.take<int32_t>(WV_REP * caps.chCap);
-    L.parts = ws.take<WvPart>(WV_REP * caps.chCap); L.cn = ws.take<WvCn>(nCn); L.rootCn = L.cn + (size_t)(WV_LB + 2) * WV_REP; L.dev = ws.take<WvDev>(1);
-    L.exact = ws.take<WvDNode>(caps.maxList2); L.exactInd = ws.take<int32_t>(caps.maxList2); L.undec = ws.take<WvDNode>(caps.maxList2); L.roots = ws.take<WvRoot>(WV_REP * caps.rootCap);
-    L.counts = ws.take<int32_t>((size_t)N); double* dKeep = ws.take<double>(nchr); WvDNode* dListIn = ws.take<WvDNode>(nnodes);
+    PrefixBufs P; WvLevelBufs L; double* dKeep; WvDNode* dListIn;
+    rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) {
+        prefix_layout(ws, P, N, nchr, true);
+        ws.take(L.listA, WV_REP * caps.listCap); ws.take(L.listB, WV_REP * caps.listCap); ws.take(L.chA, WV_REP * caps.chCap); ws.take(L.chB, WV_REP * caps.chCap);
+        ws.take(L.parts, WV_REP * caps.chCap); ws.take(L.cn, nCn); L.rootCn = L.cn + (size_t)(WV_LB + 2) * WV_REP; ws.take(L.dev, 1);
+        ws.take(L.exact, caps.maxList2); ws.take(L.exactInd, caps.maxList2); ws.take(L.undec, caps.maxList2); ws.take(L.roots, WV_REP * caps.rootCap);
+        ws.take(L.counts, (size_t)N); ws.take(dKeep, nchr); ws.take(dListIn, nnodes);
+    });
+    if (rc) return rc;
     L.listCap = (unsigned)caps.listCap; L.chCap = (unsigned)caps.chCap; L.maxList2 = (unsigned)caps.maxList2; L.rootCap = (unsigned)caps.rootCap; L.P1 = P.P1; L.P2 = P.P2; L.off = P.off; L.keep = dKeep; L.wvLong = wv_long;
     rc = wv_prefix_enqueue(ctx, nchr, h_chr_offset, d_cov, P.off, P.tile0, P.K32, P.agg, P.P1, P.P2, P.bad); if (rc) return rc;
     int bad[2] = {1, 1};
@@ -2219,14 +2194,13 @@ extern "C" int32_t canvas_wavelets_chain_probe(canvas_ctx* ctx, int64_t n_cov, c
     const int nChunks = base[(size_t)nnodes];
     const size_t opsCap = own_slices ? (size_t)o : (size_t)n_cov;
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    WsSizer sz; sz.take<WvOps>(opsCap); sz.take<WvNode>(nnodes); sz.take<WvOut>(nnodes); sz.take<int32_t>(nnodes); sz.take<int32_t>(nnodes + 1); sz.take<int32_t>(nnodes); sz.take<WvHead>(nnodes);
-    sz.take<WvCk>(nChunks + 1); sz.take<WvBest>(nChunks + 1); sz.take<long long>(nnodes); sz.take<int32_t>(nnodes);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    WvOps* dOps = ws.take<WvOps>(opsCap);
-    LongBufs B; B.nodes = ws.take<WvNode>(nnodes); B.out = ws.take<WvOut>(nnodes); B.list = ws.take<int32_t>(nnodes); B.base = ws.take<int32_t>(nnodes + 1); B.flag = ws.take<int32_t>(nnodes); B.head = ws.take<WvHead>(nnodes);
-    B.ck = ws.take<WvCk>(nChunks + 1); B.best = ws.take<WvBest>(nChunks + 1);
-    long long* dOpsOff = ws.take<long long>(nnodes); int32_t* dLim = ws.take<int32_t>(nnodes);
+    WvOps* dOps; LongBufs B; long long* dOpsOff; int32_t* dLim;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) {
+        ws.take(dOps, opsCap);
+        ws.take(B.nodes, nnodes); ws.take(B.out, nnodes); ws.take(B.list, nnodes); ws.take(B.base, nnodes + 1); ws.take(B.flag, nnodes); ws.take(B.head, nnodes); ws.take(B.ck, nChunks + 1); ws.take(B.best, nChunks + 1);
+        ws.take(dOpsOff, nnodes); ws.take(dLim, nnodes);
+    });
+    if (rc) return rc;
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(B.nodes, nodes.data(), (size_t)nnodes * sizeof(WvNode), hipMemcpyHostToDevice, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(B.list, list.data(), (size_t)nnodes * 4, hipMemcpyHostToDevice, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(B.base, base.data(), ((size_t)nnodes + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -2264,11 +2238,9 @@ extern "C" int32_t canvas_wavelets_subtree_probe(canvas_ctx* ctx, int32_t nchr, 
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = wv_fgh_ensure(ctx, wv_long); if (rc) return rc;
     const size_t capAlloc = (size_t)std::max<int64_t>(cap_cand, 1);
-    WsSizer sz; sz.take<WvRoot>(nroots); sz.take<uint32_t>((size_t)N); sz.take<int32_t>((size_t)N); sz.take<WvCand>(capAlloc); sz.take<double>(nchr); sz.take<unsigned long long>(2);
-    rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    WvRoot* dRoots = ws.take<WvRoot>(nroots); uint32_t* dStack = ws.take<uint32_t>((size_t)N); int32_t* dCounts = ws.take<int32_t>((size_t)N); WvCand* dCands = ws.take<WvCand>(capAlloc);
-    double* dKeep = ws.take<double>(nchr); unsigned long long* dNcand = ws.take<unsigned long long>(2); int32_t* dOverflow = (int32_t*)(dNcand + 1);
+    WvRoot* dRoots; uint32_t* dStack; int32_t* dCounts; WvCand* dCands; double* dKeep; unsigned long long* dNcand;
+    rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) { ws.take(dRoots, nroots); ws.take(dStack, (size_t)N); ws.take(dCounts, (size_t)N); ws.take(dCands, capAlloc); ws.take(dKeep, nchr); ws.take(dNcand, 2); }); if (rc) return rc;
+    int32_t* dOverflow = (int32_t*)(dNcand + 1);
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dRoots, roots.data(), (size_t)nroots * sizeof(WvRoot), hipMemcpyHostToDevice, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(dKeep, h_keep_above, (size_t)nchr * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dCounts, 0, (size_t)N * sizeof(int32_t), ctx->stream));
@@ -2304,13 +2276,13 @@ extern "C" int32_t canvas_wavelets_median_probe(canvas_ctx* ctx, int64_t n_cov, 
     }
     CANVAS_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t medR = WV_MED_MAXR;
-    WsSizer sz; prefix_size(sz, n_cov, 1, false); sz.take<long long>(medR); sz.take<long long>(medR); sz.take<int32_t>(medR + 2); sz.take<WvMedState>(medR); sz.take<uint32_t>(medR * 2 * WV_MD); sz.take<uint32_t>(medR);
-    sz.take<double>(medR); sz.take<unsigned long long>(medR); sz.take<double>(medR);
-    int32_t rc = canvas_ws_reserve(ctx, sz.off + 4096); if (rc) return rc;
-    WsCarver ws(ctx->ws);
-    const PrefixBufs P = prefix_carve(ws, n_cov, 1, false);
-    WvMedBufs M; M.K32 = P.K32; M.start = ws.take<long long>(medR); M.len = ws.take<long long>(medR); M.tile0 = ws.take<int32_t>(medR + 2); M.state = ws.take<WvMedState>(medR); M.hist = ws.take<uint32_t>(medR * 2 * WV_MD); M.tick = ws.take<uint32_t>(medR);
-    double* dOut = ws.take<double>(medR); unsigned long long* dSegs = ws.take<unsigned long long>(medR); double* dOutWg = ws.take<double>(medR);
+    PrefixBufs P; WvMedBufs M; double *dOut, *dOutWg; unsigned long long* dSegs;
+    int32_t rc = cvx_ws_carve(ctx, 4096, [&](WsCarver& ws) {
+        prefix_layout(ws, P, n_cov, 1, false);
+        M.K32 = P.K32; ws.take(M.start, medR); ws.take(M.len, medR); ws.take(M.tile0, medR + 2); ws.take(M.state, medR); ws.take(M.hist, medR * 2 * WV_MD); ws.take(M.tick, medR);
+        ws.take(dOut, medR); ws.take(dSegs, medR); ws.take(dOutWg, medR);
+    });
+    if (rc) return rc;
     const int64_t off[2] = {0, n_cov};
     rc = wv_prefix_enqueue(ctx, 1, off, d_cov, P.off, P.tile0, P.K32, P.agg, nullptr, nullptr, P.bad); if (rc) return rc;      // (the integers only: the medians need no sums)
     CANVAS_HIP_TRY(ctx, hipMemsetAsync(dOut, 0, (size_t)nstretch * sizeof(double), ctx->stream));      // (wv_medians_enqueue launches nothing when every stretch is empty)
