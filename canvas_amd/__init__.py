@@ -7,4 +7,4 @@ library is missing or no GPU is usable it raises."""
 # GPU_MAX_HW_QUEUES hardware queues (4 unless told otherwise) and never runs more kernels at once than that.  It reads the variable at the process's first HIP call, so it is
 # the HOST APPLICATION's to set (bench.py, tests/conftest.py and the three executables do): importing this package does not touch the process environment.
 from .lib import Canvas, CanvasError, load_library, MODE_BINARY, MODE_TDR, CLEAN_GCNORM, CLEAN_FILTSIZE, CLEAN_OUTLIERS, CLEAN_LOCALSD, CLEAN_LOESS  # noqa: F401
-from .lib import bgzf_scan, BGZF_BLOCK  # noqa: F401
+from .lib import bgzf_scan, BGZF_BLOCK, BAM_FRAME_RULE  # noqa: F401

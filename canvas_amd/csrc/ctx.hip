@@ -125,6 +125,12 @@ int32_t canvas_memcpy_h2d_async(canvas_ctx* ctx, void* d_dst, const void* h_src,
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(d_dst, h_src, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
     return CANVAS_OK;
 }
+// device to device, queued on the context's stream behind everything queued before and not waited for; the ranges must not overlap
+int32_t canvas_memcpy_d2d_async(canvas_ctx* ctx, void* d_dst, const void* d_src, int64_t bytes) {
+    if (!ctx || bytes < 0 || (bytes > 0 && (!d_dst || !d_src))) return CANVAS_ERR_INVALID;
+    if (bytes > 0) CANVAS_HIP_TRY(ctx, hipMemcpyAsync(d_dst, d_src, (size_t)bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return CANVAS_OK;
+}
 int32_t canvas_memcpy_d2h(canvas_ctx* ctx, void* h_dst, const void* d_src, int64_t bytes) {
     if (!ctx || bytes < 0) return CANVAS_ERR_INVALID;
     CANVAS_HIP_TRY(ctx, hipMemcpyAsync(h_dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "canvas_partition_states_cbs", "canvas_partition_states_breakpoints", "canvas_reference_copy_numbers", "canvas_call_somatic_ids",
     "canvas_hits_from_bam", "canvas_fragments_from_bam",
     "canvas_bgzf_inflate", "canvas_bgzf_scan",
+    "canvas_bam_frame", "canvas_memcpy_d2d_async",
 ]
 
 
@@ -136,6 +137,10 @@ class CanvasError(RuntimeError):
 BGZF_BLOCK = np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"), ("src_bytes", "<u4"), ("out_bytes", "<u4")])
 INFLATE_OK, INFLATE_DESCRIPTOR, INFLATE_HEADER, INFLATE_INPUT, INFLATE_OVERRUN, INFLATE_SHORT, INFLATE_DISTANCE, INFLATE_CODE = range(8)
 BGZF_SCAN_LIMIT, BGZF_SCAN_END, BGZF_SCAN_DAMAGED = 0, 1, 2
+# canvas_bam_frame_rule (16 bytes), its kinds, and the events of canvas_bam_frame
+BAM_FRAME_RULE = np.dtype([("kind", "<i4"), ("ref_id", "<i4"), ("paired_end", "<i4"), ("sorted", "<i4")])
+BAM_FRAME_ALL, BAM_FRAME_SNV, BAM_FRAME_HITS, BAM_FRAME_FRAGMENTS = 0, 1, 2, 3
+BAM_FRAME_NONE, BAM_FRAME_STOPPED, BAM_FRAME_MALFORMED, BAM_FRAME_UNSORTED, BAM_FRAME_CAPACITY = 0, 1, 2, 3, 4
 
 
 def bgzf_scan(buf, at=0, max_out_bytes=None):
@@ -769,6 +774,36 @@ class Canvas:
         if not want_info:
             self.__dict__.setdefault("_queued_inputs", []).append((src, blocks))      # every queued call reads its own until synchronize() has waited for the stream
         return out, status, info
+
+    def bam_frame(self, records, first, rule, offsets=None, state=None, nbytes=None):
+        """The block_size chain of one chunk of raw BAM record bytes (uint8 tensor; what bgzf_inflate leaves) from byte `first` on, under `rule`: a BAM_FRAME_RULE
+        record, a tuple (kind, ref_id, paired_end, sorted) or a bare kind.  offsets (int64) takes the offsets of the taken records and is created to hold every record
+        the bytes can hold when None; state (int64[4], zeroed when None) carries the sortedness from chunk to chunk: pass self.bam_frame_state, the tensor the last call used.
+        Returns (offsets[:taken], info): info[8] = records classified, taken, `used` (where the next chunk's carry starts), the event (BAM_FRAME_NONE / _STOPPED /
+        _MALFORMED / _UNSORTED / _CAPACITY: info[1] offsets are needed, nothing was written), the event's offset or -1, the pos an unsorted record was compared with,
+        tiles walked twice, the tile size.  The state tensor used is left in self.bam_frame_state."""
+        torch = self.torch
+        r = np.zeros(1, BAM_FRAME_RULE)
+        if isinstance(rule, np.ndarray) or isinstance(rule, np.void):
+            r[0] = rule if isinstance(rule, np.void) else rule.reshape(-1)[0]
+        else:
+            vals = tuple(rule) if isinstance(rule, (tuple, list)) else (rule,)
+            r[0] = tuple(int(v) for v in vals) + (0,) * (4 - len(vals))
+        nb = int(records.numel()) if nbytes is None else int(nbytes)
+        assert records.dtype == torch.uint8 and 0 <= nb <= records.numel()
+        if offsets is None:
+            offsets = torch.empty(max((nb - min(int(first), nb)) // 36 + 2, 1), dtype=torch.int64, device=self.device)
+        if state is None:
+            state = torch.zeros(4, dtype=torch.int64, device=self.device)
+        assert offsets.dtype == torch.int64 and state.dtype == torch.int64 and state.numel() >= 4
+        for t in (records, offsets, state):
+            assert t.is_contiguous() and t.dim() == 1 and (t.numel() == 0 or t.device == self.device), "bam_frame: tensors must be dense, one-dimensional and on the context's device"
+        torch.cuda.current_stream(self.device).synchronize()      # torch fills and copies on its own stream; the kernels run on the context's
+        info = np.zeros(8, np.int64)
+        self._check(self.lib.canvas_bam_frame(self.ctx, C.c_void_p(records.data_ptr()), C.c_uint64(nb), C.c_uint64(int(first)), _np_ptr(r), C.c_void_p(offsets.data_ptr()),
+                                              C.c_int64(int(offsets.numel())), C.c_void_p(state.data_ptr()), _np_ptr(info)))
+        self.bam_frame_state = state
+        return offsets[:0 if info[3] == BAM_FRAME_CAPACITY else int(info[1])], info
 
     def hits_from_bam(self, records, offsets, ref_id, length, mode=MODE_TDR, paired_end=False, hits=None, frag=None, state=None, nbytes=None, want_info=True):
         """LoadObservedAlignmentsBAM (CanvasBin.cs:207-275) over one chunk of raw BAM records (the chunk format of snv_count: uint8 record bytes, int64 offsets).

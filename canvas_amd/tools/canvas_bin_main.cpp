@@ -129,7 +129,8 @@ static int load_bam_device(const std::string& bam, const BamAt& b, bool pairedEn
         [&](void* dRec, uint64_t used, void* dOff, int64_t nrec) -> int32_t {
             return canvas_hits_from_bam(ctx, (const uint8_t*)dRec, used, (const uint64_t*)dOff, nrec, desired, pairedEnd ? 1 : 0, mode, L, dHits.as<uint8_t>(),
                                         dFrag ? dFrag->as<int16_t>() : nullptr, dState->as<int64_t>(), nullptr);
-        });
+        },
+        canvas_bam_frame_rule{CANVAS_BAM_FRAME_HITS, desired, pairedEnd ? 1 : 0, mode == CANVAS_MODE_GC_CONTENT_WEIGHTED ? 1 : 0});
     if (rc == 1) return 1;
     int64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (rc == 0) TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, st, dState->p, 64));
@@ -272,7 +273,8 @@ static int bin_fragments_device(const std::string& bam, const std::string& chrom
             }
             maxCarried = std::max<long long>(maxCarried, info[7]); sumCarried += info[7]; longest = std::max<long long>(longest, info[10]);
             return 0;
-        });
+        },
+        canvas_bam_frame_rule{CANVAS_BAM_FRAME_FRAGMENTS, desired, 0, 0});
     if (rc == 1) return 1;
     int64_t st[16] = {0};
     std::vector<int32_t> counts((size_t)nbins, 0);

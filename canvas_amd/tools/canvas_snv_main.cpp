@@ -137,6 +137,7 @@ int main(int argc, char** argv) {
     if (anyReads && nsites > 0) {          // (no site: the reference leaves its loop at the first read that passes the filters; no read: nothing to count)
         std::unique_ptr<Dev> dPos, dRef, dAlt, dCr, dCa;
         int32_t lastPos = -1;
+        loop.carried_pos = [&](int32_t p) { lastPos = p; };      // (framed on the device: the position an unsorted read follows, for the message below)
         const int rc = loop.run(actx, ctx, tLoop0,
             [&](canvas_ctx* c) -> int {
                 dPos.reset(new Dev(c, ((int64_t)nsites + 1) * 4)); dRef.reset(new Dev(c, nsites + 1)); dAlt.reset(new Dev(c, nsites + 1));
@@ -157,7 +158,8 @@ int main(int argc, char** argv) {
             [&](void* dRec, uint64_t used, void* dOff, int64_t nrec) -> int32_t {
                 return canvas_snv_count(ctx, (const uint8_t*)dRec, used, (const uint64_t*)dOff, nrec, refId, minMapQ, 20, dPos->as<int32_t>(), dRef->as<uint8_t>(), dAlt->as<uint8_t>(),
                                         nsites, dCr->as<int32_t>(), dCa->as<int32_t>(), nullptr);
-            });
+            },
+            canvas_bam_frame_rule{CANVAS_BAM_FRAME_SNV, refId, 0, 0});
         if (rc) return 1;
         const double t3 = Phases::now();
         TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, cntRef.data(), dCr->p, (int64_t)nsites * 4)); TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, cntAlt.data(), dCa->p, (int64_t)nsites * 4));

@@ -286,6 +286,11 @@ struct ExitStamp { const char* what; explicit ExitStamp(const char* w) : what(w)
 // instead, canvas_bgzf_inflate writes the record bytes straight into the buffer consume reads, and they are copied DOWN into the staging buffer for the framing, which
 // is the same code.  No host thread inflates and no inflated chunk is uploaded; only the carried tail (less than one record) goes up from the host copy.  A block the
 // device refuses is a block that "does not inflate to its recorded size".  The chunks are not overlapped in this form.
+// CANVAS_TOOL_DEVICE_FRAME=1 (configuration as well, off by default, implies device inflation): the framing moves to the device too.  `rule` restates the tool's `frame`
+// for canvas_bam_frame (csrc/bam_frame.hpp); the call leaves the offsets of the taken records in the buffer consume reads and says how many there are, where the carried
+// tail starts and whether the chain met a record that stops or fails the tool.  The tail moves to the front of the other buffer on the device: no inflated chunk and no
+// offset table crosses PCIe in either direction, and no staging buffer is pinned.  For a malformed or unsorted record the loop copies that one record's head down and
+// lets `frame` say what it says on the host path (carried_pos hands it the position the record was compared with); messages and exit codes are the same.
 enum class BamFrame { Take, Skip, TakeAndStop, Stop, Fail };      // TakeAndStop / Stop: nothing behind this record is read; Fail: the tool has said why (unless quiet)
 struct BamChunkLoop {
     const char* tool; std::string bam; uint64_t voff = 0; size_t chunkBytes = (size_t)32 << 20;
@@ -293,13 +298,15 @@ struct BamChunkLoop {
     const char* profile = nullptr;    // with CANVAS_TOOL_TIMING: the library scope whose device time goes to kernelMs
     double tInflate = 0, tDevice = 0, kernelMs = 0; long long records = 0, chunks = 0, bytesUp = 0;
     bool deviceInflate = false; double inflateKernelMs = 0;      // CANVAS_TOOL_DEVICE_INFLATE; with CANVAS_TOOL_TIMING the device time of canvas_bgzf_inflate
+    bool deviceFrame = false; double frameKernelMs = 0; long long framedWrong = 0;      // CANVAS_TOOL_DEVICE_FRAME; the device time of canvas_bam_frame, tiles it walked twice
+    std::function<void(int32_t)> carried_pos;                   // device framing, an unsorted record: the position it was compared with, before `frame` sees the record
     // the end of the tool's timing line
-    std::string timing_tail() const { char b[96]; snprintf(b, sizeof b, ", \"device_inflate\": %d, \"inflate_kernel_ms\": %.4f", deviceInflate ? 1 : 0, inflateKernelMs); return b; }
+    std::string timing_tail() const { char b[192]; snprintf(b, sizeof b, ", \"device_inflate\": %d, \"inflate_kernel_ms\": %.4f, \"device_frame\": %d, \"frame_kernel_ms\": %.4f", deviceInflate ? 1 : 0, inflateKernelMs, deviceFrame ? 1 : 0, frameKernelMs); return b; }
     void chunk_bytes_from(const char* envName) { if (const char* e = getenv(envName)) { const long long v = atoll(e); if (v >= 65536) chunkBytes = (size_t)v; } }
     // 0: the file was read to its end or to the record that stopped it, everything is queued and waited for.  1: the device or the runtime failed (message printed).
     // 2: the input was refused (message printed unless quiet, or by frame).  Any other value: what setup returned.
     template <class Setup, class Frame, class Consume>
-    int run(AsyncCtx& actx, canvas_ctx*& ctx, double tLoop0, Setup setup, Frame frame, Consume consume) {
+    int run(AsyncCtx& actx, canvas_ctx*& ctx, double tLoop0, Setup setup, Frame frame, Consume consume, const canvas_bam_frame_rule& rule) {
         MappedFile mf; if (!mf.open(bam)) { fprintf(stderr, "%s: cannot map %s\n", tool, bam.c_str()); return 1; }
         const uint8_t* F = (const uint8_t*)mf.p; const size_t FN = mf.n;
         // blocks of the first chunk: sizes the buffers (a small file gets small ones: pinning costs time per megabyte)
@@ -320,16 +327,26 @@ struct BamChunkLoop {
         if (!(ctx = actx.require(tool))) return 1;
         const bool timing = getenv("CANVAS_TOOL_TIMING") != nullptr;
         if (timing && profile) (void)canvas_profile_enable(ctx, 1);
-        std::unique_ptr<uint8_t[]> hRec[2] = {std::unique_ptr<uint8_t[]>(new uint8_t[cap]), std::unique_ptr<uint8_t[]>(new uint8_t[cap])};
-        std::unique_ptr<uint64_t[]> hOff[2] = {std::unique_ptr<uint64_t[]>(new uint64_t[offCap]), std::unique_ptr<uint64_t[]>(new uint64_t[offCap])};
+        { const char* e = getenv("CANVAS_TOOL_DEVICE_FRAME"); deviceFrame = e && atoi(e) == 1; }
+        { const char* e = getenv("CANVAS_TOOL_DEVICE_INFLATE"); deviceInflate = deviceFrame || (e && atoi(e) == 1); }
+        const size_t hostCap = deviceFrame ? 1 : cap, hostOffCap = deviceFrame ? 1 : offCap;      // (framed on the device: no staging buffers)
+        std::unique_ptr<uint8_t[]> hRec[2] = {std::unique_ptr<uint8_t[]>(new uint8_t[hostCap]), std::unique_ptr<uint8_t[]>(new uint8_t[hostCap])};
+        std::unique_ptr<uint64_t[]> hOff[2] = {std::unique_ptr<uint64_t[]>(new uint64_t[hostOffCap]), std::unique_ptr<uint64_t[]>(new uint64_t[hostOffCap])};
         struct Registered { canvas_ctx* c; std::vector<void*> v; ~Registered() { for (void* p : v) (void)canvas_host_unregister(c, p); } } reg{ctx, {}};
-        for (int i = 0; i < 2; i++) { TOOL_TRY(ctx, canvas_host_register(ctx, hRec[i].get(), (int64_t)cap)); reg.v.push_back(hRec[i].get());
+        for (int i = 0; i < 2 && !deviceFrame; i++) { TOOL_TRY(ctx, canvas_host_register(ctx, hRec[i].get(), (int64_t)cap)); reg.v.push_back(hRec[i].get());
                                       TOOL_TRY(ctx, canvas_host_register(ctx, hOff[i].get(), (int64_t)(offCap * 8))); reg.v.push_back(hOff[i].get()); }
         Dev dRec0(ctx, (int64_t)cap), dRec1(ctx, (int64_t)cap), dOff0(ctx, (int64_t)(offCap * 8)), dOff1(ctx, (int64_t)(offCap * 8));
         if (!dRec0.p || !dRec1.p || !dOff0.p || !dOff1.p) { fprintf(stderr, "%s: device allocation failed: %s\n", tool, canvas_last_error(ctx)); return 1; }
         void* dRec[2] = {dRec0.p, dRec1.p}; void* dOff[2] = {dOff0.p, dOff1.p};
         if (int rc = setup(ctx)) return rc;
-        { const char* e = getenv("CANVAS_TOOL_DEVICE_INFLATE"); deviceInflate = e && atoi(e) == 1; }
+        std::unique_ptr<Dev> dFrameState;      // (only when the records are framed on the device)
+        if (deviceFrame) {
+            dFrameState.reset(new Dev(ctx, 32));
+            if (!dFrameState->p) { fprintf(stderr, "%s: device allocation failed: %s\n", tool, canvas_last_error(ctx)); return 1; }
+            const int64_t zero[4] = {0, 0, 0, 0};
+            TOOL_TRY(ctx, canvas_memcpy_h2d(ctx, dFrameState->p, zero, 32));
+            if (timing) (void)canvas_profile_enable(ctx, 1);
+        }
         // device inflation: the chunk's stretch of the file, its block table and the statuses, grown as chunks need them (a level-0 block is larger than what it holds)
         std::unique_ptr<Dev> dComp, dBlk, dStatus; size_t compCap = 0, blkCap = 0; std::vector<canvas_bgzf_block> table;
         tDevice += Phases::now() - tLoop0;
@@ -355,12 +372,12 @@ struct BamChunkLoop {
                     }
                     TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dComp->p, F + compAt, (int64_t)compBytes));
                     TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dBlk->p, table.data(), (int64_t)(table.size() * sizeof(canvas_bgzf_block))));
-                    if (carry) TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dRec[cur], buf, (int64_t)carry));
+                    if (carry && !deviceFrame) TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dRec[cur], buf, (int64_t)carry));      // (framed on the device: the tail is there already)
                     int64_t info[4];
                     TOOL_TRY(ctx, canvas_bgzf_inflate(ctx, dComp->as<uint8_t>(), compBytes, dBlk->as<canvas_bgzf_block>(), (int64_t)table.size(), (uint8_t*)dRec[cur], cap,
                                                       dStatus->as<int32_t>(), info));
                     if (info[1] != 0) ok = false;
-                    else TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, buf + carry, (uint8_t*)dRec[cur] + carry, (int64_t)total));
+                    else if (!deviceFrame) TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, buf + carry, (uint8_t*)dRec[cur] + carry, (int64_t)total));
                 }
             } else
             parallel_for((int64_t)blocks.size(), [&](int64_t i) {
@@ -371,6 +388,23 @@ struct BamChunkLoop {
             // the block_size chain: one offset per record the tool takes; the shape of every record is checked here (the kernels check it again)
             size_t at = skip; skip = 0; int64_t nrec = 0; bool failed = false;
             if (at > len) { if (!quiet) fprintf(stderr, "%s: %s.bai points behind the end of a block\n", tool, bam.c_str()); (void)canvas_synchronize(ctx); return 2; }
+            if (ok && deviceFrame) {
+                int64_t fi[8];
+                TOOL_TRY(ctx, canvas_bam_frame(ctx, (const uint8_t*)dRec[cur], (uint64_t)len, (uint64_t)at, &rule, (uint64_t*)dOff[cur], (int64_t)offCap, dFrameState->as<int64_t>(), fi));
+                if (fi[3] == CANVAS_BAM_FRAME_CAPACITY) { fprintf(stderr, "%s: %s: %lld records in a chunk sized for %zu\n", tool, bam.c_str(), (long long)fi[1], offCap); return 1; }
+                nrec = fi[1]; at = (size_t)fi[2]; framedWrong += fi[6];
+                if (fi[3] == CANVAS_BAM_FRAME_STOPPED) done = true;
+                if (fi[3] == CANVAS_BAM_FRAME_MALFORMED || fi[3] == CANVAS_BAM_FRAME_UNSORTED) {
+                    // that one record's head comes down (block_size, the fixed fields, the name, the first CIGAR word), and the tool's `frame` says what it has to say
+                    uint8_t head[4 + 32 + 255 + 4] = {0};
+                    const size_t n = std::min(sizeof head, len - (size_t)fi[4]);
+                    TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, head, (const uint8_t*)dRec[cur] + fi[4], (int64_t)n));
+                    const int32_t bs = (int32_t)le32(head); BamFixed fx;
+                    if (!fx.decode(head + 4, bs)) { if (!quiet) fprintf(stderr, "%s: %s: malformed alignment record (block_size %d)\n", tool, bam.c_str(), bs); }
+                    else { if (fi[3] == CANVAS_BAM_FRAME_UNSORTED && carried_pos) carried_pos((int32_t)fi[5]); (void)frame(head + 4, fx, bs); }
+                    failed = true;
+                }
+            } else
             if (ok) while (at + 4 <= len) {
                 const int32_t bs = (int32_t)le32(buf + at);
                 if (bs >= 32 && (size_t)bs > len - at - 4) break;                            // completed by the next chunk
@@ -390,10 +424,11 @@ struct BamChunkLoop {
             carry = done ? 0 : len - at;
             const double t1 = Phases::now(); tInflate += t1 - t0;
             TOOL_TRY(ctx, canvas_synchronize(ctx));                            // chunk k - 1 ran while this one was inflated
-            if (carry) memcpy(hRec[cur ^ 1].get(), buf + at, carry);          // only now: the other buffer was the source of chunk k - 1's upload until the wait above
+            if (carry && !deviceFrame) memcpy(hRec[cur ^ 1].get(), buf + at, carry);          // only now: the other buffer was the source of chunk k - 1's upload until the wait above
+            if (carry && deviceFrame) TOOL_TRY(ctx, canvas_memcpy_d2d_async(ctx, dRec[cur ^ 1], (const uint8_t*)dRec[cur] + at, (int64_t)carry));      // (consume below only reads [0, used))
             if (nrec > 0) {
                 if (!deviceInflate) TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dRec[cur], buf, (int64_t)used));      // (inflated on the device: the bytes are there)
-                TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dOff[cur], offs, nrec * 8));
+                if (!deviceFrame) TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dOff[cur], offs, nrec * 8));
                 TOOL_TRY(ctx, consume(dRec[cur], (uint64_t)used, dOff[cur], nrec));
                 records += nrec; chunks++; bytesUp += (long long)used;
             }
@@ -408,6 +443,7 @@ struct BamChunkLoop {
         TOOL_TRY(ctx, canvas_synchronize(ctx));
         if (timing && profile) { int32_t launches = 0; (void)canvas_profile_get(ctx, profile, &kernelMs, &launches, 1); }
         if (timing && deviceInflate) { int32_t launches = 0; (void)canvas_profile_get(ctx, "bgzf_inflate", &inflateKernelMs, &launches, 1); }
+        if (timing && deviceFrame) { int32_t launches = 0; (void)canvas_profile_get(ctx, "bam_frame", &frameKernelMs, &launches, 1); }
         tDevice += Phases::now() - t3;
         return 0;
     }

@@ -139,6 +139,13 @@ namespace CanvasHipInterop
         [DllImport(Lib)] public static extern int canvas_bgzf_inflate(IntPtr ctx, IntPtr dSrc, ulong srcNbytes, IntPtr dBlocks, long nblocks, IntPtr dDst, ulong dstNbytes, IntPtr dStatus, long[] info);
         // the block table of a BGZF buffer in host memory from file offset `at` (no context): info = long[4] (blocks, next offset, inflated bytes, reason: 0 limit, 1 end, 2 damaged)
         [DllImport(Lib)] public static extern int canvas_bgzf_scan(byte[] hBytes, ulong nbytes, ulong at, ulong maxOutBytes, [Out] BgzfBlock[] hBlocks, long capacity, long[] info);
+        // BAM record framing on the device: the offsets of the records `rule` takes from the block_size chain of a chunk, from byte `first` on (Kind: 0 all, 1 SNV, 2 hits,
+        // 3 fragments); dState = long[4] on the device, zeroed before the first chunk; info = long[8] (classified, taken, used, event: 0 none, 1 stopped, 2 malformed, 3 unsorted,
+        // 4 capacity; the event's offset or -1; the pos an unsorted record was compared with; tiles walked twice; tile size).  The call waits
+        [StructLayout(LayoutKind.Sequential)] public struct BamFrameRule { public int Kind; public int RefId; public int PairedEnd; public int Sorted; }
+        [DllImport(Lib)] public static extern int canvas_bam_frame(IntPtr ctx, IntPtr dRecords, ulong nbytes, ulong first, ref BamFrameRule rule, IntPtr dRecordOffsets, long capacity,
+            IntPtr dState, long[] info);
+        [DllImport(Lib)] public static extern int canvas_memcpy_d2d_async(IntPtr ctx, IntPtr dDst, IntPtr dSrc, long bytes);
         [DllImport(Lib)] public static extern int canvas_memcpy_h2d_async(IntPtr ctx, IntPtr dDst, IntPtr hSrc, long bytes);
         // Tools/FlagUniqueKmers (KmerChecker): unique-35-mer masks of all contigs at once (stats = long[8] or null), and the letter case of kmer.fa from a mask
         [DllImport(Lib)] public static extern int canvas_flag_unique_kmers(IntPtr ctx, int nchr, IntPtr[] dBases, long[] len, IntPtr[] dMask, long maxTableBytes, long[] stats);

@@ -62,6 +62,10 @@ int32_t canvas_memcpy_d2h(canvas_ctx* ctx, void* h_dst, const void* d_src, int64
 /* canvas_memcpy_h2d without the wait: queued on the context's stream; h_src (pinned or registered with canvas_host_register) must not change before the next
  * canvas_synchronize.  What CanvasSNV's chunk loop uses to upload chunk k while it inflates chunk k + 1. */
 int32_t canvas_memcpy_h2d_async(canvas_ctx* ctx, void* d_dst, const void* h_src, int64_t bytes);
+/* Device to device on the context's stream, queued behind what was queued before and not waited for; the ranges must not overlap.  What the executables' chunk loop
+ * moves the carried tail of a chunk with when the records are framed on the device (canvas_bam_frame).  CANVAS_ERR_INVALID: NULL context, negative bytes, a NULL
+ * pointer with bytes > 0. */
+int32_t canvas_memcpy_d2d_async(canvas_ctx* ctx, void* d_dst, const void* d_src, int64_t bytes);
 
 /* Pins a host array (hipHostRegister) so that uploads from it run at the full PCIe rate and asynchronously: what a C# host does once with the arrays
  * LoadIntermediateData left in memory (GCHandle.Alloc(..., Pinned) + this call). */
@@ -973,6 +977,48 @@ int32_t canvas_bgzf_inflate(canvas_ctx* ctx, const uint8_t* d_src, uint64_t src_
 #define CANVAS_BGZF_SCAN_END 1
 #define CANVAS_BGZF_SCAN_DAMAGED 2
 int32_t canvas_bgzf_scan(const uint8_t* h_bytes, uint64_t nbytes, uint64_t at, uint64_t max_out_bytes, canvas_bgzf_block* h_blocks, int64_t capacity, int64_t* h_info);
+
+/* ---- BAM record framing on the device: d_record_offsets of the three readers above from the bytes canvas_bgzf_inflate leaves ------------------------------ */
+/* d_records[0, nbytes) holds raw record bytes; the block_size chain starts at `first`: next(o) = o + 4 + block_size(o).  The call writes the offsets of the records
+ * the rule TAKES, in chain order (each points at the block_size word), and answers in h_info where the chain ended and why.  It always waits (the caller needs the
+ * count before it can call a reader); profile scope "bam_frame".
+ *   chain       fewer than 4 bytes left, or a block_size >= 32 that reaches beyond nbytes: the chunk ends here; no event, the bytes from here on are the carry of
+ *               the next chunk.  A block_size < 32 (negative values included) is MALFORMED.
+ *   rule.kind   per whole record, the checks in this order (they restate the executables' own, canvas_amd/csrc/bam_frame.hpp):
+ *               CANVAS_BAM_FRAME_ALL        every whole record is taken.
+ *               CANVAS_BAM_FRAME_SNV        name, CIGAR, bases and qualities do not fit block_size: MALFORMED; refID < 0, pos < 0 or refID > ref_id: STOP (not taken);
+ *                                           refID != ref_id: skipped; pos below the last taken pos: UNSORTED; otherwise taken.
+ *               CANVAS_BAM_FRAME_HITS       name and CIGAR do not fit: MALFORMED; refID == ref_id and sorted == 0: taken; failing the read filters of
+ *                                           canvas_hits_from_bam (paired_end as there): taken; refID != ref_id: taken, and STOP behind it; pos below the last pos that
+ *                                           got this far: UNSORTED; otherwise taken.  sorted = 1 exactly for mode 5 (GCContentWeighted).
+ *               CANVAS_BAM_FRAME_FRAGMENTS  name and CIGAR do not fit: MALFORMED; refID != ref_id: taken, and STOP behind it; otherwise taken.
+ *   event       the first record in chain order that stops, is malformed or unsorted; nothing behind it is classified, taken or counted.
+ *   h_info      int64[8], required: [0] records classified, the event's included; [1] records taken = offsets written; [2] `used`: the offset of a STOP / MALFORMED /
+ *               UNSORTED record, the offset behind a taken stopping record, otherwise the offset of the first incomplete record or of the trailing 0-3 bytes;
+ *               [3] the event (CANVAS_BAM_FRAME_NONE ...); [4] the offset of the event's record, -1 without one; [5] the pos an UNSORTED record was compared with;
+ *               [6] tiles whose guessed entry was wrong and that were walked again (diagnostic: costs time, changes nothing); [7] the tile size in bytes.
+ *   d_state     int64[4] in device memory, zeroed before the first chunk, carried from call to call: [0] records that reached the sortedness comparison and passed it,
+ *               [1] the pos of the last of them, [2] records taken in all, [3] the last call's event.
+ *   capacity    more taken records than `capacity`: event CANVAS_BAM_FRAME_CAPACITY, h_info[1] = the number needed, the other words as the repeated call will
+ *               give them, no offset written, d_state unchanged.  The call returns CANVAS_OK and can be repeated.
+ *   exactness   the result is the sequential chain's and nothing else.  Record starts are guessed per tile so that the tiles can be walked side by side; a guess is
+ *               used only where the chain from the tiles before arrives at exactly that offset.  A record the chain reaches is classified even if it looks like
+ *               garbage; bytes that look like a record and are not on the chain are ignored.  No byte outside [d_records, d_records + nbytes) is read.
+ * nbytes - first < 4 launches nothing, leaves d_state alone and answers NONE with used = first.
+ * CANVAS_ERR_INVALID: NULL context, rule, state or info; first > nbytes; an unknown kind; NULL d_record_offsets with capacity > 0; a negative capacity; NULL d_records
+ * with nbytes > 0; nbytes - first of 2^32 and more (a chunk is cut by the caller). */
+typedef struct { int32_t kind; int32_t ref_id; int32_t paired_end; int32_t sorted; } canvas_bam_frame_rule;   /* 16 bytes */
+#define CANVAS_BAM_FRAME_ALL 0
+#define CANVAS_BAM_FRAME_SNV 1
+#define CANVAS_BAM_FRAME_HITS 2
+#define CANVAS_BAM_FRAME_FRAGMENTS 3
+#define CANVAS_BAM_FRAME_NONE 0
+#define CANVAS_BAM_FRAME_STOPPED 1
+#define CANVAS_BAM_FRAME_MALFORMED 2
+#define CANVAS_BAM_FRAME_UNSORTED 3
+#define CANVAS_BAM_FRAME_CAPACITY 4
+int32_t canvas_bam_frame(canvas_ctx* ctx, const uint8_t* d_records, uint64_t nbytes, uint64_t first, const canvas_bam_frame_rule* rule, uint64_t* d_record_offsets,
+                         int64_t capacity, int64_t* d_state, int64_t* h_info);
 
 /* ---- profiling hooks (hipEvent pairs recorded on the context's stream around the named kernels) --------------------- */
 /* on: 0 off; 1 every named scope; 2 only the scopes around the dominant (HBM-bound) kernel of CanvasBin — "bin_summary", "bin_summary_packed", "bin_pass",
