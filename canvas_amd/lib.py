@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "canvas_hits_from_bam", "canvas_fragments_from_bam",
     "canvas_bgzf_inflate", "canvas_bgzf_scan",
     "canvas_bam_frame", "canvas_memcpy_d2d_async",
+    "canvas_bgzf_crc32",
 ]
 
 
@@ -137,6 +138,7 @@ class CanvasError(RuntimeError):
 BGZF_BLOCK = np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"), ("src_bytes", "<u4"), ("out_bytes", "<u4")])
 INFLATE_OK, INFLATE_DESCRIPTOR, INFLATE_HEADER, INFLATE_INPUT, INFLATE_OVERRUN, INFLATE_SHORT, INFLATE_DISTANCE, INFLATE_CODE = range(8)
 BGZF_SCAN_LIMIT, BGZF_SCAN_END, BGZF_SCAN_DAMAGED = 0, 1, 2
+CRC_OK, CRC_MISMATCH, CRC_DESCRIPTOR, CRC_SKIPPED = range(4)                  # the block statuses of canvas_bgzf_crc32
 # canvas_bam_frame_rule (16 bytes), its kinds, and the events of canvas_bam_frame
 BAM_FRAME_RULE = np.dtype([("kind", "<i4"), ("ref_id", "<i4"), ("paired_end", "<i4"), ("sorted", "<i4")])
 BAM_FRAME_ALL, BAM_FRAME_SNV, BAM_FRAME_HITS, BAM_FRAME_FRAGMENTS = 0, 1, 2, 3
@@ -774,6 +776,40 @@ class Canvas:
         if not want_info:
             self.__dict__.setdefault("_queued_inputs", []).append((src, blocks))      # every queued call reads its own until synchronize() has waited for the stream
         return out, status, info
+
+    def bgzf_crc32(self, src, blocks, out, inflate_status=None, crc=None, status=None, want_info=True):
+        """The CRC32 of every inflated BGZF block, held against the word of the block's trailer.  src, blocks: as for bgzf_inflate (src=None: compute only, nothing is
+        compared); out: the uint8 tensor bgzf_inflate filled; inflate_status: its statuses (int32 per block; a block whose status is not 0 is CRC_SKIPPED), None: every
+        block is summed.  crc (uint32 per block; an int32 tensor is taken as the same bits) and status (int32 per block) are created when None.  Returns (crc, status,
+        info): info[4] = blocks, blocks neither CRC_OK nor CRC_SKIPPED, bytes summed, first such block or -1; want_info=False only queues the work and returns None
+        for it.  crc[i] equals zlib.crc32 of the block's bytes wherever status[i] is CRC_OK or CRC_MISMATCH."""
+        torch = self.torch
+        if isinstance(blocks, np.ndarray):
+            host = np.ascontiguousarray(blocks.astype(BGZF_BLOCK, copy=False))
+            n = int(host.size)
+            blocks = torch.from_numpy(host.view(np.uint8).reshape(-1).copy()).to(self.device)
+        else:
+            assert blocks.dtype == torch.uint8 and blocks.numel() % 24 == 0, "bgzf_crc32: blocks is n x 24 bytes"
+            n = int(blocks.numel()) // 24
+        if crc is None:
+            crc = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device).view(torch.uint32)      # (filled as int32: torch fills few unsigned types)
+        if status is None:
+            status = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.uint8 and status.dtype == torch.int32 and status.numel() >= n
+        assert src is None or src.dtype == torch.uint8
+        assert inflate_status is None or (inflate_status.dtype == torch.int32 and inflate_status.numel() >= n)
+        assert crc.dtype in (torch.uint32, torch.int32) and crc.numel() >= n
+        for t in (src, blocks, out, status, inflate_status, crc):
+            assert t is None or (t.is_contiguous() and (t.numel() == 0 or t.device == self.device)), "bgzf_crc32: tensors must be dense and on the context's device"
+        torch.cuda.current_stream(self.device).synchronize()      # torch fills and copies on its own stream; the kernel runs on the context's
+        info = np.zeros(4, np.int64) if want_info else None
+        self._check(self.lib.canvas_bgzf_crc32(self.ctx, C.c_void_p(src.data_ptr()) if src is not None else None, C.c_uint64(int(src.numel()) if src is not None else 0),
+                                               C.c_void_p(blocks.data_ptr()), C.c_int64(n), C.c_void_p(out.data_ptr()), C.c_uint64(int(out.numel())),
+                                               C.c_void_p(inflate_status.data_ptr()) if inflate_status is not None else None, C.c_void_p(crc.data_ptr()),
+                                               C.c_void_p(status.data_ptr()), _np_ptr(info) if want_info else None))
+        if not want_info:
+            self.__dict__.setdefault("_queued_inputs", []).append((src, blocks, out, inflate_status))      # every queued call reads its own until synchronize() has waited for the stream
+        return crc, status, info
 
     def bam_frame(self, records, first, rule, offsets=None, state=None, nbytes=None):
         """The block_size chain of one chunk of raw BAM record bytes (uint8 tensor; what bgzf_inflate leaves) from byte `first` on, under `rule`: a BAM_FRAME_RULE

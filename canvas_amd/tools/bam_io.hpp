@@ -3,6 +3,7 @@
 #include <zlib.h>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include <string>
@@ -23,7 +24,11 @@ static bool inflate_raw(const void* src, size_t clen, void* dst, size_t isize, b
 }
 
 // ---------------------------------------------------------------- BGZF / BAM / BAI
-struct BgzfBlock { size_t in, clen, size; uint32_t isize; };      // deflate data at [in, in + clen) of a block of `size` bytes that inflates to isize bytes
+struct BgzfBlock { size_t in, clen, size; uint32_t isize, crc; };      // deflate data at [in, in + clen) of a block of `size` bytes that inflates to isize bytes whose CRC32 is crc
+// CANVAS_TOOL_CHECK_CRC=1 (configuration of the executables, off by default): every place that inflates a BGZF block of a BAM holds the CRC32 of the inflated bytes against
+// the word of the block's trailer (RFC 1952), and a block that fails is handled as one that does not inflate to its recorded size.  A block of ISIZE 0 is not inflated.
+static inline bool bgzf_check_crc() { static const bool on = [] { const char* e = getenv("CANVAS_TOOL_CHECK_CRC"); return e && atoi(e) == 1; }(); return on; }
+static inline bool bgzf_crc_ok(const void* data, size_t n, uint32_t want) { return (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef*)data, (uInt)n) == want; }
 // The BGZF block that starts at h, of which avail bytes are at hand.  0: these bytes are no BGZF block.  More than avail: that many bytes are needed to go on (12, then the
 // extra field, then the whole block): get them and call again.  Otherwise b is filled and the value is the block's size.
 static size_t bgzf_parse(const uint8_t* h, size_t avail, BgzfBlock& b) {
@@ -36,11 +41,11 @@ static size_t bgzf_parse(const uint8_t* h, size_t avail, BgzfBlock& b) {
     if (bsize < 0 || (size_t)bsize + 1 < 12 + xlen + 8) return 0;
     b.size = (size_t)bsize + 1;
     if (avail < b.size) return b.size;
-    b.in = 12 + xlen; b.clen = b.size - b.in - 8; b.isize = le32(h + b.size - 4);
+    b.in = 12 + xlen; b.clen = b.size - b.in - 8; b.crc = le32(h + b.size - 8); b.isize = le32(h + b.size - 4);
     return b.isize <= 65536 ? b.size : 0;
 }
-// a BGZF file read as one stream.  When read() fails, `bad` tells a damaged file (a block that does not parse or does not inflate to its ISIZE, the file ending inside a
-// block) from its clean end at a block boundary
+// a BGZF file read as one stream.  When read() fails, `bad` tells a damaged file (a block that does not parse, does not inflate to its ISIZE or, with CANVAS_TOOL_CHECK_CRC=1,
+// fails its CRC32; the file ending inside a block) from its clean end at a block boundary
 struct Bgzf {
     FILE* f = nullptr; std::vector<uint8_t> raw = std::vector<uint8_t>(65536 + 16), block; size_t pos = 0; bool bad = false;
     bool open(const std::string& p) { f = fopen(p.c_str(), "rb"); return f != nullptr; }
@@ -54,6 +59,7 @@ struct Bgzf {
         }
         block.resize(need ? b.isize : 0); pos = 0;
         if (!need || (b.isize && !inflate_raw(raw.data() + b.in, b.clen, block.data(), b.isize))) bad = true;
+        else if (b.isize && bgzf_check_crc() && !bgzf_crc_ok(block.data(), b.isize, b.crc)) bad = true;
         return !bad;
     }
     bool read(void* dst, size_t n) {

@@ -291,6 +291,9 @@ struct ExitStamp { const char* what; explicit ExitStamp(const char* w) : what(w)
 // tail starts and whether the chain met a record that stops or fails the tool.  The tail moves to the front of the other buffer on the device: no inflated chunk and no
 // offset table crosses PCIe in either direction, and no staging buffer is pinned.  For a malformed or unsorted record the loop copies that one record's head down and
 // lets `frame` say what it says on the host path (carried_pos hands it the position the record was compared with); messages and exit codes are the same.
+// CANVAS_TOOL_CHECK_CRC=1 (bam_io.hpp; configuration, off by default): on the host path the worker thread that inflated a block sums it with zlib's crc32(); on the two
+// device paths canvas_bgzf_crc32 is queued behind canvas_bgzf_inflate on the same descriptors, with its statuses, and its summary is read where the inflate's is.  The
+// compressed stretch that goes up is 8 bytes longer: the last block's trailer.  A block that fails ends the loop as one that does not inflate does.
 enum class BamFrame { Take, Skip, TakeAndStop, Stop, Fail };      // TakeAndStop / Stop: nothing behind this record is read; Fail: the tool has said why (unless quiet)
 struct BamChunkLoop {
     const char* tool; std::string bam; uint64_t voff = 0; size_t chunkBytes = (size_t)32 << 20;
@@ -299,9 +302,11 @@ struct BamChunkLoop {
     double tInflate = 0, tDevice = 0, kernelMs = 0; long long records = 0, chunks = 0, bytesUp = 0;
     bool deviceInflate = false; double inflateKernelMs = 0;      // CANVAS_TOOL_DEVICE_INFLATE; with CANVAS_TOOL_TIMING the device time of canvas_bgzf_inflate
     bool deviceFrame = false; double frameKernelMs = 0; long long framedWrong = 0;      // CANVAS_TOOL_DEVICE_FRAME; the device time of canvas_bam_frame, tiles it walked twice
+    bool checkCrc = false; double crcKernelMs = 0;                // CANVAS_TOOL_CHECK_CRC; on the device paths the device time of canvas_bgzf_crc32
     std::function<void(int32_t)> carried_pos;                   // device framing, an unsorted record: the position it was compared with, before `frame` sees the record
     // the end of the tool's timing line
-    std::string timing_tail() const { char b[192]; snprintf(b, sizeof b, ", \"device_inflate\": %d, \"inflate_kernel_ms\": %.4f, \"device_frame\": %d, \"frame_kernel_ms\": %.4f", deviceInflate ? 1 : 0, inflateKernelMs, deviceFrame ? 1 : 0, frameKernelMs); return b; }
+    std::string timing_tail() const { char b[288]; snprintf(b, sizeof b, ", \"device_inflate\": %d, \"inflate_kernel_ms\": %.4f, \"device_frame\": %d, \"frame_kernel_ms\": %.4f, \"check_crc\": %d, \"crc_kernel_ms\": %.4f",
+                                                             deviceInflate ? 1 : 0, inflateKernelMs, deviceFrame ? 1 : 0, frameKernelMs, checkCrc ? 1 : 0, crcKernelMs); return b; }
     void chunk_bytes_from(const char* envName) { if (const char* e = getenv(envName)) { const long long v = atoll(e); if (v >= 65536) chunkBytes = (size_t)v; } }
     // 0: the file was read to its end or to the record that stopped it, everything is queued and waited for.  1: the device or the runtime failed (message printed).
     // 2: the input was refused (message printed unless quiet, or by frame).  Any other value: what setup returned.
@@ -329,6 +334,8 @@ struct BamChunkLoop {
         if (timing && profile) (void)canvas_profile_enable(ctx, 1);
         { const char* e = getenv("CANVAS_TOOL_DEVICE_FRAME"); deviceFrame = e && atoi(e) == 1; }
         { const char* e = getenv("CANVAS_TOOL_DEVICE_INFLATE"); deviceInflate = deviceFrame || (e && atoi(e) == 1); }
+        checkCrc = bgzf_check_crc();
+        if (timing && checkCrc && deviceInflate) (void)canvas_profile_enable(ctx, 1);
         const size_t hostCap = deviceFrame ? 1 : cap, hostOffCap = deviceFrame ? 1 : offCap;      // (framed on the device: no staging buffers)
         std::unique_ptr<uint8_t[]> hRec[2] = {std::unique_ptr<uint8_t[]>(new uint8_t[hostCap]), std::unique_ptr<uint8_t[]>(new uint8_t[hostCap])};
         std::unique_ptr<uint64_t[]> hOff[2] = {std::unique_ptr<uint64_t[]>(new uint64_t[hostOffCap]), std::unique_ptr<uint64_t[]>(new uint64_t[hostOffCap])};
@@ -348,7 +355,7 @@ struct BamChunkLoop {
             if (timing) (void)canvas_profile_enable(ctx, 1);
         }
         // device inflation: the chunk's stretch of the file, its block table and the statuses, grown as chunks need them (a level-0 block is larger than what it holds)
-        std::unique_ptr<Dev> dComp, dBlk, dStatus; size_t compCap = 0, blkCap = 0; std::vector<canvas_bgzf_block> table;
+        std::unique_ptr<Dev> dComp, dBlk, dStatus, dCrc, dCrcStatus; size_t compCap = 0, blkCap = 0; std::vector<canvas_bgzf_block> table;
         tDevice += Phases::now() - tLoop0;
 
         size_t carry = 0; int cur = 0; bool done = false; std::vector<size_t> pre;
@@ -358,17 +365,18 @@ struct BamChunkLoop {
             if (carry + total > cap) { if (!quiet) fprintf(stderr, "%s: %s: an alignment record larger than %zu bytes\n", tool, bam.c_str(), cap / 2); (void)canvas_synchronize(ctx); return 2; }
             pre.assign(blocks.size() + 1, carry);
             for (size_t i = 0; i < blocks.size(); i++) pre[i + 1] = pre[i] + blocks[i].isize;
-            std::atomic<bool> ok(true);
+            std::atomic<bool> ok(true), crcFailed(false);
             if (deviceInflate) {
                 table.clear();                                                   // (a block of ISIZE 0 is not inflated here either)
-                const size_t compAt = blocks.empty() ? 0 : blocks.front().in, compBytes = blocks.empty() ? 0 : blocks.back().in + blocks.back().clen - compAt;
+                const size_t compAt = blocks.empty() ? 0 : blocks.front().in, compBytes = blocks.empty() ? 0 : blocks.back().in + blocks.back().clen + (checkCrc ? 8 : 0) - compAt;      // (with the last trailer: inside the file, bgzf_parse has seen to it)
                 for (size_t i = 0; i < blocks.size(); i++) if (blocks[i].isize) table.push_back({(uint64_t)(blocks[i].in - compAt), (uint64_t)pre[i], (uint32_t)blocks[i].clen, blocks[i].isize});
                 if (!table.empty()) {
                     if (!dComp || compBytes > compCap || table.size() > blkCap) {      // (!dComp: a first chunk whose blocks hold no deflate data at all)
                         TOOL_TRY(ctx, canvas_synchronize(ctx));                  // chunk k - 1 may still read the buffers that go
                         if (!dComp || compBytes > compCap) { compCap = compBytes + compBytes / 4; dComp.reset(); dComp.reset(new Dev(ctx, (int64_t)compCap)); }
-                        if (table.size() > blkCap) { blkCap = 2 * table.size(); dBlk.reset(); dStatus.reset(); dBlk.reset(new Dev(ctx, (int64_t)(blkCap * sizeof(canvas_bgzf_block)))); dStatus.reset(new Dev(ctx, (int64_t)(blkCap * 4))); }
-                        if (!dComp->p || !dBlk->p || !dStatus->p) { fprintf(stderr, "%s: device allocation failed: %s\n", tool, canvas_last_error(ctx)); return 1; }
+                        if (table.size() > blkCap) { blkCap = 2 * table.size(); dBlk.reset(); dStatus.reset(); dBlk.reset(new Dev(ctx, (int64_t)(blkCap * sizeof(canvas_bgzf_block)))); dStatus.reset(new Dev(ctx, (int64_t)(blkCap * 4)));
+                                                     if (checkCrc) { dCrc.reset(); dCrcStatus.reset(); dCrc.reset(new Dev(ctx, (int64_t)(blkCap * 4))); dCrcStatus.reset(new Dev(ctx, (int64_t)(blkCap * 4))); } }
+                        if (!dComp->p || !dBlk->p || !dStatus->p || (checkCrc && (!dCrc->p || !dCrcStatus->p))) { fprintf(stderr, "%s: device allocation failed: %s\n", tool, canvas_last_error(ctx)); return 1; }
                     }
                     TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dComp->p, F + compAt, (int64_t)compBytes));
                     TOOL_TRY(ctx, canvas_memcpy_h2d_async(ctx, dBlk->p, table.data(), (int64_t)(table.size() * sizeof(canvas_bgzf_block))));
@@ -376,14 +384,23 @@ struct BamChunkLoop {
                     int64_t info[4];
                     TOOL_TRY(ctx, canvas_bgzf_inflate(ctx, dComp->as<uint8_t>(), compBytes, dBlk->as<canvas_bgzf_block>(), (int64_t)table.size(), (uint8_t*)dRec[cur], cap,
                                                       dStatus->as<int32_t>(), info));
+                    if (info[1] == 0 && checkCrc) {
+                        int64_t ci[4];
+                        TOOL_TRY(ctx, canvas_bgzf_crc32(ctx, dComp->as<uint8_t>(), compBytes, dBlk->as<canvas_bgzf_block>(), (int64_t)table.size(), (const uint8_t*)dRec[cur], cap,
+                                                        dStatus->as<int32_t>(), dCrc->as<uint32_t>(), dCrcStatus->as<int32_t>(), ci));
+                        if (ci[1] != 0) crcFailed = true;
+                    }
                     if (info[1] != 0) ok = false;
-                    else if (!deviceFrame) TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, buf + carry, (uint8_t*)dRec[cur] + carry, (int64_t)total));
+                    else if (!crcFailed && !deviceFrame) TOOL_TRY(ctx, canvas_memcpy_d2h(ctx, buf + carry, (uint8_t*)dRec[cur] + carry, (int64_t)total));
                 }
             } else
             parallel_for((int64_t)blocks.size(), [&](int64_t i) {
                 const BgzfBlock& b = blocks[(size_t)i];
                 if (b.isize && !inflate_raw(F + b.in, b.clen, buf + pre[(size_t)i], b.isize)) ok = false;
+                else if (b.isize && checkCrc && !bgzf_crc_ok(buf + pre[(size_t)i], b.isize, b.crc)) crcFailed = true;
             });
+            const bool crcBad = ok && crcFailed;      // (a block that does not inflate comes first on every path)
+            if (crcBad) ok = false;
             const size_t len = carry + total;
             // the block_size chain: one offset per record the tool takes; the shape of every record is checked here (the kernels check it again)
             size_t at = skip; skip = 0; int64_t nrec = 0; bool failed = false;
@@ -417,7 +434,7 @@ struct BamChunkLoop {
                 at += 4 + (size_t)bs;
                 if (f == BamFrame::TakeAndStop) { done = true; break; }
             }
-            if (!ok && !quiet) fprintf(stderr, "%s: %s: a BGZF block does not inflate to its recorded size\n", tool, bam.c_str());
+            if (!ok && !quiet) fprintf(stderr, crcBad ? "%s: %s: a BGZF block fails its CRC32\n" : "%s: %s: a BGZF block does not inflate to its recorded size\n", tool, bam.c_str());
             if (!ok || failed) { (void)canvas_synchronize(ctx); return 2; }
             const size_t used = at;
             if (!done && eof && at < len) { if (!quiet) fprintf(stderr, "%s: %s: the file ends inside an alignment record (truncated)\n", tool, bam.c_str()); (void)canvas_synchronize(ctx); return 2; }
@@ -444,6 +461,7 @@ struct BamChunkLoop {
         if (timing && profile) { int32_t launches = 0; (void)canvas_profile_get(ctx, profile, &kernelMs, &launches, 1); }
         if (timing && deviceInflate) { int32_t launches = 0; (void)canvas_profile_get(ctx, "bgzf_inflate", &inflateKernelMs, &launches, 1); }
         if (timing && deviceFrame) { int32_t launches = 0; (void)canvas_profile_get(ctx, "bam_frame", &frameKernelMs, &launches, 1); }
+        if (timing && checkCrc && deviceInflate) { int32_t launches = 0; (void)canvas_profile_get(ctx, "bgzf_crc32", &crcKernelMs, &launches, 1); }
         tDevice += Phases::now() - t3;
         return 0;
     }

@@ -134,11 +134,16 @@ namespace CanvasHipInterop
         [DllImport(Lib)] public static extern int canvas_fragments_from_bam(IntPtr ctx, IntPtr dRecords, ulong nbytes, IntPtr dRecordOffsets, long nrecords, int refId, IntPtr dBinStart,
             IntPtr dBinStop, long nbins, int qualityThreshold, IntPtr dCount, IntPtr dCarry, ulong carryCapacity, IntPtr dState, long[] info);
         // BGZF: the blocks of a BAM inflated on the device, one BgzfBlock (24 bytes) per block; dStatus = int per block (0, or a CANVAS_INFLATE_* code: 1 descriptor, 2 header, 3 input, 4 overrun,
-        // 5 short, 6 distance, 7 code); info = long[4] (blocks, failed, bytes of the good blocks, first failed or -1) or null (queue only).  The CRC32 is not checked
+        // 5 short, 6 distance, 7 code); info = long[4] (blocks, failed, bytes of the good blocks, first failed or -1) or null (queue only).  The CRC32 is not checked here: canvas_bgzf_crc32
         [StructLayout(LayoutKind.Sequential)] public struct BgzfBlock { public ulong SrcOffset; public ulong DstOffset; public uint SrcBytes; public uint OutBytes; }
         [DllImport(Lib)] public static extern int canvas_bgzf_inflate(IntPtr ctx, IntPtr dSrc, ulong srcNbytes, IntPtr dBlocks, long nblocks, IntPtr dDst, ulong dstNbytes, IntPtr dStatus, long[] info);
         // the block table of a BGZF buffer in host memory from file offset `at` (no context): info = long[4] (blocks, next offset, inflated bytes, reason: 0 limit, 1 end, 2 damaged)
         [DllImport(Lib)] public static extern int canvas_bgzf_scan(byte[] hBytes, ulong nbytes, ulong at, ulong maxOutBytes, [Out] BgzfBlock[] hBlocks, long capacity, long[] info);
+        // the CRC32 of every inflated block against the block's trailer word (the descriptors and dDst of canvas_bgzf_inflate; dSrc = IntPtr.Zero: compute only; dInflateStatus =
+        // IntPtr.Zero: every block): dCrc = uint per block, dStatus = int per block (0 ok, 1 mismatch, 2 descriptor, 3 skipped); info = long[4] (blocks, neither ok nor skipped,
+        // bytes summed, first such block or -1) or null (queue only)
+        [DllImport(Lib)] public static extern int canvas_bgzf_crc32(IntPtr ctx, IntPtr dSrc, ulong srcNbytes, IntPtr dBlocks, long nblocks, IntPtr dDst, ulong dstNbytes, IntPtr dInflateStatus,
+            IntPtr dCrc, IntPtr dStatus, long[] info);
         // BAM record framing on the device: the offsets of the records `rule` takes from the block_size chain of a chunk, from byte `first` on (Kind: 0 all, 1 SNV, 2 hits,
         // 3 fragments); dState = long[4] on the device, zeroed before the first chunk; info = long[8] (classified, taken, used, event: 0 none, 1 stopped, 2 malformed, 3 unsorted,
         // 4 capacity; the event's offset or -1; the pos an unsorted record was compared with; tiles walked twice; tile size).  The call waits

@@ -950,7 +950,7 @@ int32_t canvas_call_somatic_ids(canvas_ctx* ctx, int64_t nbins, int32_t nchr, co
 /* A BGZF block is an independent raw-deflate stream of at most 64 KiB in and out.  Block i of d_blocks is the stream d_src[src_offset, src_offset + src_bytes) and has to
  * give exactly out_bytes bytes at d_dst[dst_offset, ...): one wave per block, profile scope "bgzf_inflate".
  *   d_status[i] 0, or why the block failed (CANVAS_INFLATE_*).  0 if and only if zlib's raw inflate (inflateInit2(-15), Z_FINISH) reaches Z_STREAM_END with exactly
- *               out_bytes written, and the bytes are then zlib's.  Unused input behind the final deflate block is accepted; the CRC32 of the BGZF trailer is NOT checked.
+ *               out_bytes written, and the bytes are then zlib's.  Unused input behind the final deflate block is accepted; the CRC32 of the BGZF trailer is NOT checked (canvas_bgzf_crc32 below does that).
  *   ranges      src_bytes and out_bytes are at most 65536; a larger one, or a range outside src_nbytes / dst_nbytes, is CANVAS_INFLATE_DESCRIPTOR for that block and
  *               nothing of it is read or written.  A block reads no byte outside its source range and writes none outside [dst_offset, dst_offset + out_bytes); the
  *               destination bytes of a FAILED block are unspecified (this build leaves them alone).  Destination ranges of different blocks must not overlap.
@@ -977,6 +977,23 @@ int32_t canvas_bgzf_inflate(canvas_ctx* ctx, const uint8_t* d_src, uint64_t src_
 #define CANVAS_BGZF_SCAN_END 1
 #define CANVAS_BGZF_SCAN_DAMAGED 2
 int32_t canvas_bgzf_scan(const uint8_t* h_bytes, uint64_t nbytes, uint64_t at, uint64_t max_out_bytes, canvas_bgzf_block* h_blocks, int64_t capacity, int64_t* h_info);
+/* The CRC32 (RFC 1952, zlib's crc32) of every inflated block, summed on the device and held against the block's trailer: the descriptors of canvas_bgzf_inflate,
+ * unchanged, and the d_dst that call filled.  One workgroup per block, profile scope "bgzf_crc32".
+ *   d_crc[i]          the CRC32 of d_dst[dst_offset, dst_offset + out_bytes); 0 for out_bytes == 0 and for a block that is not summed (DESCRIPTOR, SKIPPED).
+ *   d_status[i]       CANVAS_CRC_*.  The expected value is the little-endian word at d_src[src_offset + src_bytes, + 4): the BGZF trailer follows the deflate data.
+ *   d_src             NULL: compute only, nothing is compared and every block with a valid data range is CANVAS_CRC_OK.
+ *   d_inflate_status  NULL: every block is checked.  Otherwise the statuses canvas_bgzf_inflate left: a block whose status is not 0 is CANVAS_CRC_SKIPPED.
+ *   h_info            NULL: the call only queues work on the context's stream.  Otherwise int64[4], and the call waits: [0] blocks, [1] blocks whose status is neither
+ *                     OK nor SKIPPED, [2] bytes summed (OK and MISMATCH blocks), [3] index of the first block counted in [1] (-1: none).
+ * No byte outside a block's data range and its trailer word is read.
+ * CANVAS_ERR_INVALID: NULL context, negative nblocks, NULL d_blocks / d_dst / d_crc / d_status with nblocks > 0.  nblocks == 0 launches nothing. */
+#define CANVAS_CRC_OK 0
+#define CANVAS_CRC_MISMATCH 1      /* computed != the trailer's */
+#define CANVAS_CRC_DESCRIPTOR 2    /* out_bytes > 65536, a data range outside dst_nbytes, or (d_src given) a trailer outside src_nbytes */
+#define CANVAS_CRC_SKIPPED 3       /* d_inflate_status given and nonzero for this block: nothing read */
+int32_t canvas_bgzf_crc32(canvas_ctx* ctx, const uint8_t* d_src, uint64_t src_nbytes, const canvas_bgzf_block* d_blocks, int64_t nblocks,
+                          const uint8_t* d_dst, uint64_t dst_nbytes, const int32_t* d_inflate_status,
+                          uint32_t* d_crc, int32_t* d_status, int64_t* h_info);
 
 /* ---- BAM record framing on the device: d_record_offsets of the three readers above from the bytes canvas_bgzf_inflate leaves ------------------------------ */
 /* d_records[0, nbytes) holds raw record bytes; the block_size chain starts at `first`: next(o) = o + 4 + block_size(o).  The call writes the offsets of the records

@@ -146,7 +146,7 @@ for mb in sizes:
         del d_src, d_blk, d_out, d_st
     say(**row)
 
-if not a.no_tool and not a.no_device:
+if not a.no_tool:                                             # (also without a device: tools/crc_probe.py takes its inputs from here)
     with open(fa, "wb") as f:
         f.write(b">chrP\n" + ref[:span].tobytes() + b"\n")
     with open(bed, "w") as f:
@@ -154,6 +154,7 @@ if not a.no_tool and not a.no_device:
     with open(vcf, "w") as f:
         f.write("##fileformat=VCFv4.1\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tS1\n")
         f.write("".join("chrP\t%d\t.\t%s\t%s\t50\tPASS\t.\tGT\t0/1\n" % (p + 1, chr(ref[p]), "ACGT"[("ACGT".index(chr(ref[p])) + 1) % 4]) for p in range(500, span, 1000)))
+if not a.no_tool and not a.no_device:
     bindir = os.path.join(ROOT, "canvas_amd", "bin")
     tools = (("CanvasSNV", "[snv] ", [os.path.join(bindir, "CanvasSNV"), "-c", "chrP", "-v", vcf, "-b", bam, "-o", os.path.join(a.dir, "snv.txt.gz")]),
              ("CanvasBin -c", "[bam] ", [os.path.join(bindir, "CanvasBin"), "-b", bam, "-r", fa, "-c", "chrP", "-o", os.path.join(a.dir, "chrP.dat"), "-d", "100", "-m", "5", "-p"]),
